@@ -7,7 +7,7 @@ src/mc/mc_moves.c:378-488) + one energy() on the device through the C ABI + Metr
 C host layer of mpmc_amd/host/ (system_t, energy(), checkpoint/make_move/restore), called via ctypes.
 energy() is evaluated incrementally -- everything pairwise is resident and only what the moved
 molecule touches is recomputed, bit-identical to a full evaluation (the reference caches per pair
-too, pairs.c:238-249) -- and `full_rebuild_steps_per_s` in the line is the same chain with every
+too, pairs.c:238-249) -- and `full_rebuild_steps_per_s` in the --full line is the same chain with every
 cached unit rebuilt every step.  Workload: the 4096-atom PCN-61 cell + 416 BSSP H2 of
 tests/golden/pcn61_bssp_4096.npz with the flags of the reference's sample_configs_gpu/3_PCN61/iter.inp
 run as NVT (Jacobi x4, cutoff 8 A, FH 4th order) -- BASELINE.json configs[3]; `--workload` selects
@@ -24,10 +24,19 @@ processes, before this process has imported torch or touched HIP) and relays ran
 `--gpus` must equal WORLD_SIZE.  Prints ONE JSON line on rank 0.
 
 Measurement layout: the timed region carries NO events or probes (value does not depend on how the
-roofline is sampled); afterwards, untimed: (1) a roofline pass -- HIP events on the engine's own stream
-around every launch of the dominant kernel, raw mean, nothing subtracted; (2) a pass with every kernel
-class timed; (3) one full (non-incremental) evaluation for the pairs/s of the VALU-bound kernels; (4) the
-same chain with --full-rebuild semantics; (5) the CPU baseline (rank 0, N = 1 only).
+roofline is sampled).  A plain run stops there: set-up, warm-up, the --steps timed steps, the outputs of
+--dump-outputs DIR, the JSON line.  With --full it goes on, untimed: (1) a roofline pass -- HIP events on
+the engine's own stream around every launch of the dominant kernel, raw mean, nothing subtracted; (2) a
+pass with every kernel class timed; (3) one full (non-incremental) evaluation for the pairs/s of the
+VALU-bound kernels; (4) the same chain with --full-rebuild semantics; (5) the CPU baseline (rank 0, N = 1
+only; --no-cpu-baseline skips it).
+
+--dump-outputs DIR writes, after the timed steps and before anything else touches the chain, what the
+timed path hands its caller on rank 0 as DIR/<name>.npy (float64): the configuration the chain reached
+(`positions`), its observables (`observables`: energy, coulombic, rd, polarization, N, polar iterations,
+accepted, rejected), the induced dipoles and fields of its last energy() (`dipoles`, `ef_static`,
+`ef_induced`, polarizable workloads) and the pooled walker averages (`walker_averages`); with several walkers
+per GPU, walker w > 0 adds `w<w>_` in front of its names.  Inputs depend only on the arguments (seeded).
 
 A/B switches (none changes what is computed; see include/mpmc_hip.h for the engine options behind them):
   --expanded-matrix / --full-sweep / --full-rebuild, --uvt, --walkers-per-gpu W, and the environment variables
@@ -61,6 +70,11 @@ def parse_args(argv=None):
     ap.add_argument("--workload", default="pcn61_4096")
     ap.add_argument("--corrtime", type=int, default=10)
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the untimed passes (roofline, per-kernel times, VALU pairs/s, "
+                         "full rebuild) and the CPU baseline, and add their figures to the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0,
                     help="seconds of single-core CPU work for the cpu_baseline sample (20 for the headline; the per-size "
@@ -312,6 +326,38 @@ def cpu_baseline(workload, budget_s=20.0, all_cores=True):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, chains, flags, averages):
+    """What the timed path hands its caller after its last step, as float64 .npy files (see the module docstring)."""
+    import numpy as np
+
+    arrays = {}
+    for w, ch in enumerate(chains):
+        pre = "w%d_" % w if w else ""
+        o = ch.observables()
+        arrays[pre + "positions"] = ch.positions()
+        arrays[pre + "observables"] = np.array([o[k] for k in ("energy", "coulombic_energy", "rd_energy",
+                                                               "polarization_energy", "N", "polar_iterations",
+                                                               "accept", "reject")], dtype=np.float64)
+        if flags.get("polarization"):
+            d = ch.dipoles()
+            arrays[pre + "dipoles"] = d["mu"]
+            arrays[pre + "ef_static"] = d["ef_static"]
+            arrays[pre + "ef_induced"] = d["ef_induced"]
+    arrays["walker_averages"] = np.array([averages[k] for k in ("samples", "energy", "energy_sdom", "rd_energy",
+                                                                "coulombic_energy", "polarization_energy",
+                                                                "polar_iterations", "acceptance")], dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
+
+
 # ---------------------------------------------------------------------------------------------------
 # the launch check: launcher + seeds + pooling, no GPU
 # ---------------------------------------------------------------------------------------------------
@@ -507,37 +553,41 @@ def main():
     if dist is not None:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
+    averages = avg.summary()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, chains, flags, averages)
 
-    # ---- untimed pass 1: the dominant kernel under HIP events on the engine's stream, every launch, raw mean
-    nprobe = 96
-    chain.set_option("timing", 1)
-    chain.set_option("timing_interval", 1)
-    chain.enable_timing(True)
-    chain.mc_steps(nprobe)
-    acc = chain.timings()
-    # ---- untimed pass 2: every kernel class
-    nb = 32
-    chain.set_option("timing", 2)
-    chain.enable_timing(True)
-    chain.mc_steps(nb)
-    brk = chain.timings()
-    # ---- untimed pass 3: one full (non-incremental) evaluation: the VALU-bound pair / field kernels over all tiles
-    chain.set_option("incremental_pairs", 0)
-    chain.enable_timing(True)
-    chain.mc_steps(4)
-    full = chain.timings()
-    chain.set_option("incremental_pairs", 1)
-    # ---- untimed pass 4: the same chain with every cached unit rebuilt every step
-    chain.set_option("timing", 0)
-    chain.set_option("incremental_amatrix", 0)
-    chain.set_option("incremental_pairs", 0)
-    nfr = max(10, min(200, args.steps // 4))
-    chain.mc_steps(5)
-    torch.cuda.synchronize(dev)
-    tf0 = time.perf_counter()
-    chain.mc_steps(nfr)
-    torch.cuda.synchronize(dev)
-    full_rebuild_rate = nfr / (time.perf_counter() - tf0)
+    if args.full:
+        # ---- untimed pass 1: the dominant kernel under HIP events on the engine's stream, every launch, raw mean
+        nprobe = 96
+        chain.set_option("timing", 1)
+        chain.set_option("timing_interval", 1)
+        chain.enable_timing(True)
+        chain.mc_steps(nprobe)
+        acc = chain.timings()
+        # ---- untimed pass 2: every kernel class
+        nb = 32
+        chain.set_option("timing", 2)
+        chain.enable_timing(True)
+        chain.mc_steps(nb)
+        brk = chain.timings()
+        # ---- untimed pass 3: one full (non-incremental) evaluation: the VALU-bound pair / field kernels over all tiles
+        chain.set_option("incremental_pairs", 0)
+        chain.enable_timing(True)
+        chain.mc_steps(4)
+        full = chain.timings()
+        chain.set_option("incremental_pairs", 1)
+        # ---- untimed pass 4: the same chain with every cached unit rebuilt every step
+        chain.set_option("timing", 0)
+        chain.set_option("incremental_amatrix", 0)
+        chain.set_option("incremental_pairs", 0)
+        nfr = max(10, min(200, args.steps // 4))
+        chain.mc_steps(5)
+        torch.cuda.synchronize(dev)
+        tf0 = time.perf_counter()
+        chain.mc_steps(nfr)
+        torch.cuda.synchronize(dev)
+        full_rebuild_rate = nfr / (time.perf_counter() - tf0)
 
     # engine counters that would silently change what the headline measures (cumulative over this rank's whole run)
     ctr = chain.timings()
@@ -555,11 +605,6 @@ def main():
 
     if rank == 0:
         value = world * W * args.steps / elapsed
-        sweep_raw_ms = acc["sweep_ms"] / max(1, acc["sweep_count"])
-        event_pair_ms = acc["event_pair_ms"] / max(1, acc["event_pair_count"])
-        # algorithmic bytes of one sweep launch (pair_sweep_kernel): one {c3, c5} coefficient pair (16 B, fp64)
-        # per unordered pair of polarizable sites, read once, + coordinates and dipoles in, field out.
-        # (sites with alpha = 0 carry no dipole, so neither their rows nor their columns exist)
         n_pol_initial = int(np.count_nonzero(np.asarray(system["alpha"]) != 0.0))
         n_pol, n_final = n_pol_initial, n
         if args.uvt:
@@ -570,75 +615,6 @@ def main():
             fin = chain.system(system["basis"])
             n_final = len(fin["charge"])
             n_pol = int(np.count_nonzero(fin["alpha"] != 0.0))
-        m3 = 3.0 * n_pol
-        gs = bool(flags.get("polar_gs") or flags.get("polar_gs_ranked"))
-        expanded = (args.expanded_matrix or args.full_sweep) and not gs
-        sym_off = ((n_pol + 127) // 128 * 128) < 2048  # size threshold of the symmetric expanded-matrix kernel
-        nblk = (n_pol + 63) // 64
-        if gs:
-            # gs_chain_kernel (the persistent lower-triangle launch of one exact Gauss-Seidel sweep): the {c3, c5}
-            # coefficients of every tile (t, s <= t-2) (16 B per pair), the sub-diagonal tiles (t, t-1) as expanded
-            # tensors (48 B per pair), the cached inverse of every diagonal block (32 x 9 x 64 doubles) and the vectors.
-            # (Round 2's accounting, kept so that the fraction stays comparable: round 3's kernel reads MORE than this --
-            # the cached matrices P_t, Q_t at 72 B per pair of the tiles (t, t-1), (t, t-2) -- by design, to shorten the
-            # chain; the PMC traffic in profiles/ shows what it really moves.)
-            sweep_bytes = (max(nblk - 1, 0) * max(nblk - 2, 0) / 2) * 4096 * 16 + max(nblk - 1, 0) * 4096 * 48 \
-                + nblk * 18432 * 8 + 6 * m3 * 8
-            kernel_name = "gs_chain_kernel"
-        elif not expanded and acc.get("resident_calls", 0) > 0 and acc["sweep_count"] <= nprobe + 1:
-            # small views: the whole solve is ONE launch (jacobi_folded_kernel up to 16 blocks, jacobi_resident_kernel up
-            # to 21) whose tiles stay in registers; priced
-            # at the bytes the sweeps of the solve need algorithmically (n_iter passes over the coefficients), so this
-            # is an EFFECTIVE bandwidth -- the launch itself reads the coefficients from memory once
-            n_iter = int(flags.get("polar_max_iter", 10))
-            sweep_bytes = n_iter * (n_pol * (n_pol - 1) / 2 * 16 + 3 * m3 * 8)
-            kernel_name = ("%s (%d sweeps in one launch, tiles held in registers: effective bandwidth)"
-                           % ("jacobi_folded_kernel" if nblk <= 16 and not os.environ.get("MPMC_RESIDENT_FOLD")
-                              else "jacobi_resident_kernel / jacobi_folded_kernel", n_iter))
-        elif not expanded:
-            sweep_bytes = n_pol * (n_pol - 1) / 2 * 16 + 3 * m3 * 8
-            kernel_name = "pair_sweep_kernel"
-        elif args.full_sweep or sym_off:
-            sweep_bytes = m3 * m3 * 8 + 5 * m3 * 8
-            kernel_name = "sweep_kernel<Jacobi>"
-        else:  # upper triangle of the expanded matrix
-            sweep_bytes = m3 * (m3 + 1) / 2 * 8 + 3 * m3 * 8
-            kernel_name = "symv_kernel"
-        achieved = sweep_bytes / (sweep_raw_ms * 1e-3) / 1e9 if sweep_raw_ms > 0 else 0.0
-        # what the committed rocprofv3 profile of this command says (profiles/run_profile.sh writes it)
-        traffic = None
-        rocprof_ms = None
-        pmc = os.path.join(ROOT, "profiles", "sweep_pmc_latest.json")
-        if os.path.exists(pmc) and args.workload == "pcn61_4096":
-            try:
-                rec = json.load(open(pmc))
-                if kernel_name.split("<")[0].split(" ")[0] in rec.get("kernel", ""):
-                    traffic = rec.get("hbm_bytes_per_launch")
-                    rocprof_ms = rec.get("rocprof_avg_launch_ms")
-            except Exception:
-                traffic = None
-        # VALU-bound kernels over ALL tiles (pass 3): pairs/s and an estimate of the fp64 vector peak they use.
-        # Per pair the screen costs ~31 fp32 operations (counted as 15.5 fp64-equivalents at the 2:1 rate); the ~3 %
-        # of pairs inside the cutoff + margin pay the exact path: minimum image 46 + LJ/FH4 ~70 + erfc/exp ~60 fp64
-        # operations for the pair kernel, 46 + ~25 for the bare-field kernel.  Estimates, stated as such.
-        npair = n * (n - 1) / 2.0
-        pair_s = full["pair_ms"] / 4 * 1e-3
-        field_s = full["field_ms"] / 4 * 1e-3
-        valu = {}
-        if pair_s > 0:
-            valu["pair_rd_es_kernel"] = dict(pairs_per_s=npair / pair_s, ms_full_pass=pair_s * 1e3,
-                                             est_flop_per_pair=15.5 + 0.03 * 176,
-                                             est_frac_fp64_valu_peak=npair * (15.5 + 0.03 * 176) / pair_s / FP64_VALU_PEAK)
-        if field_s > 0:
-            valu["static_field_kernel"] = dict(pairs_per_s=2 * npair / field_s, ms_full_pass=field_s * 1e3,
-                                               est_flop_per_pair=15.5 + 0.03 * 71,
-                                               est_frac_fp64_valu_peak=2 * npair * (15.5 + 0.03 * 71) / field_s / FP64_VALU_PEAK)
-        # what binds the dominant kernel: its coefficient set is re-read by every sweep; below the 256 MB Infinity Cache
-        # those re-reads can be served on-die, so the 8 TB/s HBM figure is the price list, not a proven roof, at that size
-        # (the same kernel at 16 384 atoms, 773 MB of coefficients, is the beyond-cache figure: DESIGN.md section 5)
-        bound_label = "hbm" if sweep_bytes > 256e6 else "hbm (set fits Infinity Cache)"
-        if gs:
-            bound_label = "hbm (latency chain: see DESIGN.md section 3)"
         out = {
             "metric": "MC steps/sec (polarizable, 4096 atoms)",
             "value": value,
@@ -662,42 +638,119 @@ def main():
                        "parallelism": "%d independent walkers, %d per GPU" % (world * W, W),
                        "collective": collective,
                        "rccl_ranks": rccl_ranks},
-            "full_rebuild_steps_per_s": full_rebuild_rate,
             # a dedicated box shows 0 / 0: a resident (one-launch) solve that lost a hand-off is repeated launch by launch
             # and the context stays on that path; a mis-speculated ranked walk is repeated with the host sorting
             "resident_fallbacks": sum(r["resident_fallbacks"] for r in ranks),
             "spec_rank_redos": sum(r["spec_rank_redos"] for r in ranks),
             "resident_calls": sum(r["resident_calls"] for r in ranks),
             "ranks": ranks,
-            "roofline": {"kernel": kernel_name + " (Thole field / dipole sweep)", "bound": bound_label,
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "avg_launch_ms": sweep_raw_ms, "launches": acc["sweep_count"],
-                         "event_pair_ms": event_pair_ms,
-                         "rocprof_avg_launch_ms": rocprof_ms,
-                         "algorithmic_bytes_per_launch": sweep_bytes,
-                         # SURVEY 8(d) asks for these two beside a sweep that does not stream a stored matrix:
-                         "pairs_per_s": (n_pol * (n_pol - 1) / 2) / (sweep_raw_ms * 1e-3) if sweep_raw_ms > 0 else 0.0,
-                         "effective_GBps_reference_layout": ((m3 * m3 * 8) / (sweep_raw_ms * 1e-3) / 1e9
-                                                             if sweep_raw_ms > 0 else 0.0),
-                         "note": "avg_launch_ms = raw mean of HIP-event pairs on the engine's stream around every launch "
-                                 "of the kernel in a separate untimed pass of %d steps (nothing subtracted: an event pair "
-                                 "itself adds event_pair_ms, so this is an upper bound of the kernel time and frac a lower "
-                                 "bound; rocprof_avg_launch_ms is the committed rocprofv3 mean of the same command); "
-                                 "achieved = bytes this design moves (16 B per unordered pair); "
-                                 "effective_GBps_reference_layout prices the same time at the reference's (3N)^2 x 8 B "
-                                 "matrix and is not a bandwidth claim; the 87 MB coefficient set is re-read every sweep and "
-                                 "fits the 256 MB Infinity Cache, so part of the traffic may be served on-die (FETCH_SIZE "
-                                 "counts memory-side requests including such hits)" % nprobe},
-            "valu_kernels": valu,
-            "device_ms_per_step": dict({k: brk[k] / nb for k in
-                                        ("pair_ms", "recip_ms", "field_ms", "amatrix_ms", "sweep_ms", "palmo_ms",
-                                         "other_ms", "total_ms")},
-                                       note="separate untimed pass of %d steps with every kernel class timed" % nb),
-            "walker_averages": avg.summary(),
+            "walker_averages": averages,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args.workload, budget_s=args.cpu_budget, all_cores=bool(args.cpu_all_cores))
+        if args.full:
+            sweep_raw_ms = acc["sweep_ms"] / max(1, acc["sweep_count"])
+            event_pair_ms = acc["event_pair_ms"] / max(1, acc["event_pair_count"])
+            # algorithmic bytes of one sweep launch (pair_sweep_kernel): one {c3, c5} coefficient pair (16 B, fp64)
+            # per unordered pair of polarizable sites, read once, + coordinates and dipoles in, field out.
+            # (sites with alpha = 0 carry no dipole, so neither their rows nor their columns exist)
+            m3 = 3.0 * n_pol
+            gs = bool(flags.get("polar_gs") or flags.get("polar_gs_ranked"))
+            expanded = (args.expanded_matrix or args.full_sweep) and not gs
+            sym_off = ((n_pol + 127) // 128 * 128) < 2048  # size threshold of the symmetric expanded-matrix kernel
+            nblk = (n_pol + 63) // 64
+            if gs:
+                # gs_chain_kernel (the persistent lower-triangle launch of one exact Gauss-Seidel sweep): the {c3, c5}
+                # coefficients of every tile (t, s <= t-2) (16 B per pair), the sub-diagonal tiles (t, t-1) as expanded
+                # tensors (48 B per pair), the cached inverse of every diagonal block (32 x 9 x 64 doubles) and the vectors.
+                # (Round 2's accounting, kept so that the fraction stays comparable: round 3's kernel reads MORE than this --
+                # the cached matrices P_t, Q_t at 72 B per pair of the tiles (t, t-1), (t, t-2) -- by design, to shorten the
+                # chain; the PMC traffic in profiles/ shows what it really moves.)
+                sweep_bytes = (max(nblk - 1, 0) * max(nblk - 2, 0) / 2) * 4096 * 16 + max(nblk - 1, 0) * 4096 * 48 \
+                    + nblk * 18432 * 8 + 6 * m3 * 8
+                kernel_name = "gs_chain_kernel"
+            elif not expanded and acc.get("resident_calls", 0) > 0 and acc["sweep_count"] <= nprobe + 1:
+                # small views: the whole solve is ONE launch (jacobi_folded_kernel up to 16 blocks, jacobi_resident_kernel up
+                # to 21) whose tiles stay in registers; priced
+                # at the bytes the sweeps of the solve need algorithmically (n_iter passes over the coefficients), so this
+                # is an EFFECTIVE bandwidth -- the launch itself reads the coefficients from memory once
+                n_iter = int(flags.get("polar_max_iter", 10))
+                sweep_bytes = n_iter * (n_pol * (n_pol - 1) / 2 * 16 + 3 * m3 * 8)
+                kernel_name = ("%s (%d sweeps in one launch, tiles held in registers: effective bandwidth)"
+                               % ("jacobi_folded_kernel" if nblk <= 16 and not os.environ.get("MPMC_RESIDENT_FOLD")
+                                  else "jacobi_resident_kernel / jacobi_folded_kernel", n_iter))
+            elif not expanded:
+                sweep_bytes = n_pol * (n_pol - 1) / 2 * 16 + 3 * m3 * 8
+                kernel_name = "pair_sweep_kernel"
+            elif args.full_sweep or sym_off:
+                sweep_bytes = m3 * m3 * 8 + 5 * m3 * 8
+                kernel_name = "sweep_kernel<Jacobi>"
+            else:  # upper triangle of the expanded matrix
+                sweep_bytes = m3 * (m3 + 1) / 2 * 8 + 3 * m3 * 8
+                kernel_name = "symv_kernel"
+            achieved = sweep_bytes / (sweep_raw_ms * 1e-3) / 1e9 if sweep_raw_ms > 0 else 0.0
+            # what the committed rocprofv3 profile of this command says (profiles/run_profile.sh writes it)
+            traffic = None
+            rocprof_ms = None
+            pmc = os.path.join(ROOT, "profiles", "sweep_pmc_latest.json")
+            if os.path.exists(pmc) and args.workload == "pcn61_4096":
+                try:
+                    rec = json.load(open(pmc))
+                    if kernel_name.split("<")[0].split(" ")[0] in rec.get("kernel", ""):
+                        traffic = rec.get("hbm_bytes_per_launch")
+                        rocprof_ms = rec.get("rocprof_avg_launch_ms")
+                except Exception:
+                    traffic = None
+            # VALU-bound kernels over ALL tiles (pass 3): pairs/s and an estimate of the fp64 vector peak they use.
+            # Per pair the screen costs ~31 fp32 operations (counted as 15.5 fp64-equivalents at the 2:1 rate); the ~3 %
+            # of pairs inside the cutoff + margin pay the exact path: minimum image 46 + LJ/FH4 ~70 + erfc/exp ~60 fp64
+            # operations for the pair kernel, 46 + ~25 for the bare-field kernel.  Estimates, stated as such.
+            npair = n * (n - 1) / 2.0
+            pair_s = full["pair_ms"] / 4 * 1e-3
+            field_s = full["field_ms"] / 4 * 1e-3
+            valu = {}
+            if pair_s > 0:
+                valu["pair_rd_es_kernel"] = dict(pairs_per_s=npair / pair_s, ms_full_pass=pair_s * 1e3,
+                                                 est_flop_per_pair=15.5 + 0.03 * 176,
+                                                 est_frac_fp64_valu_peak=npair * (15.5 + 0.03 * 176) / pair_s / FP64_VALU_PEAK)
+            if field_s > 0:
+                valu["static_field_kernel"] = dict(pairs_per_s=2 * npair / field_s, ms_full_pass=field_s * 1e3,
+                                                   est_flop_per_pair=15.5 + 0.03 * 71,
+                                                   est_frac_fp64_valu_peak=2 * npair * (15.5 + 0.03 * 71) / field_s / FP64_VALU_PEAK)
+            # what binds the dominant kernel: its coefficient set is re-read by every sweep; below the 256 MB Infinity Cache
+            # those re-reads can be served on-die, so the 8 TB/s HBM figure is the price list, not a proven roof, at that size
+            # (the same kernel at 16 384 atoms, 773 MB of coefficients, is the beyond-cache figure: DESIGN.md section 5)
+            bound_label = "hbm" if sweep_bytes > 256e6 else "hbm (set fits Infinity Cache)"
+            if gs:
+                bound_label = "hbm (latency chain: see DESIGN.md section 3)"
+            out.update({
+                "full_rebuild_steps_per_s": full_rebuild_rate,
+                "roofline": {"kernel": kernel_name + " (Thole field / dipole sweep)", "bound": bound_label,
+                             "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                             "avg_launch_ms": sweep_raw_ms, "launches": acc["sweep_count"],
+                             "event_pair_ms": event_pair_ms,
+                             "rocprof_avg_launch_ms": rocprof_ms,
+                             "algorithmic_bytes_per_launch": sweep_bytes,
+                             # SURVEY 8(d) asks for these two beside a sweep that does not stream a stored matrix:
+                             "pairs_per_s": (n_pol * (n_pol - 1) / 2) / (sweep_raw_ms * 1e-3) if sweep_raw_ms > 0 else 0.0,
+                             "effective_GBps_reference_layout": ((m3 * m3 * 8) / (sweep_raw_ms * 1e-3) / 1e9
+                                                                 if sweep_raw_ms > 0 else 0.0),
+                             "note": "avg_launch_ms = raw mean of HIP-event pairs on the engine's stream around every launch "
+                                     "of the kernel in a separate untimed pass of %d steps (nothing subtracted: an event pair "
+                                     "itself adds event_pair_ms, so this is an upper bound of the kernel time and frac a lower "
+                                     "bound; rocprof_avg_launch_ms is the committed rocprofv3 mean of the same command); "
+                                     "achieved = bytes this design moves (16 B per unordered pair); "
+                                     "effective_GBps_reference_layout prices the same time at the reference's (3N)^2 x 8 B "
+                                     "matrix and is not a bandwidth claim; the 87 MB coefficient set is re-read every sweep and "
+                                     "fits the 256 MB Infinity Cache, so part of the traffic may be served on-die (FETCH_SIZE "
+                                     "counts memory-side requests including such hits)" % nprobe},
+                "valu_kernels": valu,
+                "device_ms_per_step": dict({k: brk[k] / nb for k in
+                                            ("pair_ms", "recip_ms", "field_ms", "amatrix_ms", "sweep_ms", "palmo_ms",
+                                             "other_ms", "total_ms")},
+                                           note="separate untimed pass of %d steps with every kernel class timed" % nb),
+            })
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(args.workload, budget_s=args.cpu_budget, all_cores=bool(args.cpu_all_cores))
         print(json.dumps(out))
     if identical:
         sys.stderr.write("bench.py: walkers with IDENTICAL averages %s -- the ranks ran the same chain (seed + rank not "

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--full",
                         "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -34,6 +34,35 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     # the counters that would silently change what the line measures: a dedicated box shows 0 / 0
     assert d["resident_fallbacks"] == 0 and d["spec_rank_redos"] == 0
     assert len(d["ranks"]) == 1 and d["ranks"][0]["rank"] == 0 and d["ranks"][0]["steps_per_s"] > 10.0
+
+
+def test_plain_bench_is_the_headline_only_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run times --steps steps and prints the headline fields without the untimed passes of --full;
+    --dump-outputs writes what the timed chain reached, and the same arguments give the same inputs, hence outputs."""
+    import numpy as np
+
+    got = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 30 and line["warmup"] == 5 and line["higher_is_better"] is True and line["dtype"] == "f64"
+        assert abs(line["ms_per_step"] - 1e3 / line["value"]) < 1e-9 * line["ms_per_step"]
+        assert line["walker_averages"]["samples"] == 4  # (5 + 30) steps in corrtime intervals of 10: 1 + 3
+        for k2 in ("roofline", "valu_kernels", "device_ms_per_step", "full_rebuild_steps_per_s", "cpu_baseline"):
+            assert k2 not in line, k2
+        files = {f.name[:-4]: np.load(f) for f in d.glob("*.npy")}
+        assert {"positions", "observables", "dipoles", "ef_static", "ef_induced", "walker_averages"} <= set(files)
+        assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in files.values())
+        assert files["positions"].shape == (4096, 3) and files["dipoles"].shape == (4096, 3)
+        assert files["observables"][6] + files["observables"][7] > 0  # accepted + rejected moves of the chain
+        got.append(files)
+    for name, a in got[0].items():
+        assert np.array_equal(a, got[1][name]), name
 
 
 def test_bench_under_a_launcher_pools_through_the_c_abi_collective_with_one_rank():

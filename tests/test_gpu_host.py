@@ -275,14 +275,14 @@ def test_uvt_chain_that_outgrows_its_context():
     h.close()
 
 
-def test_driver_executable_on_reference_style_input():
+def test_driver_executable_on_reference_style_input(tmp_path):
     """mpmc_hip <input> on the 10-atom box: the step-0 line of its energy_output must carry the
     reference's golden numbers (sample_configs_gpu/cuda_pol.small/noncuda_control/small.energy.dat:2)."""
-    out = "/tmp/mpmc_hip_small.energy.dat"
-    if os.path.exists(out):
-        os.remove(out)
-    r = subprocess.run([host.EXE_PATH, os.path.join(ROOT, "tests", "data", "bssp_small", "input")],
-                       capture_output=True, text=True, timeout=300)
+    from test_reference_inputs import keyword_file
+
+    d = keyword_file(tmp_path, "bssp_small")
+    out = os.path.join(d, "energy.dat")
+    r = subprocess.run([host.EXE_PATH, os.path.join(d, "input")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = open(out).read().splitlines()
     assert lines[0].startswith("#step #energy #coulombic #rd #polar")

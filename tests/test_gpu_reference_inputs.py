@@ -19,7 +19,7 @@ import pytest
 
 from mpmc_amd import engine, host, pqr
 from oracle import oracle
-from test_reference_inputs import DATA, SOCMOF_LINE, pcn61_dir
+from test_reference_inputs import DATA, SOCMOF_LINE, keyword_file, pcn61_dir
 
 pytestmark = pytest.mark.gpu
 
@@ -28,11 +28,10 @@ PCN_FLAGS = dict(temperature=77.0, polarization=1, polar_damp=2.1304, polar_max_
                  feynman_hibbs_order=4)
 
 
-def test_driver_reproduces_the_reference_step0_line_from_its_own_pdb():
-    out = "/tmp/mpmc_hip_socmof.energy.dat"
-    if os.path.exists(out):
-        os.remove(out)
-    r = subprocess.run([host.EXE_PATH, os.path.join(DATA, "socmof", "input")], capture_output=True, text=True, timeout=600)
+def test_driver_reproduces_the_reference_step0_line_from_its_own_pdb(tmp_path):
+    d = keyword_file(tmp_path, "socmof")
+    out = os.path.join(d, "energy.dat")
+    r = subprocess.run([host.EXE_PATH, os.path.join(d, "input")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = open(out).read().splitlines()
     assert lines[0].startswith("#step #energy #coulombic #rd #polar")
@@ -51,10 +50,8 @@ def test_driver_reproduces_the_reference_step0_line_from_its_own_pdb():
 
 def test_pcn61_full_runs_through_the_driver(tmp_path):
     d = pcn61_dir(tmp_path)
-    out = "/tmp/mpmc_hip_pcn61_full.energy.dat"
-    if os.path.exists(out):
-        os.remove(out)
-    r = subprocess.run([host.EXE_PATH, os.path.join(d, "input")], capture_output=True, text=True, timeout=900)
+    out = os.path.join(d, "energy.dat")
+    r =subprocess.run([host.EXE_PATH, os.path.join(d, "input")], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = open(out).read().splitlines()
     assert [l.split()[0] for l in lines[1:]] == ["0", "2", "4"]

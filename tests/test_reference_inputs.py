@@ -18,14 +18,30 @@ DATA = os.path.join(ROOT, "tests", "data")
 SOCMOF_LINE = ["0", "-129043.736570", "-8861.486645", "-93916.094138", "-26266.155787"]  # socMOF+BSSP.energy.dat:2
 
 
+def keyword_file(tmp_path, name, pqr_dir=None):
+    """tests/data/<name>/input copied to tmp_path/<name>/input with its energy_output pointed at
+    tmp_path/<name>/energy.dat and its pqr_input at pqr_dir (default: tests/data/<name>).  Returns the directory."""
+    d = tmp_path / name
+    d.mkdir(exist_ok=True)
+    lines = []
+    for line in open(os.path.join(DATA, name, "input")).read().splitlines():
+        key = line.split()[0] if line.split() else ""
+        if key == "energy_output":
+            line = "energy_output   " + str(d / "energy.dat")
+        elif key == "pqr_input":
+            line = "pqr_input       " + os.path.join(str(pqr_dir or os.path.join(DATA, name)), line.split()[1])
+        lines.append(line)
+    (d / "input").write_text("\n".join(lines) + "\n")
+    return str(d)
+
+
 def pcn61_dir(tmp_path):
     """the 21 183-atom input unpacked beside its keyword file"""
     d = tmp_path / "pcn61_full"
     d.mkdir()
-    shutil.copy(os.path.join(DATA, "pcn61_full", "input"), d / "input")
     with gzip.open(os.path.join(DATA, "pcn61_full", "input.pdb.gz"), "rb") as f, open(d / "input.pdb", "wb") as g:
         shutil.copyfileobj(f, g)
-    return str(d)
+    return keyword_file(tmp_path, "pcn61_full", pqr_dir=d)
 
 
 def host_arrays(path):

@@ -2,7 +2,7 @@
 # Same-box A/B of an environment setting: tools/ab_env.sh "VAR=value [VAR2=value2]" -- <bench.py arguments>; interleaved pairs
 set -e
 setting=$1; shift 2
-run() { python bench.py "$@" --no-cpu-baseline 2>/dev/null | python -c "
+run() { python bench.py --full "$@" --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
@@ -11,7 +11,7 @@ for l in sys.stdin:
 " "$tag"; }
 for rep in 1 2; do
   tag=default; run "$@"
-  tag="$setting"; env $setting python bench.py "$@" --no-cpu-baseline 2>/dev/null | python -c "
+  tag="$setting"; env $setting python bench.py --full "$@" --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

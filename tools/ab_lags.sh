@@ -2,7 +2,7 @@
 # Same-box comparison of the chain's number of cached lags (option gs_lags): bench lines + the chain kernel with and without its source loop
 for rep in 1 2; do
 for L in 2 3 4; do
-  MPMC_GS_LAGS=$L python bench.py "$@" --no-cpu-baseline 2>/dev/null | python -c "
+  MPMC_GS_LAGS=$L python bench.py --full "$@" --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -6,7 +6,7 @@ set -e
 other=$1; label=$2; shift 3
 lib=mpmc_amd/csrc/libmpmc_hip.so
 cp $lib /tmp/ab_tree.so
-run() { python bench.py "$@" --no-cpu-baseline 2>/dev/null | python -c "
+run() { python bench.py --full "$@" --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

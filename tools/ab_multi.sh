@@ -8,7 +8,7 @@ shift
 for rep in $(seq $reps); do
   for s in "${settings[@]}"; do
     if [ "$s" = "-" ]; then e=""; else e="$s"; fi
-    env $e python bench.py "$@" --no-cpu-baseline 2>/dev/null | python -c "
+    env $e python bench.py --full "$@" --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -4,7 +4,7 @@ tag=$1; shift
 export TMPDIR=/tmp
 d=gpurun_out/qs_$tag
 rm -rf $d; mkdir -p $d
-rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python3 bench.py --steps 300 --warmup 30 --no-cpu-baseline "$@" > $d/bench.json 2> $d/err.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python3 bench.py --full --steps 300 --warmup 30 --no-cpu-baseline "$@" > $d/bench.json 2> $d/err.txt
 f=$(find $d -name "*kernel_stats.csv" | head -1)
 python3 - "$f" > gpurun_out/${tag}_stats.txt <<'PY'
 import csv, sys
