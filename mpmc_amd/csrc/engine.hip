@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <tuple>
 #include <utility>
 #include <ctime>
@@ -79,6 +80,72 @@ extern "C" int mpmc_hip_device_count(void) {
 // ------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------
+// Owners of the context's device memory, pinned host memory, streams and events: move-only, released by their
+// destructors.  They convert to the raw pointer / handle, so that kernel arguments and HIP calls take them as they are.
+template <typename T, bool kPinned>
+class HipBuffer {
+  public:
+    HipBuffer() = default;
+    HipBuffer(HipBuffer &&o) noexcept : p_(std::exchange(o.p_, nullptr)), n_(std::exchange(o.n_, 0)) {}
+    ~HipBuffer() { reset(); }
+    // frees the current block, then allocates `count` elements (host_flags: hipHostMalloc's); empty on failure
+    hipError_t alloc(size_t count, unsigned host_flags = hipHostMallocDefault) {
+        reset();
+        void *p = nullptr;
+        hipError_t e;
+        if constexpr (kPinned)
+            e = hipHostMalloc(&p, count * sizeof(T), host_flags);
+        else
+            e = hipMalloc(&p, count * sizeof(T));
+        if (e == hipSuccess) p_ = static_cast<T *>(p), n_ = count;
+        return e;
+    }
+    void reset() {
+        if (p_) {
+            if constexpr (kPinned)
+                hipHostFree(p_);
+            else
+                hipFree(p_);
+        }
+        p_ = nullptr;
+        n_ = 0;
+    }
+    T *get() const { return p_; }
+    size_t size() const { return n_; }  // elements
+    operator T *() const { return p_; }
+
+  private:
+    T *p_ = nullptr;
+    size_t n_ = 0;
+};
+template <typename T>
+using DevBuf = HipBuffer<T, false>;
+template <typename T>
+using PinnedBuf = HipBuffer<T, true>;
+
+template <typename H, hipError_t (*kDestroy)(H)>
+class HipHandle {
+  public:
+    HipHandle() = default;
+    HipHandle(HipHandle &&o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
+    ~HipHandle() { reset(); }
+    // releases the current handle; returns where a create call writes the new one
+    H *out() {
+        reset();
+        return &h_;
+    }
+    operator H() const { return h_; }
+
+  private:
+    void reset() {
+        if (h_) kDestroy(h_);
+        h_ = nullptr;
+    }
+    H h_ = nullptr;
+};
+using HipStream = HipHandle<hipStream_t, hipStreamDestroy>;
+using HipEvent = HipHandle<hipEvent_t, hipEventDestroy>;
+
 constexpr int kMaxDirty = 64;  // more moved atoms than this => full A rebuild (= DirtyList capacity)
 
 enum TimeClass { T_PAIR = 0, T_RECIP, T_FIELD, T_AMAT, T_SWEEP, T_PALMO, T_OTHER, T_EVPAIR, T_NCLASS };
@@ -110,28 +177,25 @@ enum ResSlot {
 // solver: the device matrix is (3 nv)^2 instead of (3 N)^2.
 struct SweepView {
     int nv = 0, nvpad = 0, cap = 0;
-    int *d_idx = nullptr;  // atom index of view slot k
-    double *px = nullptr, *py = nullptr, *pz = nullptr, *palpha = nullptr;
-    int *pflags = nullptr;
-    double *A = nullptr;
-    size_t Acap = 0;  // doubles
+    DevBuf<int> d_idx;  // atom index of view slot k
+    DevBuf<double> px, py, pz, palpha;
+    DevBuf<int> pflags;
+    DevBuf<double> A;
     bool A_valid = false;  // A matches the configuration as of the last energy() (minus `dirty` atoms)
-    double2 *C = nullptr;  // pair-coefficient tiles {c3, c5} (kernels_coef.h), the default sweep storage
+    DevBuf<double2> C;  // pair-coefficient tiles {c3, c5} (kernels_coef.h), the default sweep storage
     int ntld = 0;          // tile stride of C: the number of 64-atom tiles the view can grow to
-    double *energy_part = nullptr;      // [cap/64][2] per-block sums for U_pol and <rrms>
-    size_t Ccap = 0;       // double2 elements
+    DevBuf<double> energy_part;  // [cap/64][2] per-block sums for U_pol and <rrms>
     bool C_valid = false;
     bool pos_valid = false;  // px/py/pz/palpha/pflags match the configuration (moves are applied to both copies)
     unsigned long long ranked_call = 0;  // view 1: the energy() call that last walked (and so maintained) it
-    int *d_slot = nullptr;  // device copy of slot_of_atom (padded with -1)
+    DevBuf<int> d_slot;  // device copy of slot_of_atom (padded with -1)
     std::vector<int> slot_of_atom;  // atom index -> view slot, -1 if not in the view
-    double *mupub = nullptr;  // Gauss-Seidel chain: the published dipoles of a sweep, planar per block (hand-off buffer)
-    double *es = nullptr, *mu0 = nullptr, *mu1 = nullptr, *munew = nullptr, *y = nullptr, *efind = nullptr,
-           *efchg = nullptr, *rrms = nullptr;
-    unsigned *gsflags = nullptr; // [8] gs_chain_kernel: ticket counter, sticky error word, breadcrumbs
+    DevBuf<double> mupub;  // Gauss-Seidel chain: the published dipoles of a sweep, planar per block (hand-off buffer)
+    DevBuf<double> es, mu0, mu1, munew, y, efind, efchg, rrms;
+    DevBuf<unsigned> gsflags;  // [8] gs_chain_kernel: ticket counter, sticky error word, breadcrumbs
     // Gauss-Seidel chain (kernels_gs_chain.h): cached inverses of the diagonal blocks and expanded sub-diagonal tiles
-    double *Minv = nullptr;      // [cap/64][kMinvDoubles]
-    double *Lnb[kGsMaxLag] = {nullptr, nullptr, nullptr, nullptr};  // [k-1]: [cap/64][kPnbDoubles], L(k)_t = M_t D T(t,t-k)
+    DevBuf<double> Minv;         // [cap/64][kMinvDoubles]
+    DevBuf<double> Lnb[kGsMaxLag];  // [k-1]: [cap/64][kPnbDoubles], L(k)_t = M_t D T(t,t-k)
     int Lnb_lags = 0;            // how many of them are allocated
     int nlag = 0, nlag_built = 0;   // lags this view's chain uses / has matrices for (decided at a whole-view rebuild)
     long long last_full_call = -1;  // energy_calls of the view's last whole rebuild
@@ -141,13 +205,13 @@ struct SweepView {
     unsigned long long M_call = 0;    // energy() call that last maintained them
     int rebuild_from = -1;            // >= 0: the view's order changed from this 64-atom block on (set_sweep_order):
                                       // blocks in front of it keep their data, the rest is rebuilt at the next energy()
-    double *Srow = nullptr, *Zcol = nullptr;  // partial sums of the symmetric sweep
-    size_t symcap = 0;
+    DevBuf<double> Srow;  // partial sums of the symmetric sweep
+    double *Zcol = nullptr;  // (inside Srow)
     // resident Jacobi solver (kernels_resident.h): partial-sum slots (sentinel between calls), published dipoles
-    double *resP = nullptr;
+    DevBuf<double> resP;
     int res_pld = 0;
     bool resP_armed = false;
-    double *respub = nullptr;
+    DevBuf<double> respub;
     std::vector<int> h_idx;
 };
 
@@ -174,16 +238,14 @@ struct mpmc_hip_ctx {
     int device = 0;
     int max_atoms = 0, max_npad = 0;
     int n = 0, npad = 0;
-    hipStream_t stream = nullptr;
+    HipStream stream;
     // SoA configuration (HBM)
-    double *d_x = nullptr, *d_y = nullptr, *d_z = nullptr, *d_q = nullptr, *d_alpha = nullptr, *d_eps = nullptr,
-           *d_sig = nullptr, *d_molmass = nullptr;
-    int *d_mol = nullptr, *d_flags = nullptr;
+    DevBuf<double> d_x, d_y, d_z, d_q, d_alpha, d_eps, d_sig, d_molmass;
+    DevBuf<int> d_mol, d_flags;
     // polarization state: full-size per-atom vectors (atom order) + the two sweep views
     SweepView view[2];
-    double *d_es = nullptr, *d_mu = nullptr, *d_efind = nullptr, *d_efchg = nullptr, *d_rank = nullptr,
-           *d_tmp3 = nullptr;
-    unsigned long long *d_errmax = nullptr;
+    DevBuf<double> d_es, d_mu, d_efind, d_efchg, d_rank, d_tmp3;
+    DevBuf<unsigned long long> d_errmax;
     bool have_polar_result = false;
     // where the last polarization result lives (view order); scattered to atom order on demand
     SweepView *result_view = nullptr;
@@ -245,9 +307,9 @@ struct mpmc_hip_ctx {
     int opt_gs_ablate = 0;                 // timing-only ablations of the chain kernel (wrong results; tools/gs_ablate.py)
     int opt_gs_stamps = 0;                 // diagnostic: time stamps inside the chain kernel (printed by the sweep)
     int opt_inv_stamps = 0;                // diagnostic: time stamps inside gs_block_inverse_kernel (main stream launches)
-    unsigned long long *d_istamps = nullptr;
+    DevBuf<unsigned long long> d_istamps;
     int gs_qoff = 0;                       // offset (doubles) of the q_t hand-off buffer inside a view's mupub
-    unsigned long long *d_stamps = nullptr;
+    DevBuf<unsigned long long> d_stamps;
     int gs_sweeps_this_call = 0;
     int opt_pair_coef = 1;  // Jacobi/Palmo sweeps on pair coefficients (0: on the expanded A matrix)
     int opt_incremental_pairs = 1;  // LJ/Ewald-real and static-field tile partials persist between calls
@@ -255,15 +317,14 @@ struct mpmc_hip_ctx {
     bool pair_part_valid_before = false;  // its value when the energy() call in progress started (after collect_dirty_blocks)
     bool field_part_valid = false;  // same for d_fieldpart (real-space static field)
     int field_key = -1;             // mode / chunking the resident field partials were made with
-    double *d_lrcpart = nullptr;    // tile partials of the (cached) long-range correction
-    double2 *d_sfpart = nullptr;    // [block][nk] partial structure factors of the reciprocal-space sum
-    size_t sfpart_cap = 0;
+    DevBuf<double> d_lrcpart;       // tile partials of the (cached) long-range correction
+    DevBuf<double2> d_sfpart;       // [block][nk] partial structure factors of the reciprocal-space sum
     bool recip_part_valid = false;
-    double *d_recipsum = nullptr;   // [ceil(nk/64)] per-chunk sums of w_k |S(k)|^2, folded by the publish kernel
+    DevBuf<double> d_recipsum;      // [ceil(nk/64)] per-chunk sums of w_k |S(k)|^2, folded by the publish kernel
     int recip_chunks = 0;           // of this call (0: R_RECIP was written directly)
     bool self_valid = false;        // d_res[R_SELF] holds the Ewald self term of the current charges
     double self_alpha = 0.0;
-    double *d_rankpart = nullptr;   // scratch of the ranking metric (per-tile minima)
+    DevBuf<double> d_rankpart;      // scratch of the ranking metric (per-tile minima)
     DirtyBlocks dirty_blocks;       // of the energy() call in progress
     bool in_flight = false;         // between energy_begin() and energy_end()
     // ---- grand-canonical edits (insert_molecule / remove_molecule): c->n is the number of atom SLOTS in use,
@@ -299,35 +360,35 @@ struct mpmc_hip_ctx {
     int opt_timing_interval = 32;  // timing 1 / -1: every how many calls
     int opt_sym_mode = 0;  // bit 0: alternate sweep direction, bit 1: default-policy loads
     int sweep_parity = 0;
-    int *h_dirty = nullptr;         // pinned staging for dirty slots
-    double *h_stage = nullptr;      // pinned staging ring for update_atoms() coordinates
-    size_t stage_cap = 0, stage_used = 0;
-    hipStream_t stream2 = nullptr;  // pair / reciprocal kernels overlap the polarization chain
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    PinnedBuf<int> h_dirty;         // pinned staging for dirty slots
+    PinnedBuf<double> h_stage;      // pinned staging ring for update_atoms() coordinates
+    size_t stage_used = 0;
+    HipStream stream2;              // pair / reciprocal kernels overlap the polarization chain
+    HipEvent ev_fork, ev_join;
     // scratch
-    double *d_pairpart = nullptr;   // [ntile*ntile][4]
-    double *d_fieldpart = nullptr;  // [nchunk][3][npad]
-    KVec *d_kvec = nullptr;
+    DevBuf<double> d_pairpart;      // [ntile*ntile][4]
+    DevBuf<double> d_fieldpart;     // [nchunk][3][npad]
+    DevBuf<KVec> d_kvec;
     int nk = 0;
-    KVecF *d_kvecf = nullptr;  // k list weighted with polar_ewald_alpha (Ewald static field)
-    double2 *d_sf = nullptr;
+    DevBuf<KVecF> d_kvecf;          // k list weighted with polar_ewald_alpha (Ewald static field)
+    DevBuf<double2> d_sf;
     int nkf = 0;
     double kvecf_alpha = -1.0;
     int kvecf_kmax = -1;
     bool kvecf_valid = false;
-    double *d_res = nullptr;  // R_COUNT doubles
-    double *h_res = nullptr;  // pinned, mapped
+    DevBuf<double> d_res;     // R_COUNT doubles
+    PinnedBuf<double> h_res;  // pinned, mapped
     double *h_res_dev = nullptr;
-    double *h_res2 = nullptr;  // the side stream's part of the record (LJ / Ewald sums) with a sequence number of its own
+    PinnedBuf<double> h_res2;  // the side stream's part of the record (LJ / Ewald sums) with a sequence number of its own
     double *h_res2_dev = nullptr;
-    unsigned long long *h_err = nullptr;  // pinned, 1 word
-    unsigned *h_gserr = nullptr;          // pinned: error words of the persistent Gauss-Seidel kernel (2 views)
+    PinnedBuf<unsigned long long> h_err;  // pinned, 1 word
+    PinnedBuf<unsigned> h_gserr;          // pinned: error words of the persistent Gauss-Seidel kernel (2 views)
     bool gs_used[2] = {false, false};
     // polar_gs_ranked without a host round trip: the ranked view (1) is kept for the walk of the previous call and
     // the whole evaluation is enqueued on that assumption; the device compares the new ranking metric with the one
     // that walk was sorted from (d_rank_used) and energy_end() repeats the call the slow way if they differ
-    double *d_rank_used = nullptr;
-    unsigned int *d_rankcnt = nullptr;    // neighbour counters of the ranking metric
+    DevBuf<double> d_rank_used;
+    DevBuf<unsigned int> d_rankcnt;       // neighbour counters of the ranking metric
     std::vector<double> rank_saved;       // host copy of the metric d_rank_used holds (download_ranking sorts it on demand)
     bool perm_ranked = false;             // the last call's sweeps used the ranked walk
     bool rank_used_valid = false;
@@ -340,18 +401,18 @@ struct mpmc_hip_ctx {
     bool rank_on_side = false;            // this call: metric computed and copied to the host on the side stream
     int opt_spec_rank = 1;
     unsigned long long spec_redos = 0;
-    hipEvent_t ev_rank = nullptr;
-    hipStream_t stream3 = nullptr;         // the chain-data builder of the main stream's view runs here, beside that stream's next kernels
-    hipEvent_t ev_bfork = nullptr, ev_bjoin = nullptr;
+    HipEvent ev_rank;
+    HipStream stream3;                     // the chain-data builder of the main stream's view runs here, beside that stream's next kernels
+    HipEvent ev_bfork, ev_bjoin;
     bool build_join_pending = false;       // the main stream has not yet waited for the builder launch of this call
     int opt_gs_build_fork = 1;             // "gs_build_fork": 0 = the builder in the main stream (A/B)
     int opt_gs_side_waves = 0;             // "gs_side_waves": 16 = the OTHER view's rebuild in the side stream always with 16-wave workgroups;
                                            // 0 = the fastest geometry that leaves the chain kernel its CUs
-    int *h_order = nullptr;               // pinned staging of set_sweep_order (2 x max_npad ints)
-    hipEvent_t ev_order = nullptr;
-    double *h_rank = nullptr;             // pinned, max_npad
-    int *h_perm = nullptr;                // pinned, max_npad
-    int *h_slotmap = nullptr;             // pinned, max_npad: an atom -> slot map on its way to the device
+    PinnedBuf<int> h_order;               // pinned staging of set_sweep_order (2 x max_npad ints)
+    HipEvent ev_order;
+    PinnedBuf<double> h_rank;             // pinned, max_npad
+    PinnedBuf<int> h_perm;                // pinned, max_npad
+    PinnedBuf<int> h_slotmap;             // pinned, max_npad: an atom -> slot map on its way to the device
     // host state
     mpmc_hip_params par;
     bool have_params = false, have_box = false, have_atoms = false;
@@ -361,10 +422,10 @@ struct mpmc_hip_ctx {
     double lrc_cached = 0.0;
     int kvec_kmax = -1;
     // timing
-    std::vector<hipEvent_t> ev_pool;
+    std::vector<HipEvent> ev_pool;
     size_t ev_next = 0;
     std::vector<TimeRec> recs;
-    hipEvent_t ev_first = nullptr, ev_last = nullptr;
+    HipEvent ev_first, ev_last;
     bool timed = false;
 };
 
@@ -631,7 +692,8 @@ extern "C" int mpmc_hip_create(mpmc_hip_ctx **out, int device, int max_atoms) {
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail("MPMC_HIP: device %d is %s; this engine is built for gfx950 (MI355X) only", device,
                     prop.gcnArchName);
-    mpmc_hip_ctx *c = new mpmc_hip_ctx();
+    std::unique_ptr<mpmc_hip_ctx> owner(new mpmc_hip_ctx());  // (an early return below frees what was made)
+    mpmc_hip_ctx *c = owner.get();
     c->device = device;
     c->max_atoms = max_atoms;
     c->max_npad = round_up(max_atoms, 128);
@@ -659,97 +721,95 @@ extern "C" int mpmc_hip_create(mpmc_hip_ctx **out, int device, int max_atoms) {
      * the critical path and takes the higher priority. */
     int prio_least = 0, prio_greatest = 0;
     HIPCHK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    HIPCHK(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_greatest));
-    HIPCHK(hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio_least));
-    HIPCHK(hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, prio_greatest));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_bfork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_bjoin, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_rank, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming));
-#define DALLOC(ptr, count, type) HIPCHK(hipMalloc((void **)&(ptr), (count) * sizeof(type)))
-    DALLOC(c->d_x, np, double);
-    DALLOC(c->d_y, np, double);
-    DALLOC(c->d_z, np, double);
-    DALLOC(c->d_q, np, double);
-    DALLOC(c->d_alpha, np, double);
-    DALLOC(c->d_eps, np, double);
-    DALLOC(c->d_sig, np, double);
-    DALLOC(c->d_molmass, np, double);
-    DALLOC(c->d_mol, np, int);
-    DALLOC(c->d_flags, np, int);
-    DALLOC(c->d_es, 3 * np, double);
-    DALLOC(c->d_mu, 3 * np, double);
-    DALLOC(c->d_efind, 3 * np, double);
-    DALLOC(c->d_efchg, 3 * np, double);
-    DALLOC(c->d_tmp3, 3 * np, double);
-    DALLOC(c->d_rank, np, double);
-    DALLOC(c->d_rank_used, np, double);
-    DALLOC(c->d_rankcnt, np, unsigned int);
-    DALLOC(c->d_errmax, 256, unsigned long long);
+    HIPCHK(hipStreamCreateWithPriority(c->stream.out(), hipStreamNonBlocking, prio_greatest));
+    HIPCHK(hipStreamCreateWithPriority(c->stream2.out(), hipStreamNonBlocking, prio_least));
+    HIPCHK(hipStreamCreateWithPriority(c->stream3.out(), hipStreamNonBlocking, prio_greatest));
+    HIPCHK(hipEventCreateWithFlags(c->ev_bfork.out(), hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(c->ev_bjoin.out(), hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(c->ev_fork.out(), hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(c->ev_join.out(), hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(c->ev_rank.out(), hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(c->ev_order.out(), hipEventDisableTiming));
+    HIPCHK(c->d_x.alloc(np));
+    HIPCHK(c->d_y.alloc(np));
+    HIPCHK(c->d_z.alloc(np));
+    HIPCHK(c->d_q.alloc(np));
+    HIPCHK(c->d_alpha.alloc(np));
+    HIPCHK(c->d_eps.alloc(np));
+    HIPCHK(c->d_sig.alloc(np));
+    HIPCHK(c->d_molmass.alloc(np));
+    HIPCHK(c->d_mol.alloc(np));
+    HIPCHK(c->d_flags.alloc(np));
+    HIPCHK(c->d_es.alloc(3 * np));
+    HIPCHK(c->d_mu.alloc(3 * np));
+    HIPCHK(c->d_efind.alloc(3 * np));
+    HIPCHK(c->d_efchg.alloc(3 * np));
+    HIPCHK(c->d_tmp3.alloc(3 * np));
+    HIPCHK(c->d_rank.alloc(np));
+    HIPCHK(c->d_rank_used.alloc(np));
+    HIPCHK(c->d_rankcnt.alloc(np));
+    HIPCHK(c->d_errmax.alloc(256));
     for (SweepView &v : c->view) {
         v.cap = (int)np;
-        DALLOC(v.d_idx, np, int);
-        DALLOC(v.d_slot, np, int);
-        DALLOC(v.px, np, double);
-        DALLOC(v.py, np, double);
-        DALLOC(v.pz, np, double);
-        DALLOC(v.palpha, np, double);
-        DALLOC(v.pflags, np, int);
-        DALLOC(v.es, 3 * np, double);
-        DALLOC(v.mu0, 3 * np, double);
-        DALLOC(v.mu1, 3 * np, double);
-        DALLOC(v.munew, 3 * np, double);
-        DALLOC(v.mupub, kGsMaxLag * (3 * np + 192), double);  // mu_t of a sweep, then (gs_qoff apart) the auxiliary lags' vectors; a spare block each
+        HIPCHK(v.d_idx.alloc(np));
+        HIPCHK(v.d_slot.alloc(np));
+        HIPCHK(v.px.alloc(np));
+        HIPCHK(v.py.alloc(np));
+        HIPCHK(v.pz.alloc(np));
+        HIPCHK(v.palpha.alloc(np));
+        HIPCHK(v.pflags.alloc(np));
+        HIPCHK(v.es.alloc(3 * np));
+        HIPCHK(v.mu0.alloc(3 * np));
+        HIPCHK(v.mu1.alloc(3 * np));
+        HIPCHK(v.munew.alloc(3 * np));
+        HIPCHK(v.mupub.alloc(kGsMaxLag * (3 * np + 192)));  // mu_t of a sweep, then (gs_qoff apart) the auxiliary lags' vectors; a spare block each
         c->gs_qoff = (int)(3 * np + 192);
-        DALLOC(v.y, 3 * np, double);
-        DALLOC(v.efind, 3 * np, double);
-        DALLOC(v.efchg, 3 * np, double);
-        DALLOC(v.rrms, np, double);
-        DALLOC(v.gsflags, 16, unsigned);
+        HIPCHK(v.y.alloc(3 * np));
+        HIPCHK(v.efind.alloc(3 * np));
+        HIPCHK(v.efchg.alloc(3 * np));
+        HIPCHK(v.rrms.alloc(np));
+        HIPCHK(v.gsflags.alloc(16));
         HIPCHK(hipMemsetAsync(v.gsflags, 0, 16 * sizeof(unsigned), c->stream));
-        DALLOC(v.energy_part, 2 * (np / 64 + 1), double);
+        HIPCHK(v.energy_part.alloc(2 * (np / 64 + 1)));
         // slots past the last tile of a view are never written by the tiled sweep: keep them defined
-        for (double *p : {v.mu0, v.mu1, v.munew, v.y, v.efind, v.efchg, v.es})
+        for (double *p : {v.mu0.get(), v.mu1.get(), v.munew.get(), v.y.get(), v.efind.get(), v.efchg.get(), v.es.get()})
             HIPCHK(hipMemsetAsync(p, 0, 3 * np * sizeof(double), c->stream));
         HIPCHK(hipMemsetAsync(v.rrms, 0, np * sizeof(double), c->stream));
     }
     const size_t ntile = np / 64;
-    DALLOC(c->d_pairpart, ntile * ntile * kPairChannels, double);
-    DALLOC(c->d_lrcpart, ntile * ntile, double);
-    DALLOC(c->d_rankpart, ntile * ntile, double);
+    HIPCHK(c->d_pairpart.alloc(ntile * ntile * kPairChannels));
+    HIPCHK(c->d_lrcpart.alloc(ntile * ntile));
+    HIPCHK(c->d_rankpart.alloc(ntile * ntile));
     const size_t nchunk_max = std::max<size_t>(1, np / 64) + 16;  // + k-chunk slots of the Ewald field
-    DALLOC(c->d_fieldpart, nchunk_max * 3 * np, double);
-    DALLOC(c->d_res, R_COUNT, double);
-#undef DALLOC
-    HIPCHK(hipHostMalloc((void **)&c->h_res, (R_COUNT + 1) * sizeof(double), hipHostMallocMapped));
+    HIPCHK(c->d_fieldpart.alloc(nchunk_max * 3 * np));
+    HIPCHK(c->d_res.alloc(R_COUNT));
+    HIPCHK(c->h_res.alloc(R_COUNT + 1, hipHostMallocMapped));
     c->h_res[R_COUNT] = 0.0;
     HIPCHK(hipHostGetDevicePointer((void **)&c->h_res_dev, c->h_res, 0));
-    HIPCHK(hipHostMalloc((void **)&c->h_res2, (R_COUNT + 1) * sizeof(double), hipHostMallocMapped));
+    HIPCHK(c->h_res2.alloc(R_COUNT + 1, hipHostMallocMapped));
     memset(c->h_res2, 0, (R_COUNT + 1) * sizeof(double));
     HIPCHK(hipHostGetDevicePointer((void **)&c->h_res2_dev, c->h_res2, 0));
-    HIPCHK(hipHostMalloc((void **)&c->h_err, sizeof(unsigned long long), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&c->h_gserr, 2 * sizeof(unsigned), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&c->h_rank, np * sizeof(double), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&c->h_perm, np * sizeof(int), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&c->h_slotmap, np * sizeof(int), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&c->h_dirty, kMaxDirty * sizeof(int), hipHostMallocDefault));
-    c->stage_cap = 3 * 4096;
-    HIPCHK(hipHostMalloc((void **)&c->h_stage, c->stage_cap * sizeof(double), hipHostMallocDefault));
+    HIPCHK(c->h_err.alloc(1));
+    HIPCHK(c->h_gserr.alloc(2));
+    HIPCHK(c->h_rank.alloc(np));
+    HIPCHK(c->h_perm.alloc(np));
+    HIPCHK(c->h_slotmap.alloc(np));
+    HIPCHK(c->h_dirty.alloc(kMaxDirty));
+    HIPCHK(c->h_stage.alloc(3 * 4096));
     c->ev_pool.resize(2 * 512);
-    for (auto &e : c->ev_pool) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipEventCreate(&c->ev_first));
-    HIPCHK(hipEventCreate(&c->ev_last));
+    for (auto &e : c->ev_pool) HIPCHK(hipEventCreate(e.out()));
+    HIPCHK(hipEventCreate(c->ev_first.out()));
+    HIPCHK(hipEventCreate(c->ev_last.out()));
     HIPCHK(hipMemsetAsync(c->d_res, 0, R_COUNT * sizeof(double), c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (device < 64) ++g_ctx_on_device[device];
-    *out = c;
+    *out = owner.release();
     return 0;
 }
 
 static void graph_destroy(mpmc_hip_ctx *c);
 
+// the context's members free its buffers, streams and events
 extern "C" void mpmc_hip_destroy(mpmc_hip_ctx *c) {
     if (!c) return;
     if (getenv("MPMC_HIP_HOST_PROFILE") && c->energy_calls)
@@ -760,44 +820,11 @@ extern "C" void mpmc_hip_destroy(mpmc_hip_ctx *c) {
         fprintf(stderr, "MPMC_HIP graph steps: node updates %.1f us, launch %.1f us per step\n",
                 1e6 * c->graph_update_s / c->graph_launches, 1e6 * c->graph_launch_s / c->graph_launches);
     hipSetDevice(c->device);
-    if (c->device < 64) --g_ctx_on_device[c->device];
-    if (c->stream) hipStreamSynchronize(c->stream);
-    if (c->stream2) hipStreamSynchronize(c->stream2);
-    void *dptrs[] = {c->d_x,   c->d_y,     c->d_z,     c->d_q,    c->d_alpha, c->d_eps,      c->d_sig,
-                     c->d_molmass, c->d_mol, c->d_flags, c->d_es, c->d_mu,    c->d_efind,    c->d_efchg,
-                     c->d_tmp3, c->d_rank, c->d_rank_used, c->d_rankcnt, c->d_errmax, c->d_pairpart, c->d_fieldpart, c->d_kvec,
-                     c->d_res,  c->d_kvecf, c->d_sf, c->d_lrcpart, c->d_rankpart, c->d_sfpart, c->d_recipsum, c->d_istamps};
-    for (void *p : dptrs)
-        if (p) hipFree(p);
-    for (SweepView &v : c->view) {
-        void *vp[] = {v.resP, v.respub, v.Srow, v.Minv, v.Lnb[0], v.Lnb[1], v.Lnb[2], v.Lnb[3], v.mupub, v.gsflags, v.d_idx, v.d_slot, v.px, v.py, v.pz, v.palpha, v.pflags, v.A,    v.C, v.energy_part, v.es,
-                      v.mu0,   v.mu1, v.munew, v.y, v.efind, v.efchg, v.rrms};
-        for (void *p : vp)
-            if (p) hipFree(p);
-    }
+    hipStreamSynchronize(c->stream);
+    hipStreamSynchronize(c->stream2);
+    hipStreamSynchronize(c->stream3);
     graph_destroy(c);
-    if (c->stream2) hipStreamDestroy(c->stream2);
-    if (c->stream3) hipStreamDestroy(c->stream3);
-    if (c->ev_bfork) hipEventDestroy(c->ev_bfork);
-    if (c->ev_bjoin) hipEventDestroy(c->ev_bjoin);
-    if (c->ev_fork) hipEventDestroy(c->ev_fork);
-    if (c->ev_join) hipEventDestroy(c->ev_join);
-    if (c->ev_rank) hipEventDestroy(c->ev_rank);
-    if (c->ev_order) hipEventDestroy(c->ev_order);
-    if (c->h_order) hipHostFree(c->h_order);
-    if (c->h_res) hipHostFree(c->h_res);
-    if (c->h_res2) hipHostFree(c->h_res2);
-    if (c->h_err) hipHostFree(c->h_err);
-    if (c->h_gserr) hipHostFree(c->h_gserr);
-    if (c->h_rank) hipHostFree(c->h_rank);
-    if (c->h_perm) hipHostFree(c->h_perm);
-    if (c->h_slotmap) hipHostFree(c->h_slotmap);
-    if (c->h_dirty) hipHostFree(c->h_dirty);
-    if (c->h_stage) hipHostFree(c->h_stage);
-    for (auto &e : c->ev_pool) hipEventDestroy(e);
-    if (c->ev_first) hipEventDestroy(c->ev_first);
-    if (c->ev_last) hipEventDestroy(c->ev_last);
-    if (c->stream) hipStreamDestroy(c->stream);
+    if (c->device < 64) --g_ctx_on_device[c->device];
     delete c;
 }
 
@@ -965,7 +992,7 @@ extern "C" int mpmc_hip_upload(mpmc_hip_ctx *c, int n, const double *x, const do
         HIPCHK(hipMemcpy(v0.d_slot, hs.data(), nall * sizeof(int), hipMemcpyHostToDevice));
     }
     if (v0.C) {  // tiles beyond the ones the coming build rewrites must read as "no pair"
-        HIPCHK(hipMemsetAsync(v0.C, 0, v0.Ccap * sizeof(double2), c->stream));
+        HIPCHK(hipMemsetAsync(v0.C, 0, v0.C.size() * sizeof(double2), c->stream));
     }
     c->all_dirty = true;
     c->dirty_atoms.clear();
@@ -1045,14 +1072,14 @@ extern "C" int mpmc_hip_update_atoms(mpmc_hip_ctx *c, int first, int count, cons
     }
     if (queued) {
         // nothing to launch yet
-    } else if ((size_t)(3 * count) <= c->stage_cap) {
+    } else if ((size_t)(3 * count) <= c->h_stage.size()) {
         if (flush_moves(c)) return -1;
         c->staged_copies = true;
         c->main_writes = true;
         c->view[0].pos_valid = false;
         // small delta (one molecule): stage in pinned memory so the copies are truly asynchronous and the
         // caller's buffers are free at once; the ring is recycled after the next energy() has synchronised
-        if (c->stage_used + 3 * (size_t)count > c->stage_cap) {
+        if (c->stage_used + 3 * (size_t)count > c->h_stage.size()) {
             HIPCHK(hipStreamSynchronize(c->stream));
             c->stage_used = 0;
         }
@@ -1313,7 +1340,7 @@ extern "C" int mpmc_hip_set_sweep_order(mpmc_hip_ctx *c, int count, const int *s
     // staged in pinned memory of their own (the ranked view's staging buffers may still be in flight), copied in
     // stream order: nothing here waits for the device
     if (!c->h_order) {
-        HIPCHK(hipHostMalloc((void **)&c->h_order, 2 * (size_t)c->max_npad * sizeof(int), hipHostMallocDefault));
+        HIPCHK(c->h_order.alloc(2 * (size_t)c->max_npad));
     } else {
         HIPCHK(hipEventSynchronize(c->ev_order));  // the previous use of the staging buffer has been copied
     }
@@ -1367,13 +1394,10 @@ static int build_kvectors(mpmc_hip_ctx *c) {
                 v.w = std::exp(-k2 / (4.0 * alpha * alpha)) / k2;
                 kv.push_back(v);
             }
-    if (c->d_kvec) {
-        hipFree(c->d_kvec);
-        c->d_kvec = nullptr;
-    }
+    c->d_kvec.reset();
     c->nk = (int)kv.size();
     if (c->nk > 0) {
-        HIPCHK(hipMalloc((void **)&c->d_kvec, kv.size() * sizeof(KVec)));
+        HIPCHK(c->d_kvec.alloc(kv.size()));
         HIPCHK(hipMemcpy(c->d_kvec, kv.data(), kv.size() * sizeof(KVec), hipMemcpyHostToDevice));
     }
     c->kvec_valid = true;
@@ -1405,14 +1429,12 @@ static int build_field_kvectors(mpmc_hip_ctx *c) {
                 v.w = std::exp(-k2 / (4.0 * ea * ea)) / k2;
                 kv.push_back(v);
             }
-    if (c->d_kvecf) hipFree(c->d_kvecf);
-    if (c->d_sf) hipFree(c->d_sf);
-    c->d_kvecf = nullptr;
-    c->d_sf = nullptr;
+    c->d_kvecf.reset();
+    c->d_sf.reset();
     c->nkf = (int)kv.size();
     if (c->nkf > 0) {
-        HIPCHK(hipMalloc((void **)&c->d_kvecf, kv.size() * sizeof(KVecF)));
-        HIPCHK(hipMalloc((void **)&c->d_sf, kv.size() * sizeof(double2)));
+        HIPCHK(c->d_kvecf.alloc(kv.size()));
+        HIPCHK(c->d_sf.alloc(kv.size()));
         HIPCHK(hipMemcpy(c->d_kvecf, kv.data(), kv.size() * sizeof(KVecF), hipMemcpyHostToDevice));
     }
     c->kvecf_alpha = ea;
@@ -1424,13 +1446,7 @@ static int build_field_kvectors(mpmc_hip_ctx *c) {
 static int ensure_sym_scratch(SweepView &v) {
     const size_t ncol = 3 * (size_t)v.nvpad;
     const size_t need = ncol * (v.nvpad / kSymChunkAtoms + v.nvpad / kSymRowAtoms);
-    if (v.symcap < need) {
-        if (v.Srow) hipFree(v.Srow);
-        v.Srow = v.Zcol = nullptr;
-        v.symcap = 0;
-        HIPCHK(hipMalloc((void **)&v.Srow, need * sizeof(double)));
-        v.symcap = need;
-    }
+    if (v.Srow.size() < need) HIPCHK(v.Srow.alloc(need));
     v.Zcol = v.Srow + ncol * (v.nvpad / kSymChunkAtoms);
     return 0;
 }
@@ -1439,16 +1455,10 @@ static int ensure_sym_scratch(SweepView &v) {
 static int ensure_coef_scratch(SweepView &v, int nt) {
     const size_t ncol = 3 * (size_t)kCoefTile * nt;
     // sized for every tile the view can grow to: a grand-canonical insertion that starts a new 64-atom block must not
-    // pay a hipFree + hipMalloc (a millisecond, with the device idle) in the middle of an energy() call
+    // pay a free + re-allocation (a millisecond, with the device idle) in the middle of an energy() call
     const size_t ntcap = (size_t)std::max(nt, v.ntld);
     const size_t need = 4 * (3 * (size_t)kCoefTile * ntcap) * ntcap;  // (two planes: whole-tile or half-tile workgroups)
-    if (v.symcap < need) {
-        if (v.Srow) hipFree(v.Srow);
-        v.Srow = v.Zcol = nullptr;
-        v.symcap = 0;
-        HIPCHK(hipMalloc((void **)&v.Srow, need * sizeof(double)));
-        v.symcap = need;
-    }
+    if (v.Srow.size() < need) HIPCHK(v.Srow.alloc(need));
     v.Zcol = v.Srow + ncol * nt;
     return 0;
 }
@@ -1459,15 +1469,11 @@ static int ensure_view_coef(mpmc_hip_ctx *c, SweepView &v, int nt, hipStream_t s
     // never changes; tiles start out as zeros (= "no pair"), which is what unused slots must read as
     const int ntld = std::max(nt, (v.cap + kCoefTile - 1) / kCoefTile);
     const size_t need = (size_t)ntld * ntld * kCoefTile * kCoefTile;
-    if (v.Ccap < need || v.ntld != ntld) {
-        if (v.C) hipFree(v.C);
-        v.C = nullptr;
-        v.Ccap = 0;
-        HIPCHK(hipMalloc((void **)&v.C, need * sizeof(double2)));
+    if (v.C.size() < need || v.ntld != ntld) {
+        HIPCHK(v.C.alloc(need));
         // on the stream that builds the view (the non-blocking streams do not order themselves after the null stream; and
         // a ranked view may be built on the side stream while the main one is busy: a memset queued THERE would come last)
         HIPCHK(hipMemsetAsync(v.C, 0, need * sizeof(double2), st));
-        v.Ccap = need;
         v.ntld = ntld;
         v.C_valid = false;
     }
@@ -1479,11 +1485,11 @@ static int ensure_view_chain(mpmc_hip_ctx *c, SweepView &v, hipStream_t st) {
     if (v.Minv && v.Lnb_lags >= c->opt_gs_lags) return 0;
     const size_t nbcap = (size_t)(v.cap + 63) / 64;
     for (; v.Lnb_lags < c->opt_gs_lags; ++v.Lnb_lags) {
-        HIPCHK(hipMalloc((void **)&v.Lnb[v.Lnb_lags], nbcap * kPnbDoubles * sizeof(double)));
+        HIPCHK(v.Lnb[v.Lnb_lags].alloc(nbcap * kPnbDoubles));
         v.M_epoch = 0;
     }
     if (v.Minv) return 0;
-    HIPCHK(hipMalloc((void **)&v.Minv, nbcap * kMinvDoubles * sizeof(double)));
+    HIPCHK(v.Minv.alloc(nbcap * kMinvDoubles));
     // the folded inverse has 32 padding lanes per block that no build writes: they must read as zero
     HIPCHK(hipMemsetAsync(v.Minv, 0, nbcap * kMinvDoubles * sizeof(double), st));
     v.M_epoch = 0;
@@ -1492,13 +1498,7 @@ static int ensure_view_chain(mpmc_hip_ctx *c, SweepView &v, hipStream_t st) {
 
 static int ensure_view_matrix(SweepView &v) {
     const size_t need = (size_t)(3 * (size_t)v.nvpad) * (3 * (size_t)v.nvpad);
-    if (v.Acap < need) {
-        if (v.A) hipFree(v.A);
-        v.A = nullptr;
-        v.Acap = 0;
-        HIPCHK(hipMalloc((void **)&v.A, need * sizeof(double)));
-        v.Acap = need;
-    }
+    if (v.A.size() < need) HIPCHK(v.A.alloc(need));
     return 0;
 }
 
@@ -1577,9 +1577,7 @@ static int ensure_view_resident(mpmc_hip_ctx *c, SweepView &v) {
     const int pld = std::min(std::max(1, v.ntld), kResMaxBlocks);
     const size_t pstride = (size_t)pld * pld * 384;
     if (!v.resP || v.res_pld != pld) {
-        if (v.resP) hipFree(v.resP);
-        v.resP = nullptr;
-        HIPCHK(hipMalloc((void **)&v.resP, 3 * pstride * sizeof(double)));  // (two parities; three rotating buffers when folded)
+        HIPCHK(v.resP.alloc(3 * pstride));  // (two parities; three rotating buffers when folded)
         v.res_pld = pld;
         v.resP_armed = false;
     }
@@ -1589,7 +1587,7 @@ static int ensure_view_resident(mpmc_hip_ctx *c, SweepView &v) {
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)v.resP, (int)(kGsSentinel & 0xffffffffull), 3 * pstride * 2, c->stream));
         v.resP_armed = true;
     }
-    if (!v.respub) HIPCHK(hipMalloc((void **)&v.respub, (size_t)kResMaxSweeps * 3 * v.cap * sizeof(double)));
+    if (!v.respub) HIPCHK(v.respub.alloc((size_t)kResMaxSweeps * 3 * v.cap));
     return 0;
 }
 
@@ -1923,15 +1921,10 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
         if (ewald_recip) {
             // partial structure factors per 64-atom block stay resident; only the moved blocks are redone
             const size_t need = (size_t)(c->max_npad / 64) * c->nk;
-            if (c->sfpart_cap < need) {
-                if (c->d_sfpart) hipFree(c->d_sfpart);
-                c->d_sfpart = nullptr;
-                c->sfpart_cap = 0;
-                HIPCHK(hipMalloc((void **)&c->d_sfpart, need * sizeof(double2)));
-                if (c->d_recipsum) hipFree(c->d_recipsum);
-                c->d_recipsum = nullptr;
-                HIPCHK(hipMalloc((void **)&c->d_recipsum, ((c->nk + 63) / 64) * sizeof(double)));
-                c->sfpart_cap = need;
+            const size_t nchunk = (c->nk + 63) / 64;
+            if (c->d_sfpart.size() < need || c->d_recipsum.size() < nchunk) {
+                HIPCHK(c->d_sfpart.alloc(need));
+                HIPCHK(c->d_recipsum.alloc(nchunk));
                 c->recip_part_valid = false;
             }
         }
@@ -2288,7 +2281,7 @@ extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
         hipMemcpy(dbg, gv.gsflags, sizeof(dbg), hipMemcpyDeviceToHost);  // (the allocation is exactly 8 words)
         return fail("MPMC_HIP: persistent Gauss-Seidel kernel gave up waiting on a hand-off (spin limit) in view %d: "
                     "workgroup %u thread %u addr-lo 0x%x; mu_new-lo 0x%x",
-                    c->h_gserr[1] ? 1 : 0, dbg[2], dbg[3], dbg[4], (unsigned)((unsigned long long)gv.mupub & 0xffffffffu));
+                    c->h_gserr[1] ? 1 : 0, dbg[2], dbg[3], dbg[4], (unsigned)((unsigned long long)gv.mupub.get() & 0xffffffffu));
     }
     HIPCHK(hipGetLastError());
     c->timed = timed_call;
@@ -2351,14 +2344,13 @@ extern "C" int mpmc_hip_download_amatrix(mpmc_hip_ctx *c, double *A) {
     HIPCHK(hipSetDevice(c->device));
     const size_t n3 = 3 * (size_t)c->n, lda = 3 * (size_t)c->npad;
     if (flush_moves(c)) return -1;
-    double *dA = nullptr;
-    HIPCHK(hipMalloc((void **)&dA, lda * lda * sizeof(double)));
+    DevBuf<double> dA;
+    HIPCHK(dA.alloc(lda * lda));
     hipLaunchKernelGGL(build_amatrix_kernel, dim3(c->npad / 128, c->npad / kARows), dim3(64), 0, c->stream,
                        dev_atoms(c), dev_box(c), c->par.polar_damp, dA, (int)lda);
     hipError_t e = hipMemcpy2DAsync(A, n3 * sizeof(double), dA, lda * sizeof(double), n3 * sizeof(double), n3,
                                     hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(dA);
     if (e != hipSuccess) return fail("MPMC_HIP: download_amatrix: %s", hipGetErrorString(e));
     return 0;
 }
@@ -2420,19 +2412,6 @@ extern "C" int mpmc_hip_get_timings(mpmc_hip_ctx *c, mpmc_hip_timings *t) {
 // RCCL (xGMI) averaging of walker observables.  librccl is bound lazily so that the energy
 // path has no hard dependency on it.
 // ------------------------------------------------------------------------------------------
-struct mpmc_hip_comm {
-    ncclComm_t nccl = nullptr;
-    int device = 0;                // (not the context: a caller may replace its context, e.g. when uvt outgrows it)
-    hipStream_t stream = nullptr;  // of its own: the collective never queues behind (or in front of) an energy()
-    double *d_buf = nullptr;
-    double *h_buf = nullptr;       // pinned staging, so that both copies are truly asynchronous
-    int cap = 0;
-    int nranks = 1, rank = 0;
-    int pending = 0;               // doubles of the all-reduce in flight (0: none)
-    unsigned char *d_gather = nullptr, *h_gather = nullptr;  // mpmc_hip_gather_observables: [send | nranks records]
-    size_t gather_cap = 0;
-};
-
 struct Rccl {
     void *h = nullptr;
     ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
@@ -2444,6 +2423,23 @@ struct Rccl {
     const char *(*GetErrorString)(ncclResult_t) = nullptr;
 };
 static Rccl g_rccl;
+
+struct mpmc_hip_comm {
+    HipStream stream;              // of its own: the collective never queues behind (or in front of) an energy()
+    ncclComm_t nccl = nullptr;
+    int device = 0;                // (not the context: a caller may replace its context, e.g. when uvt outgrows it)
+    DevBuf<double> d_buf;
+    PinnedBuf<double> h_buf;       // pinned staging, so that both copies are truly asynchronous
+    int nranks = 1, rank = 0;
+    int pending = 0;               // doubles of the all-reduce in flight (0: none)
+    DevBuf<unsigned char> d_gather;  // mpmc_hip_gather_observables: [send | nranks records]
+    PinnedBuf<unsigned char> h_gather;
+    // (the caller has set the device; the members free the buffers, then the stream)
+    ~mpmc_hip_comm() {
+        if (stream) hipStreamSynchronize(stream);
+        if (nccl) g_rccl.CommDestroy(nccl);
+    }
+};
 
 static int load_rccl() {
     if (g_rccl.h) return 0;
@@ -2482,27 +2478,20 @@ extern "C" int mpmc_hip_comm_create(mpmc_hip_comm **out, mpmc_hip_ctx *ctx, int 
         return fail("MPMC_HIP: comm_create: bad arguments");
     if (load_rccl()) return -1;
     HIPCHK(hipSetDevice(ctx->device));
-    mpmc_hip_comm *cm = new mpmc_hip_comm();
+    std::unique_ptr<mpmc_hip_comm> cm(new mpmc_hip_comm());  // (an early return below frees what was made)
     cm->device = ctx->device;
     cm->nranks = nranks;
     cm->rank = rank;
     ncclUniqueId u;
     memcpy(u.internal, id, 128);
-    const ncclResult_t rc = g_rccl.CommInitRank(&cm->nccl, nranks, u, rank);
-    if (rc != ncclSuccess) {
-        delete cm;
-        return rccl_fail("ncclCommInitRank", rc);
-    }
-    cm->cap = 64;
-    // (not HIPCHK: a failure here must not leak the communicator the other ranks are now part of)
-    hipError_t e = hipStreamCreateWithFlags(&cm->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&cm->d_buf, cm->cap * sizeof(double));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&cm->h_buf, cm->cap * sizeof(double), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        mpmc_hip_comm_destroy(cm);
-        return fail("MPMC_HIP: comm_create: %s", hipGetErrorString(e));
-    }
-    *out = cm;
+    ncclComm_t nccl = nullptr;  // (cm destroys it only once the init has succeeded)
+    const ncclResult_t rc = g_rccl.CommInitRank(&nccl, nranks, u, rank);
+    if (rc != ncclSuccess) return rccl_fail("ncclCommInitRank", rc);
+    cm->nccl = nccl;
+    HIPCHK(hipStreamCreateWithFlags(cm->stream.out(), hipStreamNonBlocking));
+    HIPCHK(cm->d_buf.alloc(64));
+    HIPCHK(cm->h_buf.alloc(64));
+    *out = cm.release();
     return 0;
 }
 
@@ -2515,7 +2504,7 @@ extern "C" int mpmc_hip_comm_rank(const mpmc_hip_comm *cm) { return cm ? cm->ran
 // caller can run the next corrtime interval's energy() calls in between (the reference blocks in MPI_Gather,
 // mc.c:431).  One collective in flight per communicator.
 extern "C" int mpmc_hip_allreduce_observables_begin(mpmc_hip_comm *cm, const double *values, int count) {
-    if (!cm || !values || count <= 0 || count > cm->cap) return fail("MPMC_HIP: allreduce: bad arguments");
+    if (!cm || !values || count <= 0 || (size_t)count > cm->d_buf.size()) return fail("MPMC_HIP: allreduce: bad arguments");
     if (cm->pending) return fail("MPMC_HIP: allreduce_begin: the previous all-reduce has not been collected");
     HIPCHK(hipSetDevice(cm->device));
     memcpy(cm->h_buf, values, count * sizeof(double));
@@ -2552,14 +2541,9 @@ extern "C" int mpmc_hip_gather_observables(mpmc_hip_comm *cm, const void *record
     if (cm->pending) return fail("MPMC_HIP: gather: an all-reduce is in flight on this communicator");
     HIPCHK(hipSetDevice(cm->device));
     const size_t b = (size_t)bytes, need = b * (size_t)(cm->nranks + 1);
-    if (need > cm->gather_cap) {
-        if (cm->d_gather) HIPCHK(hipFree(cm->d_gather));
-        if (cm->h_gather) HIPCHK(hipHostFree(cm->h_gather));
-        cm->d_gather = cm->h_gather = nullptr;
-        cm->gather_cap = 0;
-        HIPCHK(hipMalloc((void **)&cm->d_gather, need));
-        HIPCHK(hipHostMalloc((void **)&cm->h_gather, need, hipHostMallocDefault));
-        cm->gather_cap = need;
+    if (cm->d_gather.size() < need || cm->h_gather.size() < need) {
+        HIPCHK(cm->d_gather.alloc(need));
+        HIPCHK(cm->h_gather.alloc(need));
     }
     memcpy(cm->h_gather, record, b);
     HIPCHK(hipMemcpyAsync(cm->d_gather, cm->h_gather, b, hipMemcpyHostToDevice, cm->stream));
@@ -2574,12 +2558,5 @@ extern "C" int mpmc_hip_gather_observables(mpmc_hip_comm *cm, const void *record
 extern "C" void mpmc_hip_comm_destroy(mpmc_hip_comm *cm) {
     if (!cm) return;
     hipSetDevice(cm->device);
-    if (cm->stream) hipStreamSynchronize(cm->stream);
-    if (cm->nccl && g_rccl.CommDestroy) g_rccl.CommDestroy(cm->nccl);
-    if (cm->d_buf) hipFree(cm->d_buf);
-    if (cm->h_buf) hipHostFree(cm->h_buf);
-    if (cm->d_gather) hipFree(cm->d_gather);
-    if (cm->h_gather) hipHostFree(cm->h_gather);
-    if (cm->stream) hipStreamDestroy(cm->stream);
     delete cm;
 }

@@ -363,7 +363,7 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
             unsigned long long *istamps = nullptr;
             const size_t nwg = (size_t)gi.x * gi.y * gi.z;
             if (c->opt_inv_stamps > 0 && st == c->stream) {
-                if (!c->d_istamps) HIPCHK(hipMalloc((void **)&c->d_istamps, (size_t)16 * 256 * 3 * 4 * sizeof(unsigned long long)));
+                if (!c->d_istamps) HIPCHK(c->d_istamps.alloc((size_t)16 * 256 * 3 * 4));
                 if (nwg <= (size_t)16 * 256 * 3) {
                     HIPCHK(hipMemsetAsync(c->d_istamps, 0, nwg * 4 * sizeof(unsigned long long), st));
                     istamps = c->d_istamps;
@@ -599,7 +599,8 @@ static int launch_gs_sweep(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, con
             if (finished) *finished = true;
         }
         if (c->opt_gs_stamps > 0) {
-            if (!c->d_stamps) HIPCHK(hipMalloc((void **)&c->d_stamps, (size_t)(c->max_npad / 64 + 1) * 16 * sizeof(unsigned long long)));
+            const size_t need = (size_t)(c->max_npad / 64 + 1) * 16;
+            if (c->d_stamps.size() < need) HIPCHK(c->d_stamps.alloc(need));
             HIPCHK(hipMemsetAsync(c->d_stamps, 0, (size_t)nt * 16 * sizeof(unsigned long long), c->stream));
             gp.stamps = c->d_stamps;
         }
@@ -706,7 +707,8 @@ static int launch_resident(mpmc_hip_ctx *c, SweepView &v, const DevBox &bx, cons
     const int nrole = rp.fold ? rp.ngroups : rp.nt + rp.ngroups;
     const size_t nstamp = (size_t)nrole * (kResMaxSweeps + 1) * 4;
     if (c->opt_res_stamps > 0) {
-        if (!c->d_stamps) HIPCHK(hipMalloc((void **)&c->d_stamps, (size_t)768 * (kResMaxSweeps + 1) * 4 * sizeof(unsigned long long)));
+        const size_t need = (size_t)768 * (kResMaxSweeps + 1) * 4;
+        if (c->d_stamps.size() < need) HIPCHK(c->d_stamps.alloc(need));
         HIPCHK(hipMemsetAsync(c->d_stamps, 0, nstamp * sizeof(unsigned long long), c->stream));
         rs.stamps = c->d_stamps;
     }
@@ -1034,7 +1036,7 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
                         } else {
                             std::vector<int> walk(v0idx);
                             std::stable_sort(walk.begin(), walk.end(), [rk](int x, int y) { return rk[x] > rk[y]; });
-                            std::copy(walk.begin(), walk.end(), c->h_perm);
+                            std::copy(walk.begin(), walk.end(), c->h_perm.get());
                         }
                     }
                     // A single-molecule move rarely changes the ranked order: if the walk is the one of the previous
@@ -1042,12 +1044,12 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
                     // (the reference rebuilds everything; so did this engine: 118 us at 4096 atoms).
                     const bool same_walk = (chain_mode ? W.C_valid : (W.A_valid && (W.C_valid || !c->opt_pair_coef))) &&
                                            W.ranked_call + 1 == c->energy_calls && W.nv == nv &&
-                                           W.nvpad == V->nvpad && std::equal(c->h_perm, c->h_perm + nv, W.h_idx.begin());
+                                           W.nvpad == V->nvpad && std::equal(c->h_perm.get(), c->h_perm + nv, W.h_idx.begin());
                     W.ranked_call = c->energy_calls;
                     if (!same_walk) {
                         W.nv = nv;
                         W.nvpad = V->nvpad;
-                        W.h_idx.assign(c->h_perm, c->h_perm + nv);
+                        W.h_idx.assign(c->h_perm.get(), c->h_perm + nv);
                         W.slot_of_atom.assign(n, -1);
                         for (int k = 0; k < npad; ++k) c->h_slotmap[k] = -1;
                         for (int k = 0; k < nv; ++k) {
