@@ -203,6 +203,15 @@ int mpmc_hip_set_params(mpmc_hip_ctx *ctx, const mpmc_hip_params *p);
  * pbc_cutoff = 0 => half the shortest lattice vector (pbc.c:13-34). */
 int mpmc_hip_set_box(mpmc_hip_ctx *ctx, const double basis[9], double pbc_cutoff);
 
+/* NPT volume move (mc_moves.c:168-210) and its revert (:213-248) on the resident configuration:
+ * new basis (+ pbc_cutoff as in set_box) and one displacement per molecule, in upload order;
+ * every atom of molecule m becomes pos + delta[m] -- the very addition volume_change() does.
+ * Nothing is uploaded again and the call does not wait for the device.  Return 0 = done; 1 = the resident
+ * molecules are no longer those of the upload (insert_molecule / remove_molecule since): upload the whole
+ * configuration again; < 0 = error (evaluation in flight, nothing uploaded, wrong n_molecules, bad box). */
+int mpmc_hip_scale_box(mpmc_hip_ctx *ctx, const double basis[9], double pbc_cutoff,
+                       int n_molecules, const double *delta /* [n_molecules][3] */);
+
 /* Full configuration, atoms in the reference's list order (molecule after molecule).
  * molecule[i]: id of the molecule; a molecule is a contiguous run of equal ids.
  * mass[i]: atomic mass (amu); molecular masses are summed here (pairs.c:364-385). */
@@ -244,7 +253,7 @@ int mpmc_hip_energy(mpmc_hip_ctx *ctx, mpmc_hip_result *out);
 /* The same in two halves: _begin enqueues the evaluation and returns, _end waits for it and fills the
  * result.  The reference's energy() does host-side bookkeeping that does not depend on the energies
  * (update_com(), countN(): pairs.c:331, energy.c:217); between the two calls that work overlaps the
- * device.  No upload/update_atoms/set_box is accepted while an evaluation is in flight. */
+ * device.  No upload/update_atoms/set_box/scale_box is accepted while an evaluation is in flight. */
 int mpmc_hip_energy_begin(mpmc_hip_ctx *ctx);
 int mpmc_hip_energy_end(mpmc_hip_ctx *ctx, mpmc_hip_result *out);
 

@@ -144,9 +144,29 @@ int hook_mc(system_t *system, char *snd_strct, char *rcv_strct, int msgsize, dou
 void hook_make_move_displace(system_t *system) {
     energy_hip_note_moved(system, system->checkpoint->molecule_altered, system->checkpoint->molecule_altered);
 }
-/* make_move() MOVETYPE_INSERT / MOVETYPE_REMOVE / MOVETYPE_VOLUME and restore()'s counterparts: */
+/* make_move() MOVETYPE_INSERT / MOVETYPE_REMOVE and restore()'s counterparts: */
 void hook_list_changed(system_t *system) {
     energy_hip_note_list_changed(system);
+}
+/* volume_change() (:168-210) and revert_volume_change() (:213-248), the same added lines in both (nothing else of
+ * either function changes): the displacement of every molecule is kept while the molecule loop runs and handed over
+ * behind it, so that energy_hip() moves the resident configuration into the new box instead of uploading it again
+ * (without them: a full upload, as before).  `delta_pos` is the loop's own variable. */
+void hook_volume_change(system_t *system, const double delta_pos[3]) {
+    molecule_t *m;
+
+    /* in front of the molecule loop (:195 / :232) */
+    int hip_k = 0, hip_n = 0;
+    for (m = system->molecules; m; m = m->next) hip_n++;
+    double *hip_delta = system->hip ? malloc(3 * hip_n * sizeof(double)) : NULL;
+
+    /* inside it, once per molecule, behind the loop that fills delta_pos (:200 / :238) */
+    if (hip_delta) memcpy(hip_delta + 3 * hip_k++, delta_pos, 3 * sizeof(double));
+
+    /* behind it (:207 / :245) */
+    if (system->hip && !hip_delta) energy_hip_note_list_changed(system);
+    if (hip_delta) energy_hip_note_volume_change(system, hip_delta);
+    free(hip_delta);
 }
 /* restore(), default branch (:778-797), where the backup is linked into the list in place of the altered node: */
 void hook_restore_displace(system_t *system) {

@@ -42,6 +42,7 @@
 #include "kernels_resident.h"
 #include "kernels_symv.h"
 #include "kernels_coef.h"
+#include "kernels_volume.h"
 
 using namespace mpmc;
 
@@ -361,8 +362,11 @@ struct mpmc_hip_ctx {
     int opt_sym_mode = 0;  // bit 0: alternate sweep direction, bit 1: default-policy loads
     int sweep_parity = 0;
     PinnedBuf<int> h_dirty;         // pinned staging for dirty slots
-    PinnedBuf<double> h_stage;      // pinned staging ring for update_atoms() coordinates
+    PinnedBuf<double> h_stage;      // pinned staging ring for update_atoms() coordinates and scale_box() displacements
     size_t stage_used = 0;
+    DevBuf<double> d_delta;         // scale_box(): per-molecule displacements [n_molecules][3]
+    int n_mol_uploaded = 0;         // molecules of the last upload (their ids are 0 .. n_mol_uploaded - 1)
+    bool edited = false;            // insert_molecule / remove_molecule since the last upload: ids no longer in upload order
     HipStream stream2;              // pair / reciprocal kernels overlap the polarization chain
     HipEvent ev_fork, ev_join;
     // scratch
@@ -857,10 +861,8 @@ extern "C" int mpmc_hip_set_params(mpmc_hip_ctx *c, const mpmc_hip_params *p) {
     return 0;
 }
 
-// reference src/energy/pbc.c:13-83
-extern "C" int mpmc_hip_set_box(mpmc_hip_ctx *c, const double basis[9], double pbc_cutoff) {
-    if (!c || !basis) return fail("MPMC_HIP: set_box: null argument");
-    if (c->in_flight) return fail("MPMC_HIP: set_box between energy_begin() and energy_end()");
+// reference src/energy/pbc.c:13-83; shared by set_box() and scale_box()
+static int apply_box(mpmc_hip_ctx *c, const double basis[9], double pbc_cutoff) {
     double b[3][3];
     for (int p = 0; p < 3; ++p)
         for (int q = 0; q < 3; ++q) b[p][q] = basis[3 * p + q];
@@ -908,6 +910,12 @@ extern "C" int mpmc_hip_set_box(mpmc_hip_ctx *c, const double basis[9], double p
     c->lrc_valid = false;
     c->all_dirty = true;
     return 0;
+}
+
+extern "C" int mpmc_hip_set_box(mpmc_hip_ctx *c, const double basis[9], double pbc_cutoff) {
+    if (!c || !basis) return fail("MPMC_HIP: set_box: null argument");
+    if (c->in_flight) return fail("MPMC_HIP: set_box between energy_begin() and energy_end()");
+    return apply_box(c, basis, pbc_cutoff);
 }
 
 extern "C" int mpmc_hip_upload(mpmc_hip_ctx *c, int n, const double *x, const double *y, const double *z,
@@ -965,6 +973,8 @@ extern "C" int mpmc_hip_upload(mpmc_hip_ctx *c, int n, const double *x, const do
     c->npad = npad;
     c->n_valid = n;
     c->next_mol = m + 1;
+    c->n_mol_uploaded = m + 1;
+    c->edited = false;
     c->slot_valid.assign(n, 1);
     c->slot_polar.assign(n, 0);
     for (int i = 0; i < n; ++i) c->slot_polar[i] = (polarizability[i] != 0.0);
@@ -1111,6 +1121,83 @@ extern "C" int mpmc_hip_update_atoms(mpmc_hip_ctx *c, int first, int count, cons
     return 0;
 }
 
+// NPT volume move (mc_moves.c:168-210) and its revert (:213-248) on the resident configuration: the new box, and
+// every molecule shifted rigidly by the displacement the host computed from its own centres of mass.  Nothing is
+// uploaded again: the molecule table, the views' index arrays and slot maps and the coefficient store's padding stay;
+// everything that is a function of the box or of all coordinates is marked for a rebuild by the next energy().
+// Return 1 = the molecule ids are no longer those of the upload (grand-canonical edits): upload again.
+extern "C" int mpmc_hip_scale_box(mpmc_hip_ctx *c, const double basis[9], double pbc_cutoff, int n_molecules,
+                                  const double *delta) {
+    if (!c || !basis || !delta) return fail("MPMC_HIP: scale_box: null argument");
+    if (c->in_flight) return fail("MPMC_HIP: scale_box between energy_begin() and energy_end()");
+    if (!c->have_atoms || !c->have_box) return fail("MPMC_HIP: scale_box: no configuration uploaded");
+    if (c->edited || !c->holes.empty()) return 1;
+    if (n_molecules != c->n_mol_uploaded)
+        return fail("MPMC_HIP: scale_box: %d displacements for the %d molecules of the upload", n_molecules,
+                    c->n_mol_uploaded);
+    HIPCHK(hipSetDevice(c->device));
+    const size_t need = 3 * (size_t)n_molecules;
+    double dmax = 0.0;
+    for (size_t k = 0; k < need; ++k) {
+        const double v = std::fabs(delta[k]);
+        if (!(v <= dmax)) dmax = (v == v) ? v : INFINITY;
+    }
+    if (flush_moves(c)) return -1;  // keep the order of the caller's operations
+    if (c->d_delta.size() < need) {
+        HIPCHK(hipStreamSynchronize(c->stream));  // (growth only: an earlier launch may still read the old buffer)
+        HIPCHK(c->d_delta.alloc(need));
+    }
+    if (c->h_stage.size() < 2 * need) {  // room for a change and its revert between two energy() calls
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(c->h_stage.alloc(2 * need + 3 * 4096));
+        c->stage_used = 0;
+    }
+    if (c->stage_used + need > c->h_stage.size()) {  // (as update_atoms: the ring is recycled after energy_end())
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->stage_used = 0;
+    }
+    if (apply_box(c, basis, pbc_cutoff)) return -1;  // (nothing enqueued yet: a refused box leaves the context as it was)
+    double *s = c->h_stage + c->stage_used;
+    memcpy(s, delta, need * sizeof(double));
+    c->stage_used += need;
+    HIPCHK(hipMemcpyAsync(c->d_delta, s, need * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    SweepView &v0 = c->view[0];
+    hipLaunchKernelGGL(shift_molecules_kernel, dim3((c->n + kShiftThreads - 1) / kShiftThreads), dim3(kShiftThreads), 0,
+                       c->stream, c->n, n_molecules, (const double *)c->d_delta, (const int *)c->d_mol,
+                       (const int *)c->d_flags, c->d_x.get(), c->d_y.get(), c->d_z.get(), (const int *)v0.d_slot,
+                       v0.px.get(), v0.py.get(), v0.pz.get());
+    HIPCHK(hipGetLastError());
+    // |new coordinate| <= |old| + |delta|: the fp32 screen's guard holds without reading anything back.  The bound only
+    // grows (a rejected volume move adds its shift twice for no net motion), so when it would cross the screen's limit
+    // it is replaced once by the true maximum, read back from the device: the only case in which this call waits.
+    {
+        const bool was64 = c->coord_max > kScreen32MaxCoord;
+        double bound = c->coord_max + dmax;
+        if (!was64 && bound > kScreen32MaxCoord) {
+            hipLaunchKernelGGL(coord_absmax_kernel, dim3(1), dim3(kShiftThreads), 0, c->stream, c->n,
+                               (const int *)c->d_flags, (const double *)c->d_x, (const double *)c->d_y,
+                               (const double *)c->d_z, c->d_delta.get());  // (d_delta has been consumed by the launch above)
+            double truth = INFINITY;
+            HIPCHK(hipMemcpyAsync(&truth, c->d_delta, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            c->stage_used = 0;  // (the ring's copies have completed)
+            bound = truth;
+        }
+        c->coord_max = bound;
+        if ((c->coord_max > kScreen32MaxCoord) != was64) ++c->config_rev;
+    }
+    c->staged_copies = true;  // coordinates reached the device outside the MoveList ...
+    c->main_writes = true;    // ... on the main stream: the side stream waits for the event behind them
+    c->dirty_atoms.clear();   // (apply_box() set all_dirty)
+    for (SweepView &v : c->view) v.A_valid = v.C_valid = false;
+    c->view[1].pos_valid = false;  // (view 0's packed positions were shifted by the same launch)
+    c->rank_used_valid = false;
+    c->rank_saved.clear();
+    c->perm_ranked = false;
+    c->have_polar_result = false;
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Grand-canonical moves without a re-upload.  The engine's atom order is its own business (sums are
 // over all atoms / pairs), so an inserted molecule takes the slots a removed one of the same size
@@ -1169,6 +1256,7 @@ static void mark_edited(mpmc_hip_ctx *c, int first, int count) {
     c->have_polar_result = false;
     c->self_valid = false;
     c->rank_used_valid = false;  // (polar_gs_ranked: the next call sorts the metric on the host)
+    c->edited = true;
     ++c->config_rev;
 }
 

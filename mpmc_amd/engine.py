@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libmpmc_hip.so")
 EXPORTS = [
     "mpmc_hip_last_error", "mpmc_hip_abi_version", "mpmc_hip_device_count", "mpmc_hip_create",
     "mpmc_hip_destroy", "mpmc_hip_set_option", "mpmc_hip_default_params", "mpmc_hip_set_params", "mpmc_hip_set_box",
+    "mpmc_hip_scale_box",
     "mpmc_hip_upload", "mpmc_hip_update_atoms", "mpmc_hip_insert_molecule", "mpmc_hip_remove_molecule",
     "mpmc_hip_slot_count", "mpmc_hip_set_sweep_order", "mpmc_hip_energy", "mpmc_hip_energy_begin", "mpmc_hip_energy_end",
     "mpmc_hip_download_dipoles",
@@ -126,6 +127,7 @@ def load():
     lib.mpmc_hip_default_params.restype = None
     lib.mpmc_hip_set_params.argtypes = [vp, C.POINTER(Params)]
     lib.mpmc_hip_set_box.argtypes = [vp, dp, C.c_double]
+    lib.mpmc_hip_scale_box.argtypes = [vp, dp, C.c_double, C.c_int, vp]
     lib.mpmc_hip_upload.argtypes = [vp, C.c_int] + [vp] * 10
     lib.mpmc_hip_update_atoms.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     lib.mpmc_hip_insert_molecule.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
@@ -204,6 +206,17 @@ class Engine:
     def set_box(self, basis, pbc_cutoff=0.0):
         b = np.ascontiguousarray(basis, dtype=np.float64).reshape(9)
         _chk(self.lib.mpmc_hip_set_box(self.ctx, b.ctypes.data_as(C.POINTER(C.c_double)), float(pbc_cutoff)))
+
+    def scale_box(self, basis, delta, pbc_cutoff=0.0):
+        """NPT volume move on the resident configuration (mpmc_hip_scale_box): the new basis and one displacement
+        per molecule, in upload order.  False = the engine asks for a full upload instead."""
+        b = np.ascontiguousarray(basis, dtype=np.float64).reshape(9)
+        d = np.ascontiguousarray(delta, dtype=np.float64).reshape(-1, 3)
+        rc = self.lib.mpmc_hip_scale_box(self.ctx, b.ctypes.data_as(C.POINTER(C.c_double)), float(pbc_cutoff),
+                                         d.shape[0], d.ctypes.data)
+        if rc < 0:
+            _chk(rc)
+        return rc == 0
 
     def upload(self, system):
         """system: dict with pos[n,3], charge, alpha, epsilon, sigma, mass, molecule, frozen."""

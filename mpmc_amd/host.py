@@ -61,6 +61,20 @@ def load():
     lib.walkers_finalize.argtypes = [vp]
     lib.walkers_finalize.restype = None
     lib.host_device_error.argtypes = [vp]
+    lib.host_get_basis.argtypes = [vp, vp]
+    lib.host_get_basis.restype = None
+    lib.host_get_npt.argtypes = [vp, vp]
+    lib.host_get_npt.restype = None
+    lib.host_set_volume_notes.argtypes = [vp, C.c_int]
+    lib.host_set_volume_notes.restype = None
+    lib.host_force_volume_move.argtypes = [vp, C.c_double, C.c_int]
+    lib.host_force_volume_move.restype = None
+    lib.host_init_chain_no_energy.argtypes = [vp]
+    lib.host_init_chain_no_energy.restype = None
+    lib.volume_change.argtypes = [vp]
+    lib.volume_change.restype = None
+    lib.revert_volume_change.argtypes = [vp]
+    lib.revert_volume_change.restype = None
     _lib = lib
     return lib
 
@@ -140,8 +154,32 @@ class HostSystem:
     def observables(self):
         out = np.zeros(8)
         self.lib.host_get_observables(self.ptr, out.ctypes.data)
+        npt = np.zeros(5)
+        self.lib.host_get_npt(self.ptr, npt.ctypes.data)
         return dict(energy=out[0], coulombic_energy=out[1], rd_energy=out[2], polarization_energy=out[3], N=out[4],
-                    polar_iterations=out[5], accept=int(out[6]), reject=int(out[7]))
+                    polar_iterations=out[5], accept=int(out[6]), reject=int(out[7]), volume=npt[0], cutoff=npt[1],
+                    accept_volume=int(npt[2]), reject_volume=int(npt[3]))
+
+    # ---- npt
+    def basis(self):
+        """Current lattice vectors (rows), which volume moves scale."""
+        b = np.zeros(9)
+        self.lib.host_get_basis(self.ptr, b.ctypes.data)
+        return b.reshape(3, 3)
+
+    def next_movetype(self):
+        """What checkpoint() decided the next make_move() does: 'insert', 'remove', 'displace' or 'volume'."""
+        npt = np.zeros(5)
+        self.lib.host_get_npt(self.ptr, npt.ctypes.data)
+        return ("insert", "remove", "displace", "volume")[int(npt[4])]
+
+    def set_volume_notes(self, on):
+        """False: the binding ignores volume-move notes, so every volume step uploads the whole configuration."""
+        self.lib.host_set_volume_notes(self.ptr, int(bool(on)))
+
+    def force_volume_move(self, new_volume, revert=False):
+        """One volume move to `new_volume` outside Metropolis and, on request, its revert (no energy evaluated)."""
+        self.lib.host_force_volume_move(self.ptr, float(new_volume), int(bool(revert)))
 
     def mc_steps(self, nsteps):
         r = self.lib.host_mc_steps(self.ptr, int(nsteps))

@@ -26,6 +26,7 @@ int host_apply_config(system_t *system, const char *text) {
     pbc(system);
     if (system->ensemble == ENSEMBLE_UVT && !system->user_fugacities) system->fugacity = system->pressure;
     if (system->ensemble == ENSEMBLE_UVT && !(system->fugacity > 0.0)) return 1;
+    if (system->ensemble == ENSEMBLE_NPT && !(system->pressure > 0.0)) return 1; /* check_input.c:673-678 */
     return 0;
 }
 
@@ -51,13 +52,16 @@ int host_mc_steps(system_t *system, int nsteps) {
             system->nodestats->boltzmann_factor = 0;
         } else
             boltzmann_factor(system, initial_energy, final_energy);
+        const int volume_move = system->checkpoint->movetype == MOVETYPE_VOLUME;
         if ((get_rand(system) < system->nodestats->boltzmann_factor) && (system->iter_success == 0)) {
             checkpoint(system);
             ++system->nodestats->accept;
+            if (volume_move) ++system->nodestats->accept_volume;
         } else {
             system->iter_success = 0;
             restore(system);
             ++system->nodestats->reject;
+            if (volume_move) ++system->nodestats->reject_volume;
         }
     }
     return system->nodestats->accept - acc0;
@@ -194,3 +198,34 @@ void host_get_system(system_t *system, double *pos, double *charge, double *alph
         }
 }
 void host_set_ensemble(system_t *system, int ensemble) { system->ensemble = ensemble; }
+
+/* ---- npt ---------------------------------------------------------------------------------------------------- */
+void host_get_basis(system_t *system, double basis[9]) {
+    for (int p = 0; p < 3; p++)
+        for (int q = 0; q < 3; q++) basis[3 * p + q] = system->pbc->basis[p][q];
+}
+/* volume, cutoff, the volume moves accepted / rejected so far, the move checkpoint() decided on */
+void host_get_npt(system_t *system, double out[5]) {
+    out[0] = system->pbc->volume;
+    out[1] = system->pbc->cutoff;
+    out[2] = (double)system->nodestats->accept_volume;
+    out[3] = (double)system->nodestats->reject_volume;
+    out[4] = (double)system->checkpoint->movetype;
+}
+/* 0 = energy_hip() ignores volume-move notes: every volume step uploads the whole configuration (A/B, tests) */
+void host_set_volume_notes(system_t *system, int on) { energy_hip_set_volume_notes(system, on); }
+/* One volume move to a stated new volume, outside Metropolis, so that tests reach both branches: exactly what
+ * make_move() does for MOVETYPE_VOLUME except that the new volume is given instead of drawn (as the reference's
+ * ENSEMBLE_REPLAY branch, mc_moves.c:176-178), and on request exactly what restore() does to take it back.  The
+ * observables are checkpointed first, as checkpoint() does.  No energy is evaluated here (only the centres of mass
+ * an energy() between the two would leave are refreshed). */
+void host_force_volume_move(system_t *system, double new_volume, int revert) {
+    memcpy(system->checkpoint->observables, system->observables, sizeof(observables_t));
+    system->checkpoint->observables->volume = system->pbc->volume;
+    volume_change_to(system, new_volume);
+    if (revert) {
+        update_com(system->molecules); /* what the energy() between a change and its revert leaves (pairs.c:331) */
+        memcpy(system->observables, system->checkpoint->observables, sizeof(observables_t));
+        revert_volume_change(system);
+    }
+}

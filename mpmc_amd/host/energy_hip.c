@@ -63,6 +63,9 @@ typedef struct shim_state {
     int in_sync, nnotes;
     struct { molecule_t *now, *was; } notes[8];
     int last_found;
+    /* noted volume moves (energy_hip_note_volume_change): one displacement per resident molecule, in list order */
+    int nvol, vol_notes_off;
+    double *vol_delta[4];
     int timing;
     mpmc_hip_timings tsum;
     int walker_rank, walker_nranks;
@@ -101,6 +104,7 @@ void energy_hip_cleanup(system_t *system) {
     if (st->comm) mpmc_hip_comm_destroy(st->comm);
     if (st->ctx) mpmc_hip_destroy(st->ctx);
     free_image(st);
+    for (int v = 0; v < st->nvol; v++) free(st->vol_delta[v]);
     free(st->res); free(st->res2); free(st->mols);
     free(st);
 }
@@ -234,8 +238,14 @@ static int hip_fail(const char *what) {
 /* every error return of energy_hip_begin() / _end() goes through here: the failure is recorded in its own channel
  * and the notes are dropped -- restore() may free a molecule that is still noted -- so the next energy(), if the
  * caller tries one, walks the lists */
+static void drop_volume_notes(shim_state *st) {
+    for (int v = 0; v < st->nvol; v++) free(st->vol_delta[v]);
+    st->nvol = 0;
+}
+
 static int device_failed(shim_state *st) {
     st->failed = 1;
+    drop_volume_notes(st);
     st->nnotes = 0;
     st->in_sync = 0;
     return -1;
@@ -326,6 +336,7 @@ static int full_upload(shim_state *st, system_t *system) {
     st->uploaded = 1;
     st->in_sync = 1;
     st->nnotes = 0;
+    drop_volume_notes(st);
     return 0;
 }
 
@@ -343,6 +354,53 @@ void energy_hip_note_moved(system_t *system, molecule_t *now, molecule_t *was) {
 void energy_hip_note_list_changed(system_t *system) {
     shim_state *st = state_of(system, 0);
     if (st) st->in_sync = 0;
+}
+/* volume_change() / revert_volume_change() shifted every molecule rigidly: delta_per_molecule[3 * k + i] is what was
+ * added to coordinate i of every atom of the k-th molecule of the list.  The next energy_hip() then scales the box
+ * of the resident configuration (mpmc_hip_scale_box) instead of uploading everything again. */
+void energy_hip_note_volume_change(system_t *system, const double *delta_per_molecule) {
+    shim_state *st = state_of(system, 0);
+    if (!st || !st->in_sync) return;
+    double *copy = NULL;
+    if (!st->vol_notes_off && delta_per_molecule && st->nvol < 4 && st->nres > 0)
+        copy = malloc((size_t)st->nres * 3 * sizeof(double));
+    if (!copy) {
+        st->in_sync = 0; /* the next energy() uploads the whole configuration */
+        return;
+    }
+    memcpy(copy, delta_per_molecule, (size_t)st->nres * 3 * sizeof(double));
+    st->vol_delta[st->nvol++] = copy;
+}
+void energy_hip_set_volume_notes(system_t *system, int on) {
+    shim_state *st = state_of(system, 1);
+    if (st) st->vol_notes_off = !on;
+}
+
+/* Carry out the noted volume moves on the resident configuration: the host image takes the additions the lists
+ * took (same operands, same order: the image stays bit-identical to the lists), the device the same through
+ * mpmc_hip_scale_box().  Molecules noted as displaced are compared with the image afterwards, so the order in which
+ * displacements and volume moves were noted does not matter.  Every call is given the box as it is now: with more
+ * than one note pending (mc() never leaves more than a revert and the next change) the earlier calls set up a box
+ * that only the last one's matters for -- a lattice sum on the host each, nothing on the device.  Returns 1 when the engine wants the whole
+ * configuration again, < 0 on error. */
+static int apply_volume_notes(shim_state *st, system_t *system) {
+    double basis[9];
+    for (int p = 0; p < 3; p++)
+        for (int r = 0; r < 3; r++) basis[3 * p + r] = system->pbc->basis[p][r];
+    for (int v = 0; v < st->nvol; v++) {
+        const double *d = st->vol_delta[v];
+        const int rc = mpmc_hip_scale_box(st->ctx, basis, system->pbc->cutoff, st->nres, d);
+        if (rc < 0) return hip_fail("scale_box");
+        if (rc > 0) return 1;
+        for (int k = 0; k < st->nres; k++) {
+            const int s = st->res[k].slot;
+            for (int a = 0; a < st->res[k].natoms; a++) {
+                st->x[s + a] += d[3 * k + 0]; st->y[s + a] += d[3 * k + 1]; st->z[s + a] += d[3 * k + 2];
+            }
+        }
+    }
+    drop_volume_notes(st);
+    return 0;
 }
 
 /* does list node m still hold exactly what resident r's slots were last sent? */
@@ -538,10 +596,18 @@ int energy_hip_begin(system_t *system) {
         return device_failed(st);
     }
     int need_upload = !st->ctx || !st->uploaded || system->last_volume != system->pbc->volume;
+    /* ... unless the box changed by volume moves that were noted: those are carried out on the resident configuration */
+    const int scale_box = st->ctx && st->uploaded && st->in_sync && st->nvol > 0;
+    if (scale_box) need_upload = 0;
     if (!need_upload) {
         mpmc_hip_params now;
         fill_params(system, &now); /* simulated annealing moves the temperature, surface fits the charges ... */
         if (memcmp(&now, &st->params, sizeof(now))) need_upload = 1;
+    }
+    if (!need_upload && scale_box) {
+        const int rc = apply_volume_notes(st, system);
+        if (rc < 0) return device_failed(st);
+        need_upload = rc;
     }
     if (!need_upload) {
         static int verify = -1;

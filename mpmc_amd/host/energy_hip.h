@@ -41,6 +41,13 @@ int energy_hip_failed(system_t *system);
  * Without these calls energy_hip() walks the lists on every call and finds the differences itself. */
 void energy_hip_note_moved(system_t *system, molecule_t *now, molecule_t *was);
 void energy_hip_note_list_changed(system_t *system);
+/* volume_change() / revert_volume_change() (npt): every molecule was shifted rigidly; delta_per_molecule[3 * k + i] is
+ * what was added to coordinate i of the atoms of the k-th molecule of the list (copied; the caller keeps its array).
+ * The next energy_hip() then moves the resident configuration into the new box (mpmc_hip_scale_box) instead of
+ * uploading everything again.  Without this note a changed volume means a full upload, as before. */
+void energy_hip_note_volume_change(system_t *system, const double *delta_per_molecule);
+/* on = 0: volume notes are ignored (the full upload of an un-hooked caller; for A/B measurement and tests) */
+void energy_hip_set_volume_notes(system_t *system, int on);
 
 /* atom->mu / ef_static / ef_induced / ef_induced_change as polar() leaves them; called where the reference
  * reads them (write_dipole() / write_field() at corrtime, src/mc/mc.c:398-414) instead of on every step */

@@ -61,6 +61,7 @@ static void setdefaults(system_t *system) {
     system->hip = 1;
     system->corrtime = 1;
     system->feynman_hibbs_order = 2;
+    system->volume_change_factor = 0.25; /* input.c:1608-1611 */
     strcpy(system->job_name, "untitled");
 }
 
@@ -97,10 +98,12 @@ int do_command(system_t *system, char **token) {
             system->ensemble = ENSEMBLE_NVT;
         else if (!strcasecmp(v, "uvt"))
             system->ensemble = ENSEMBLE_UVT;
+        else if (!strcasecmp(v, "npt"))
+            system->ensemble = ENSEMBLE_NPT;
         else if (!strcasecmp(v, "total_energy"))
             system->ensemble = ENSEMBLE_TE;
         else {
-            error("INPUT: only `ensemble nvt`, `uvt` and `total_energy` are implemented by this host layer\n");
+            error("INPUT: only `ensemble nvt`, `uvt`, `npt` and `total_energy` are implemented by this host layer\n");
             return 1;
         }
         return 0;
@@ -125,6 +128,8 @@ int do_command(system_t *system, char **token) {
     REAL("scale_charge", scale_charge);
     REAL("insert_probability", insert_probability);
     REAL("pressure", pressure);
+    REAL("volume_probability", volume_probability);
+    REAL("volume_change_factor", volume_change_factor);
     if (!strcasecmp(k, "user_fugacities")) {
         system->user_fugacities = 1;
         return safe_atof(v, &system->fugacity);
@@ -336,8 +341,13 @@ static int check_system(system_t *system) {
         error("INPUT: `hip off` requested but this host layer has no CPU energy path\n");
         return -1;
     }
-    if (system->ensemble != ENSEMBLE_NVT && system->ensemble != ENSEMBLE_TE && system->ensemble != ENSEMBLE_UVT) {
-        error("INPUT: ensemble must be nvt, uvt or total_energy\n");
+    if (system->ensemble != ENSEMBLE_NVT && system->ensemble != ENSEMBLE_TE && system->ensemble != ENSEMBLE_UVT &&
+        system->ensemble != ENSEMBLE_NPT) {
+        error("INPUT: ensemble must be nvt, uvt, npt or total_energy\n");
+        return -1;
+    }
+    if (system->ensemble == ENSEMBLE_NPT && !(system->pressure > 0.0)) { /* check_input.c:673-678 */
+        error("INPUT: invalid pressure set for NPT\n");
         return -1;
     }
     if (system->ensemble == ENSEMBLE_UVT && !system->user_fugacities) system->fugacity = system->pressure;

@@ -1,5 +1,5 @@
 /*
- * mc.c -- canonical (NVT) Markov chain, host side; mirrors the control flow of the reference's
+ * mc.c -- canonical (NVT), grand-canonical (UVT) and isobaric (NPT) Markov chain, host side; mirrors the control flow of the reference's
  * mc() (src/mc/mc.c:196-525), checkpoint()/restore() (src/mc/checkpoint.c:4-186,
  * src/mc/mc_moves.c:744-807), make_move()/displace() (src/mc/mc_moves.c:378-488, :567-741) and
  * get_rand() (src/mersenne/mersenne.cpp:9-22) for the displacement move.  Random numbers are
@@ -123,6 +123,81 @@ void rotate(system_t *system, molecule_t *molecule, pbc_t *pbc, double scale) {
     }
 }
 
+/* ---- npt: scale the volume (reference volume_change() / revert_volume_change(), src/mc/mc_moves.c:168-248) ---- */
+int wrapall(molecule_t *molecules, pbc_t *pbc) { /* reference src/io/output.c:142-183 */
+    double d[3], dimg[3];
+    for (molecule_t *m = molecules; m; m = m->next) {
+        if (!m->frozen) {
+            for (int i = 0; i < 3; i++) {
+                d[i] = 0;
+                for (int j = 0; j < 3; j++) d[i] += pbc->reciprocal_basis[j][i] * m->com[j];
+                d[i] = rint(d[i]);
+            }
+            for (int i = 0; i < 3; i++) {
+                dimg[i] = 0;
+                for (int j = 0; j < 3; j++) dimg[i] += pbc->basis[j][i] * d[j];
+                m->wrapped_com[i] = dimg[i];
+            }
+            for (atom_t *a = m->atoms; a; a = a->next)
+                for (int i = 0; i < 3; i++) a->wrapped_pos[i] = a->pos[i] - dimg[i];
+        } else
+            for (atom_t *a = m->atoms; a; a = a->next)
+                for (int i = 0; i < 3; i++) a->wrapped_pos[i] = a->pos[i];
+    }
+    return 0;
+}
+
+/* what both functions share: the basis is scaled, pbc() redone (the cutoff, once set, stays: pbc.c:71), and every
+ * molecule -- frozen ones too -- is shifted rigidly by (scaled COM - COM).  The displacements are handed to the
+ * binding, whose device copy takes the very same additions (energy_hip_note_volume_change). */
+static void scale_volume(system_t *system, double new_volume, int revert) {
+    double new_com[3], old_com[3], delta_pos[3];
+    int nmol = 0, k = 0;
+    for (molecule_t *m = system->molecules; m; m = m->next) nmol++;
+    double *hip_delta = malloc((nmol > 0 ? nmol : 1) * 3 * sizeof(double));
+
+    const double basis_scale_factor = pow(new_volume / system->pbc->volume, 1.0 / 3.0);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) system->pbc->basis[i][j] *= basis_scale_factor;
+
+    pbc(system);
+    system->observables->volume = system->pbc->volume;
+
+    for (molecule_t *m = system->molecules; m; m = m->next, k++) {
+        for (int i = 0; i < 3; i++) {
+            old_com[i] = m->com[i]; /* a change leaves com to the next energy(); a revert has none following */
+            new_com[i] = m->com[i] * basis_scale_factor;
+            if (revert) m->com[i] = new_com[i];
+            delta_pos[i] = new_com[i] - old_com[i];
+            if (hip_delta) hip_delta[3 * k + i] = delta_pos[i];
+        }
+        for (atom_t *a = m->atoms; a; a = a->next)
+            for (int i = 0; i < 3; i++) {
+                a->pos[i] += delta_pos[i];
+                a->wrapped_pos[i] += delta_pos[i];
+            }
+    }
+    if (revert) wrapall(system->molecules, system->pbc);
+    if (hip_delta)
+        energy_hip_note_volume_change(system, hip_delta);
+    else
+        energy_hip_note_list_changed(system);
+    free(hip_delta);
+}
+
+void volume_change_to(system_t *system, double new_volume) { scale_volume(system, new_volume, 0); }
+
+void volume_change(system_t *system) {
+    const double log_new_volume = log(system->pbc->volume) + (get_rand(system) - 0.5) * system->volume_change_factor;
+    const double new_volume = exp(log_new_volume);
+    scale_volume(system, new_volume, 0);
+}
+
+void revert_volume_change(system_t *system) {
+    /* system->pbc->volume still has the rejected value until pbc() is called */
+    scale_volume(system, system->checkpoint->observables->volume, 1);
+}
+
 /* deep copy of a molecule and its atoms (reference copy_molecule(), src/mc/mc_moves.c:251-330) */
 molecule_t *copy_molecule(system_t *system, molecule_t *src) {
     (void)system;
@@ -193,6 +268,18 @@ void checkpoint(system_t *system) {
                 cp->movetype = MOVETYPE_REMOVE;
         } else
             cp->movetype = MOVETYPE_DISPLACE;
+    } else if (system->ensemble == ENSEMBLE_NPT) { /* checkpoint.c:84-98 */
+        if (system->volume_probability == 0.0) { /* not set: volume moves with probability 1 / nmolecules */
+            if (get_rand(system) < 1.0 / system->observables->N)
+                cp->movetype = MOVETYPE_VOLUME;
+            else
+                cp->movetype = MOVETYPE_DISPLACE;
+        } else {
+            if (get_rand(system) < system->volume_probability)
+                cp->movetype = MOVETYPE_VOLUME;
+            else
+                cp->movetype = MOVETYPE_DISPLACE;
+        }
     } else
         cp->movetype = MOVETYPE_DISPLACE;
 
@@ -220,6 +307,10 @@ void checkpoint(system_t *system) {
 /* apply what checkpoint() decided (reference make_move(), src/mc/mc_moves.c:567-741) */
 void make_move(system_t *system) {
     checkpoint_t *cp = system->checkpoint;
+    if (cp->movetype == MOVETYPE_VOLUME) { /* (needs no picked molecule) */
+        volume_change(system);
+        return;
+    }
     if (!cp->molecule_altered) return;
     switch (cp->movetype) {
         case MOVETYPE_INSERT: {
@@ -293,6 +384,9 @@ void restore(system_t *system) {
             cp->molecule_backup->next = cp->tail;
             cp->molecule_backup = NULL;
             break;
+        case MOVETYPE_VOLUME:
+            revert_volume_change(system);
+            break;
         default:
             if (cp->molecule_altered) {
                 /* link the backup into the working list again */
@@ -329,6 +423,12 @@ void boltzmann_factor(system_t *system, double initial_energy, double final_ener
         else if (system->checkpoint->movetype == MOVETYPE_REMOVE)
             bf = system->temperature * ((double)(system->observables->N) + 1.0) /
                  (system->pbc->volume * fugacity * ATM2REDUCED) * exp(-delta_energy / system->temperature);
+    } else if (system->ensemble == ENSEMBLE_NPT && system->checkpoint->movetype == MOVETYPE_VOLUME) { /* mc.c:116-129 */
+        const double v_old = system->checkpoint->observables->volume;
+        const double v_new = system->observables->volume;
+        bf = exp(-(delta_energy + system->pressure * ATM2REDUCED * (v_new - v_old) -
+                   (system->observables->N + 1) * system->temperature * log(v_new / v_old)) /
+                 system->temperature);
     }
     system->nodestats->boltzmann_factor = bf;
 }
@@ -417,15 +517,22 @@ int mc(system_t *system) {
             boltzmann_factor(system, initial_energy, final_energy);
 
         /* Metropolis function */
+        const int volume_move = system->checkpoint->movetype == MOVETYPE_VOLUME; /* mc.c:160-190 */
         if ((get_rand(system) < system->nodestats->boltzmann_factor) && (system->iter_success == 0)) {
             checkpoint(system);
             ++system->nodestats->accept;
-            ++system->nodestats->accept_displace;
+            if (volume_move)
+                ++system->nodestats->accept_volume;
+            else
+                ++system->nodestats->accept_displace;
         } else {
             system->iter_success = 0; /* reset the polar iterative failure flag */
             restore(system);
             ++system->nodestats->reject;
-            ++system->nodestats->reject_displace;
+            if (volume_move)
+                ++system->nodestats->reject_volume;
+            else
+                ++system->nodestats->reject_displace;
         }
         system->nodestats->acceptance_rate =
             (double)system->nodestats->accept / (double)(system->nodestats->accept + system->nodestats->reject);

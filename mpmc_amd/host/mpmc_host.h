@@ -29,7 +29,7 @@ extern "C" {
 
 enum { ENSEMBLE_UVT, ENSEMBLE_NVT, ENSEMBLE_SURF, ENSEMBLE_SURF_FIT, ENSEMBLE_NVE, ENSEMBLE_TE, ENSEMBLE_NPT,
        ENSEMBLE_REPLAY };
-enum { MOVETYPE_INSERT, MOVETYPE_REMOVE, MOVETYPE_DISPLACE };
+enum { MOVETYPE_INSERT, MOVETYPE_REMOVE, MOVETYPE_DISPLACE, MOVETYPE_VOLUME };
 
 typedef struct _atom {
     int id, bond_id;
@@ -68,6 +68,7 @@ typedef struct _observables {
 typedef struct _nodestats {
     int accept, reject;
     int accept_displace, reject_displace;
+    int accept_volume, reject_volume; /* npt (mc.c:164-165, :189-190) */
     double boltzmann_factor, acceptance_rate, acceptance_rate_displace;
     double polarization_iterations;
 } nodestats_t;
@@ -93,6 +94,7 @@ typedef struct _system {
     double move_factor, rot_factor, temperature, scale_charge;
     double insert_probability, pressure, fugacity; /* uvt: fugacity = user_fugacities value, else pressure */
     int user_fugacities;
+    double volume_probability, volume_change_factor; /* npt (input.c:635-640; defaults 0.0 and 0.25) */
     int preset_seeds_on;
     unsigned int preset_seeds;
     int rng_initialized;
@@ -154,6 +156,11 @@ molecule_t *copy_molecule(system_t *system, molecule_t *src);
 void free_molecule(system_t *system, molecule_t *molecule);
 void translate(system_t *system, molecule_t *molecule, pbc_t *pbc, double scale);
 void rotate(system_t *system, molecule_t *molecule, pbc_t *pbc, double scale);
+void volume_change(system_t *system);        /* npt: mc_moves.c:168-210 */
+void volume_change_to(system_t *system, double new_volume); /* not a reference function: volume_change() from its basis scaling on, for
+                                                              * a given volume (the forced-move test entry of bench_api.c) */
+void revert_volume_change(system_t *system); /* mc_moves.c:213-248 */
+int wrapall(molecule_t *molecules, pbc_t *pbc);
 
 /* output */
 void output(const char *msg);
