@@ -44,6 +44,9 @@ struct DevBox {
     float frb[3][3];
     float rc2_pre;    // (cutoff + 0.01 A)^2
     int screen64;     // some |coordinate| is too large for the fp32 screen: screen on fp64 displacements (see below)
+    float half_tie32; // 0.5 - tie32: a fractional displacement this far from the integer it rounds to may round the other way
+    double tie64;     // 2^-49 * max |rb|: the same guard for the fp64 screen, per A of |dx| + |dy| + |dz|
+    int tie_guard;    // the cell is not orthorhombic: the screens apply the half-integer guard (see below)
 };
 
 // SoA view of the configuration resident in HBM.  All arrays have npad entries
@@ -188,44 +191,76 @@ __device__ __forceinline__ void minimum_image_sq(const DevBox &bx, double dx, do
 // Cheap single-precision screen for the cutoff-limited pair kernels: in a 40 A box with an 8 A cutoff
 // 97 % of the pairs lie outside the cutoff, and the exact fp64 minimum image (no FMA contraction, ~46
 // fp64 operations) is what those kernels spend their time on.  The screen evaluates the same minimum
-// image in fp32 (~30 operations at twice the rate) and keeps every pair within cutoff + 0.01 A; fp32
-// rounding of coordinates below ~100 A moves a distance by < 1e-4 A, and if fp32 picks the other image
-// of a tie both images are equidistant to that accuracy, so no pair the exact test accepts is lost.
-// Pairs that pass are decided by the exact fp64 path as before, so results are unchanged.
+// image in fp32 (~30 operations at twice the rate) and must keep EVERY pair the exact test accepts; pairs that
+// pass are decided by the exact fp64 path as before, so the screen never changes a result, it can only lose one.
 //
-// Guard: the reference never wraps atom->pos (wrapall() only fills wrapped_pos, src/io/output.c:142-183) and a
-// PQR may sit anywhere, so coordinates are not bounded by the box.  An fp32 coordinate carries an error of
-// |x| 2^-24; with |x| <= kScreen32MaxCoord = 2048 A the screened distance is off by < 2e-3 A, well inside the
-// 0.01 A margin.  The host tracks max |coordinate| over everything it sends (upload / update_atoms /
-// insert_molecule) and above that bound sets DevBox::screen64: the screen then works on fp64 displacements,
-// lattice reduction included (contracted arithmetic; exact to ~1e-10 A up to |x| ~ 1e5 A and never worse than
-// the exact path's own resolution), so no in-cutoff pair can be dropped however far the atoms sit.
+// Why it loses none, for every cell shape.  Let f_k be the fractional displacement the exact path hands to rint()
+// and f'_k the screen's.  Two cases:
+//  (a) rint(f'_k) == rint(f_k) for k = 0..2: both paths measure the SAME lattice image.  The reference never wraps
+//      atom->pos (wrapall() only fills wrapped_pos, src/io/output.c:142-183) and a PQR may sit anywhere, so the host
+//      tracks max |coordinate| over everything it sends (upload / update_atoms / insert_molecule / scale_box) and
+//      keeps the fp32 screen to |x| <= kScreen32MaxCoord = 2048 A.  There an fp32 coordinate is off by <= 2^-13 A and
+//      a coordinate difference by <= 3 * 2^-13 A (two roundings of the inputs, one of the difference, |d| < 4096);
+//      the image translation sum_q fb[q][k] * i_q (|term| < 4096) adds <= ~3 * 2^-12 A: the screened distance is off
+//      by < 2e-3 A, well inside the 0.01 A margin of rc2_pre.
+//  (b) some rint(f'_k) != rint(f_k): the screen measured ANOTHER image.  Rounding can only flip rint() when f_k lies
+//      within the error e_k = |f'_k - f_k| of a half-integer (bound below).
+//      Orthorhombic cell (every off-diagonal basis entry exactly 0; S_k = 1 / L_k): the other image mirrors component k
+//      of the displacement, (0.5 - u) L_k <-> (0.5 + u) L_k with u <= e_k, so the distance changes by at most
+//      2 e_k L_k <= 22 * 2^-13 = 2.7e-3 A; with the 2e-3 A of (a) that is still under the 0.01 A margin, and the
+//      screen needs nothing more.  DevBox::tie_guard = 0 there (wave-uniform: a kernel argument), so the cubic and
+//      orthorhombic boxes, bench.py's among them, run the screen they always ran.
+//      Sheared cell: the r^2 of the two images differ by 2 (s1 a.b + s2 a.c), which is of order L^2 -- the wrong image can
+//      sit many A outside the cutoff while the right one is inside.  There (tie_guard = 1) the screen KEEPS, without
+//      looking at the distance, every pair that has a component with 0.5 - |f'_k - rint(f'_k)| <= tie32, tie32 >= max_k e_k.
+//      Bound on e_k (dev_box(), engine.hip): with S_k = sum_q |rb[q][k]|,
+//        input error        3 * 2^-13 A per difference                       -> S_k * 3 * 2^-13
+//        frb rounded to fp32, three products, two additions (fused or not): four relative errors of 2^-24 on terms
+//        of magnitude <= S_k * 4096                                           -> S_k * 4 * 2^-12
+//      e_k <= 11 * 2^-13 * S_k; tie32 = 1.25 * 11 * 2^-13 * max_k S_k (5e-5 .. 1e-4 in a 25 A cell, so well under
+//      1e-3 of all pairs are kept on this ground -- the exact path drops them after its minimum image).  f'_k -
+//      rint(f'_k) is exact in fp32 (Sterbenz), and the exact path's own error in f_k (~1e-13) vanishes in the 1.25.
+// Above 2048 A the host sets DevBox::screen64 and the screen works on fp64 displacements, lattice reduction included.
+// It is compiled with FMA contraction and minimum_image_sq() without, so the two can still round an f_k to different
+// sides of a half-integer: the same guard applies with tie64 = 2^-48 + 2^-49 * max|rb| * (|dx| + |dy| + |dz|) (six
+// roundings of 2^-53 relative to the largest partial sum, times 2.7).  In case (a) this screen's distance is exact to
+// ~1e-10 A up to |x| ~ 1e5 A and never worse than the exact path's own resolution.
+// tests/test_gpu_screen_edges.py holds both screens to this with near-tie pairs in sheared cells.
 constexpr double kScreen32MaxCoord = 2048.0;
 __device__ __forceinline__ bool prefilter_within_f(const DevBox &bx, float dx, float dy, float dz);
 __device__ __forceinline__ bool prefilter_within_d(const DevBox &bx, double dx, double dy, double dz) {
-    const double i0 = rint(bx.rb[0][0] * dx + bx.rb[1][0] * dy + bx.rb[2][0] * dz);
-    const double i1 = rint(bx.rb[0][1] * dx + bx.rb[1][1] * dy + bx.rb[2][1] * dz);
-    const double i2 = rint(bx.rb[0][2] * dx + bx.rb[1][2] * dy + bx.rb[2][2] * dz);
+    const double f0 = bx.rb[0][0] * dx + bx.rb[1][0] * dy + bx.rb[2][0] * dz;
+    const double f1 = bx.rb[0][1] * dx + bx.rb[1][1] * dy + bx.rb[2][1] * dz;
+    const double f2 = bx.rb[0][2] * dx + bx.rb[1][2] * dy + bx.rb[2][2] * dz;
+    const double i0 = rint(f0), i1 = rint(f1), i2 = rint(f2);
     const double ex = dx - (bx.b[0][0] * i0 + bx.b[1][0] * i1 + bx.b[2][0] * i2);
     const double ey = dy - (bx.b[0][1] * i0 + bx.b[1][1] * i1 + bx.b[2][1] * i2);
     const double ez = dz - (bx.b[0][2] * i0 + bx.b[1][2] * i1 + bx.b[2][2] * i2);
     const double r2 = ex * ex + ey * ey + ez * ez;
-    return !(r2 > (double)bx.rc2_pre);  // NaN passes: the exact path handles it
+    bool keep = !(r2 > (double)bx.rc2_pre);  // NaN passes: the exact path handles it
+    if (bx.tie_guard) {                      // sheared cell: case (b) above
+        const double edge = fmax(fmax(fabs(f0 - i0), fabs(f1 - i1)), fabs(f2 - i2));  // distance from the integer picked
+        const double tie = 0x1p-48 + bx.tie64 * (fabs(dx) + fabs(dy) + fabs(dz));
+        keep = keep || (edge >= 0.5 - tie);
+    }
+    return keep;
 }
-// same screen on single-precision displacements (coordinates rounded to fp32 when a tile is staged:
-// |x| < 64 A => 4e-6 A per coordinate, far inside the 0.01 A margin)
+// same screen on single-precision displacements (coordinates rounded to fp32 when a tile is staged)
 __device__ __forceinline__ bool prefilter_within_f(const DevBox &bx, float dx, float dy, float dz) {
-    float i0 = bx.frb[0][0] * dx + bx.frb[1][0] * dy + bx.frb[2][0] * dz;
-    float i1 = bx.frb[0][1] * dx + bx.frb[1][1] * dy + bx.frb[2][1] * dz;
-    float i2 = bx.frb[0][2] * dx + bx.frb[1][2] * dy + bx.frb[2][2] * dz;
-    i0 = rintf(i0);
-    i1 = rintf(i1);
-    i2 = rintf(i2);
+    const float f0 = bx.frb[0][0] * dx + bx.frb[1][0] * dy + bx.frb[2][0] * dz;
+    const float f1 = bx.frb[0][1] * dx + bx.frb[1][1] * dy + bx.frb[2][1] * dz;
+    const float f2 = bx.frb[0][2] * dx + bx.frb[1][2] * dy + bx.frb[2][2] * dz;
+    const float i0 = rintf(f0), i1 = rintf(f1), i2 = rintf(f2);
     const float ex = dx - (bx.fb[0][0] * i0 + bx.fb[1][0] * i1 + bx.fb[2][0] * i2);
     const float ey = dy - (bx.fb[0][1] * i0 + bx.fb[1][1] * i1 + bx.fb[2][1] * i2);
     const float ez = dz - (bx.fb[0][2] * i0 + bx.fb[1][2] * i1 + bx.fb[2][2] * i2);
     const float r2 = ex * ex + ey * ey + ez * ez;
-    return !(r2 > bx.rc2_pre);  // NaN passes: the exact path handles it
+    bool keep = !(r2 > bx.rc2_pre);  // NaN passes: the exact path handles it
+    if (bx.tie_guard) {              // sheared cell: case (b) above
+        const float edge = fmaxf(fmaxf(fabsf(f0 - i0), fabsf(f1 - i1)), fabsf(f2 - i2));  // one v_max3_f32 with |.| modifiers
+        keep = keep || (edge >= bx.half_tie32);
+    }
+    return keep;
 }
 
 // Squared-distance pre-filter for the cutoff tests `rimg - 1e-12 < rc` / `!(rimg > rc)`: any pair that

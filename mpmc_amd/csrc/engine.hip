@@ -466,6 +466,16 @@ static DevBox dev_box(const mpmc_hip_ctx *c) {
         }
     b.rc2_pre = (float)((c->cutoff + 0.01) * (c->cutoff + 0.01));
     b.screen64 = (c->coord_max > kScreen32MaxCoord || !(c->coord_max == c->coord_max)) ? 1 : 0;
+    // half-integer guard of the screens (device_common.h): bound on the error of a fractional displacement
+    double smax = 0.0, rmax = 0.0;
+    for (int q = 0; q < 3; ++q) {
+        smax = std::max(smax, std::fabs(c->recip[0][q]) + std::fabs(c->recip[1][q]) + std::fabs(c->recip[2][q]));
+        for (int p = 0; p < 3; ++p) rmax = std::max(rmax, std::fabs(c->recip[p][q]));
+    }
+    const float tie32 = (float)(1.25 * 11.0 * 0x1p-13 * smax);
+    b.half_tie32 = 0.5f - tie32;  // (NaN basis: the comparison is false and the distance test's NaN rule decides)
+    b.tie64 = 0x1p-49 * rmax;
+    b.tie_guard = c->box_ortho ? 0 : 1;
     return b;
 }
 

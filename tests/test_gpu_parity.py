@@ -176,8 +176,11 @@ def test_half_box_ties_use_one_image_everywhere():
     g = np.arange(4) * (L / 4)
     frac = np.array([[x, y, z] for x in g for y in g for z in g])
     rng = np.random.default_rng(2)
-    for basis in (np.diag([L, L, L]), np.array([[L, 0, 0], [0.25 * L, L, 0], [0.0, 0.5 * L, L]])):
-        pos = (frac / L) @ basis  # lattice points of the cell: ties are exact in fractional coordinates
+    # shift = 0: lattice points of the cell, ties exact in fractional coordinates and in the fp32 copies of the screen;
+    # shift = 0.123456789 A on every coordinate: the same ties up to fp64 rounding, which fp32 no longer carries exactly
+    for basis, shift in [(b, sh) for b in (np.diag([L, L, L]), np.array([[L, 0, 0], [0.25 * L, L, 0], [0.0, 0.5 * L, L]]))
+                         for sh in (0.0, 0.123456789)]:
+        pos = (frac / L) @ basis + shift
         s = dict(pos=pos, charge=rng.normal(scale=60.0, size=n), alpha=rng.uniform(0.3, 1.2, size=n),
                  epsilon=np.full(n, 10.0), sigma=np.full(n, 2.5), mass=np.full(n, 4.0),
                  molecule=np.arange(n, dtype=np.int32), frozen=np.zeros(n, dtype=np.int32), basis=basis)
