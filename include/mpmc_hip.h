@@ -128,13 +128,16 @@ void mpmc_hip_destroy(mpmc_hip_ctx *ctx);
  *                          static field persist between calls; only tiles of moved atoms' blocks are recomputed;
  *   "overlap_streams"     (default 1): run the LJ/Ewald kernels on a second HIP stream beside the
  *                          polarization chain;
+ *   "side_after"          (default 1; at least 1): the LJ/Ewald stream is fed after this many sweeps have been enqueued;
  *   "symmetric_sweep"     (default 1; with pair_coefficients = 0): sweeps read only the upper triangle of A and
  *                          use every element for both products; 0 = full-matrix sweep; 2 = also below 2048 atoms;
+ *   "sym_mode"            (default 0): symmetric sweep on A: bit 0 = alternate the sweep direction, bit 1 = default-policy loads;
  *   "timing"              (default 1): 0 = record no HIP events; 1 = the sweep kernels (pair_sweep_kernel /
  *                          gs_chain_kernel) of every 32nd call ("timing_interval" changes the 32) are launched with a
  *                          start / stop event pair that carries the dispatch's own begin / end timestamps; 2 = time
  *                          every kernel class of every call (an event pair recorded AROUND a launch costs ~5
  *                          microseconds of stream time);
+ *   "timing_interval"     (default 32; at least 1): timing 1 / -1 sample every this many calls;
  *   "persistent_gs"       (default 1): Gauss-Seidel lower-triangle phase as one persistent launch (gs_chain_kernel:
  *                          a workgroup per 64-atom block in ticket order, cached block inverses, pair coefficients);
  *                          0 = the literal forward substitution on the expanded matrix, two launches per block;
@@ -156,6 +159,8 @@ void mpmc_hip_destroy(mpmc_hip_ctx *ctx);
  *                          stream beside the first sweep instead of on the main stream behind it (0 = main; A/B);
  *   "gs_fold_upper"       (default 1): the chain kernel's workgroups add up pair_upper_kernel's row sums of their own
  *                          blocks (0 = pair_upper_finish_kernel as a launch of its own in front of every chain launch);
+ *   "gs_fold_finish"      (default 1): the chain kernel's workgroups do the end-of-sweep bookkeeping of their own block
+ *                          (0 = gs_finish_kernel as a launch of its own behind every chain launch; A/B; same bits);
  *   "rank_late"           (default 1): in a speculative polar_gs_ranked call the side stream's ranking kernels and
  *                          ranked-view maintenance are enqueued behind the first sweep's launches, so the main stream's
  *                          own first kernels are not kept waiting for the host (0 = in front; 2 = the metric's four kernels behind the
@@ -168,11 +173,15 @@ void mpmc_hip_destroy(mpmc_hip_ctx *ctx);
  *   "resident_fold"       (default 16): views of up to this many blocks run that launch WITHOUT finisher workgroups
  *                          (jacobi_folded_kernel: every tile workgroup finishes its own two blocks, one hand-off per
  *                          sweep instead of two); 0 = a finisher workgroup per block at every size (A/B; same bits);
+ *   "resident_side"       (default 0): 1 = the LJ/Ewald stream is fed before the resident launch instead of behind it (A/B);
  *   "sweep_alternate"     (default 1): pair_sweep_kernel walks each XCD's tiles forwards / backwards in alternate sweeps;
  *   "sweep_nt"            (default -1): coefficient loads of the sweep non-temporal (1), default policy (0), or
  *                          non-temporal only when the tile set exceeds the Infinity Cache (-1);
+ *   "sweep_split"         (default -1): half-tile workgroups in pair_sweep_kernel: 1 always, 0 never, -1 by size (A/B);
  *   "fuse_moves"          (default 1): a single-molecule move is applied inside the coefficient update of the step
  *                          (update_coef_moves_kernel) instead of by a launch of its own;
+ *   "gs_fuse_moves"       (default 1): Gauss-Seidel modes on the chain kernel: the move rides in the coefficient update of
+ *                          view 0 as well (0 = apply_moves_kernel + update_coef_kernel; A/B; same bits);
  *   "fuse_field"          (default 1): ... and both ride in a third z-slice of the incremental static-field launch
  *                          (field_coef_kernel): the step's first launch does the move, the coefficient update and the
  *                          field; 0 = update_coef_moves_kernel as a launch of its own (A/B; same bits);
@@ -190,6 +199,8 @@ void mpmc_hip_destroy(mpmc_hip_ctx *ctx);
  *   "resident_stamps" / "sweep_ablate": diagnostics (in-kernel time line of the resident launch; timing-only ablations
  *                          of the sweep: results are wrong); "resident_fault": test hook (a lost hand-off);
  *   "gs_stamps"           diagnostic: the next `value` Gauss-Seidel sweeps print in-kernel time stamps per block;
+ *   "inv_stamps"          diagnostic: the next `value` block-inverse launches of the main stream print in-kernel time stamps;
+ *   "gs_ablate"           timing-only ablations of the chain kernel (results are wrong; tools/gs_ablate.py);
  *   "gs_fault_sweep"      test hook: in sweep number `value` of a call one block is never published (the call must
  *                          fail with a hand-off error, tests/test_gpu_parity.py);
  *   "step_graph"          (default 0): replay a steady-state MC step as a HIP graph (bit-identical; measured

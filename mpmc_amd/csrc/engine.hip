@@ -233,19 +233,131 @@ struct StepGraph {
     const double *result_mu = nullptr;
     const double *energy_part = nullptr;
     int energy_nt = 0;
+    int recip_chunks = 0, pair_rows_to_sum = 0;
+    unsigned res_zero_mask = 0;
+};
+
+// The knobs of mpmc_hip_set_option(), with their defaults: one member per row of kOptions (below), which names them.
+struct EngineOptions {
+    int pair_coef = 1;          // Jacobi/Palmo sweeps on pair coefficients (0: on the expanded A matrix)
+    int incremental = 1;        // "incremental_amatrix"
+    int incremental_pairs = 1;  // LJ/Ewald-real and static-field tile partials persist between calls
+    int overlap = 1;            // "overlap_streams"
+    int side_after = 1;         // feed the LJ/Ewald stream after this many sweeps are enqueued
+    int symmetric = 1;          // "symmetric_sweep"
+    int sym_mode = 0;           // bit 0: alternate sweep direction, bit 1: default-policy loads
+    int timing = 1;             // 0: no events, 1: sweep kernels + total only, 2: every kernel class
+    int timing_interval = 32;   // timing 1 / -1: every how many calls
+    int persistent_gs = 1;
+    int spec_rank = 1;          // "speculative_ranking": 0 = polar_gs_ranked asks the host for the sweep order in every call (A/B)
+    int fuse_tensor = 1;        // (round 2's A/B switch; accepted and ignored: the chain no longer uses tensor tiles)
+    int gs_lags = 3;            // cached neighbour matrices of the chain, 2 .. kGsMaxLag (kernels_gs_chain.h)
+    int gs_build_fork = 1;      // 0 = the builder in the main stream (A/B)
+    int gs_side_waves = 0;      // 16 = the OTHER view's rebuild in the side stream always with 16-wave workgroups;
+                                // 0 = the fastest geometry that leaves the chain kernel its CUs
+    int rank_view_side = 1;     // a host-sorted ranked view is (re)built on the side stream (0: main stream, behind the first sweep)
+    int gs_fold_upper = 1;      // the chain's workgroups add up pair_upper_kernel's row sums themselves
+    int gs_fold_finish = 1;     // gs_chain_kernel's workgroups do gs_finish_kernel's work for their block
+    int rank_late = 1;          // polar_gs_ranked's side-stream ranking work is enqueued behind the first sweep
+    int resident = 1;           // "resident_jacobi": fixed-count Jacobi-type solves as one launch, tiles in registers
+    int res_fold = 16;          // "resident_fold": views of up to this many blocks run the solve without finisher
+                                // workgroups (jacobi_folded_kernel); 0 = always with finishers
+    int res_side = 0;           // "resident_side": 1 = feed the LJ/Ewald stream BEFORE the resident launch
+    int sweep_alternate = 1;    // pair_sweep_kernel walks each XCD's tiles forwards / backwards in turn
+    int sweep_nt = -1;          // non-temporal coefficient loads in pair_sweep_kernel: 1 always, 0 never,
+                                // -1 = only when the tile set cannot stay in the 256-MB Infinity Cache
+    int sweep_split = -1;       // half-tile workgroups in pair_sweep_kernel: 1 always, 0 never, -1 by size
+    int fuse_moves = 1;         // the step's move is applied inside view 0's coefficient update
+    int gs_fuse_moves = 1;      // Gauss-Seidel modes: the move rides in the coefficient update of view 0
+    int fuse_field = 1;         // the move + coefficient update ride inside the field kernel's launch
+    int fuse_recip = 1;         // the reciprocal-space partials ride in the pair kernel's launch
+    int split_record = 1;       // the side stream publishes its own part of the result record
+    int side_moves = 1;         // 0 = fork event after the main stream's move (A/B; same bits)
+    int res_stamps = 0;         // "resident_stamps", diagnostic: the next resident launches print their hand-off time line
+    int sweep_ablate = 0;       // timing-only ablations of pair_sweep_kernel (wrong results)
+    int res_fault = 0;          // "resident_fault", test hook: the next resident launch loses a hand-off (-> fallback)
+    int gs_stamps = 0;          // diagnostic: the next Gauss-Seidel sweeps print where a block's time goes (slow)
+    int inv_stamps = 0;         // diagnostic: time stamps inside gs_block_inverse_kernel (main stream launches)
+    int gs_ablate = 0;          // timing-only ablations of the chain kernel (wrong results; tools/gs_ablate.py)
+    int gs_fault_sweep = 0;     // test hook: in Gauss-Seidel sweep number `value` (1-based) block 1 never publishes
+    int graph = 0;              // "step_graph": off by default, see graph_step()
+};
+
+// What belongs to ONE evaluation: begin_call() resets it, enqueue_direct() / graph_step() fill it in, energy_end() reads what
+// it needs after the wait.  Nothing here carries information from one call to the next.
+struct CallState {
+    // predicates of the call (enqueue_direct)
+    bool do_polar = false;        // the polarization chain runs
+    bool gs_mode = false;         // polar_gs or polar_gs_ranked
+    bool two_streams = false;     // the LJ / Ewald kernels run on the side stream beside it
+    bool plain_launches = false;  // neither captured into a step graph nor eligible to be ("step_graph" off)
+    DirtyBlocks dirty_blocks;             // 64-atom blocks of the atoms moved since the last call
+    bool pair_part_valid_before = false;  // pair_part_valid when the call started (after collect_dirty_blocks)
+    bool moves_deferred = false;  // pending moves not yet applied: they ride in view 0's coefficient update ...
+    bool moves_in_pair = false;   // ... or inside the pair kernel's launch (steps without polarization)
+    bool side_carry = false;      // ... and the side stream's pair kernel carries the same move itself (side_moves):
+    MoveList side_moves;          //     no fork event between the two streams in a steady-state polarizable step
+    MoveList side_apply;          // a move the main stream applied with apply_moves_kernel: the side stream applies it
+    bool side_applied = false;    //     too (a launch of its own, in front of its first kernel) instead of waiting for an event
+    bool coef_job_valid = false;  // setup_view() left the coefficient update of this step for launch_field()
+    bool coef_job_fork = false;   //   ... which then also records the fork event behind it
+    CoefJob coef_job;
+    bool build_join_pending = false;  // the main stream has not yet waited for the builder launch of this call
+    bool rank_on_side = false;        // ranking metric computed and copied to the host on the side stream
+    int gs_sweeps = 0;                // Gauss-Seidel sweeps enqueued so far
+    bool gs_used[2] = {false, false};  // the persistent kernel ran on view 0 / 1: its error word travels with the record
+    std::function<void()> enqueue_side;  // set while run_polarization() may feed the side stream (see enqueue_direct)
+    bool recip_fused = false;     // the reciprocal-space partials rode in the pair kernel's launch
+    int recip_chunks = 0;         // chunk sums the publish kernel folds (0: R_RECIP was written directly)
+    int pair_rows_to_sum = 0;     // tile partials of the pair kernel the publish kernel has to add up
+    unsigned res_zero_mask = 0;   // result slots the publish kernel writes as zero
+    // what energy_end() needs to know about the call it collects
+    bool split = false;           // the side stream published its own part of the record (two sequence numbers)
+    bool resident = false;        // the resident kernel was used
+    bool spec_rank = false;       // enqueued speculatively (polar_gs_ranked)
+    bool timed = false;           // events were recorded
+    int iterations = 0, iter_success = 0;
 };
 
 struct mpmc_hip_ctx {
+    // ---- configuration and box
     int device = 0;
+    int num_cus = 256;
     int max_atoms = 0, max_npad = 0;
     int n = 0, npad = 0;
+    EngineOptions opt;
+    CallState call;
+    mpmc_hip_params par;
+    bool have_params = false, have_box = false, have_atoms = false;
+    double basis[3][3], recip[3][3];
+    double pbc_cutoff_in = 0.0, cutoff = 0.0, volume = 0.0, ewald_alpha = 0.0, polar_ewald_alpha = 0.0;
+    bool box_ortho = false; // every off-diagonal basis entry is exactly zero
+    double coord_max = 0.0; // max |coordinate| of everything sent since the last upload (guards the fp32 screen)
+    unsigned long long config_rev = 1;   // bumped by everything that changes what an energy() call enqueues
+    unsigned long long energy_calls = 0;
+    bool in_flight = false;         // between energy_begin() and energy_end()
+    // ---- streams and events (declared in front of the buffers used on them: destroyed after those)
     HipStream stream;
+    HipStream stream2;              // pair / reciprocal kernels overlap the polarization chain
+    HipStream stream3;              // the chain-data builder of the main stream's view runs here, beside that stream's next kernels
+    HipEvent ev_fork, ev_join;
+    HipEvent ev_rank;
+    HipEvent ev_bfork, ev_bjoin;
+    HipEvent ev_order;
     // SoA configuration (HBM)
     DevBuf<double> d_x, d_y, d_z, d_q, d_alpha, d_eps, d_sig, d_molmass;
     DevBuf<int> d_mol, d_flags;
-    // polarization state: full-size per-atom vectors (atom order) + the two sweep views
+    MoveList pending;               // coordinates handed over by update_atoms(), applied at the next energy()
+    std::vector<int> dirty_atoms;   // atoms moved by update_atoms() since the last energy()
+    bool all_dirty = true;
+    bool staged_copies = false;          // coordinates reached the device outside the MoveList since the last call
+    bool main_writes = false;            // the MAIN stream was given writes of coordinates / parameters / the slot map outside
+                                         // the MoveList since the last call (staged copies, an upload, edits, a new sweep
+                                         // order): the side stream must then wait for an event recorded behind them -- it may
+                                         // not just apply the queued move for itself (side_apply / side_carry)
+    // ---- sweep views and polarization results: full-size per-atom vectors (atom order) + the two sweep views
     SweepView view[2];
-    DevBuf<double> d_es, d_mu, d_efind, d_efchg, d_rank, d_tmp3;
+    DevBuf<double> d_es, d_mu, d_efind, d_efchg, d_tmp3;
     DevBuf<unsigned long long> d_errmax;
     bool have_polar_result = false;
     // where the last polarization result lives (view order); scattered to atom order on demand
@@ -253,141 +365,39 @@ struct mpmc_hip_ctx {
     const double *result_mu = nullptr;
     bool results_scattered = true;
     const double *energy_part = nullptr;  // per-block energy sums to fold in publish_result_kernel (or null)
+    int energy_nt = 0;
     bool es_stale = false;  // d_es (atom order) not yet reduced from the field partials
     int es_slots = 0;
-    int energy_nt = 0;
-    MoveList pending;               // coordinates handed over by update_atoms(), applied at the next energy()
-    unsigned long long energy_calls = 0;
-    std::vector<int> dirty_atoms;   // atoms moved by update_atoms() since the last energy()
-    bool all_dirty = true;
-    int opt_incremental = 1, opt_overlap = 1, opt_symmetric = 1, opt_persistent_gs = 1;
-    int opt_gs_fault_sweep = 0;
-    int opt_sweep_alternate = 1;           // "sweep_alternate": pair_sweep_kernel walks each XCD's tiles forwards / backwards in turn
-    int opt_sweep_ablate = 0;              // timing-only ablations of pair_sweep_kernel (wrong results)
-    int opt_gs_lags = 3;                   // "gs_lags": cached neighbour matrices of the chain, 2 .. kGsMaxLag (kernels_gs_chain.h)
-    int opt_gs_fuse_moves = 1;             // "gs_fuse_moves": Gauss-Seidel modes: the move rides in the coefficient update of view 0
-    int opt_sweep_split = -1;              // "sweep_split": half-tile workgroups in pair_sweep_kernel: 1 always, 0 never, -1 by size
-    int opt_sweep_nt = -1;                 // "sweep_nt": non-temporal coefficient loads in pair_sweep_kernel: 1 always, 0 never,
-                                           // -1 = only when the tile set cannot stay in the 256-MB Infinity Cache
-    int opt_resident = 1;                  // "resident_jacobi": fixed-count Jacobi-type solves as one launch, tiles in registers
-    int opt_res_fault = 0;                 // test hook: the next resident launch loses a hand-off
-    int opt_res_stamps = 0;                // diagnostic: the next resident launches print their hand-off time line
-    int opt_res_side = 0;                  // "resident_side": 1 = feed the LJ/Ewald stream BEFORE the resident launch
-    int opt_res_fold = 16;                 // "resident_fold": views of up to this many blocks run the solve without finisher
-                                           // workgroups (jacobi_folded_kernel); 0 = always with finishers
-    bool resident_off = false;             // a resident launch gave up: this context keeps to the multi-launch path ...
-    long resident_retry_at = 0;            // ... until this many energy() calls have been made (then it tries once more),
-    long resident_backoff = 0;             // the interval doubling with every further give-up (4 096 ... 1 048 576 calls)
-    bool call_resident = false;            // the call in flight used the resident kernel
-    bool force_multi_launch = false;       // while energy_end() repeats such a call
-    bool res_attr_set = false;
-    int pair_rows_to_sum = 0;              // tile partials of the pair kernel the publish kernel has to add up
-    unsigned res_zero_mask = 0;            // result slots the publish kernel writes as zero in the call being enqueued
-    int opt_gs_fold_finish = 1;            // "gs_fold_finish": gs_chain_kernel's workgroups do gs_finish_kernel's work for their block
-    int opt_fuse_moves = 1;                // "fuse_moves": the step's move is applied inside view 0's coefficient update
-    bool moves_in_pair = false;            // ... or inside the pair kernel's launch (steps without polarization)
-    bool moves_deferred = false;           // pending moves not yet applied in the call being enqueued
-    bool side_carry = false;               // ... and the side stream's pair kernel carries the same move itself (side_moves):
-    MoveList side_moves;                   //     no fork event between the two streams in a steady-state polarizable step
-    MoveList side_apply;                   // a move the main stream applied with apply_moves_kernel: the side stream applies it
-    bool side_applied = false;             //     too (a launch of its own, in front of its first kernel) instead of waiting for an event
-    int opt_split_record = 1;              // "split_record": the side stream publishes its own part of the result record
-    bool call_split = false;               // the call in flight did (energy_end waits for both sequence numbers)
-    int opt_fuse_recip = 1;                // "fuse_recip": the reciprocal-space partials ride in the pair kernel's launch
-    bool recip_fused = false;              // ... and did, in the call being enqueued
-    int opt_rank_view_side = 1;            // "rank_view_side": a host-sorted ranked view is (re)built on the side stream
-    int opt_gs_fold_upper = 1;             // "gs_fold_upper": the chain's workgroups add up pair_upper_kernel's row sums themselves
-    int opt_fuse_tensor = 1;               // "fuse_tensor": a move's sub-diagonal tensor tiles ride in the block-inverse launch
-    int opt_rank_late = 1;                 // "rank_late": polar_gs_ranked's side-stream ranking work is enqueued behind the first sweep
-    int opt_fuse_field = 1;                // "fuse_field": the move + coefficient update ride inside the field kernel's launch
-    bool coef_job_valid = false;           // setup_view() left the coefficient update of this step for launch_field()
-    bool coef_job_fork = false;            //   ... which then also records the fork event behind it
-    CoefJob coef_job;
-    int opt_side_moves = 1;                // "side_moves": 0 = fork event after the main stream's move (A/B; same bits)
-    unsigned long long resident_calls = 0, resident_fallbacks = 0;
-    int opt_gs_ablate = 0;                 // timing-only ablations of the chain kernel (wrong results; tools/gs_ablate.py)
-    int opt_gs_stamps = 0;                 // diagnostic: time stamps inside the chain kernel (printed by the sweep)
-    int opt_inv_stamps = 0;                // diagnostic: time stamps inside gs_block_inverse_kernel (main stream launches)
-    DevBuf<unsigned long long> d_istamps;
+    int sweep_parity = 0;
     int gs_qoff = 0;                       // offset (doubles) of the q_t hand-off buffer inside a view's mupub
-    DevBuf<unsigned long long> d_stamps;
-    int gs_sweeps_this_call = 0;
-    int opt_pair_coef = 1;  // Jacobi/Palmo sweeps on pair coefficients (0: on the expanded A matrix)
-    int opt_incremental_pairs = 1;  // LJ/Ewald-real and static-field tile partials persist between calls
+    DevBuf<unsigned long long> d_stamps, d_istamps;  // diagnostics: in-kernel time stamps (gs_stamps / resident_stamps, inv_stamps)
+    // ---- pair / field / reciprocal caches
+    DevBuf<double> d_pairpart;      // [ntile*ntile][4]
     bool pair_part_valid = false;   // d_pairpart holds the tile partials of the configuration before the pending moves
-    bool pair_part_valid_before = false;  // its value when the energy() call in progress started (after collect_dirty_blocks)
+    DevBuf<double> d_fieldpart;     // [nchunk][3][npad]
     bool field_part_valid = false;  // same for d_fieldpart (real-space static field)
     int field_key = -1;             // mode / chunking the resident field partials were made with
     DevBuf<double> d_lrcpart;       // tile partials of the (cached) long-range correction
+    bool lrc_valid = false;
+    double lrc_cached = 0.0;
+    DevBuf<KVec> d_kvec;
+    int nk = 0;
+    bool kvec_valid = false;
+    int kvec_kmax = -1;
     DevBuf<double2> d_sfpart;       // [block][nk] partial structure factors of the reciprocal-space sum
     bool recip_part_valid = false;
     DevBuf<double> d_recipsum;      // [ceil(nk/64)] per-chunk sums of w_k |S(k)|^2, folded by the publish kernel
-    int recip_chunks = 0;           // of this call (0: R_RECIP was written directly)
     bool self_valid = false;        // d_res[R_SELF] holds the Ewald self term of the current charges
     double self_alpha = 0.0;
-    DevBuf<double> d_rankpart;      // scratch of the ranking metric (per-tile minima)
-    DirtyBlocks dirty_blocks;       // of the energy() call in progress
-    bool in_flight = false;         // between energy_begin() and energy_end()
-    // ---- grand-canonical edits (insert_molecule / remove_molecule): c->n is the number of atom SLOTS in use,
-    // some of which may be holes left by removed molecules
-    int n_valid = 0;                     // atoms actually present
-    int next_mol = 0;                    // next unused molecule id
-    std::vector<char> slot_valid;        // per atom slot
-    std::vector<char> slot_polar;        // per atom slot: polarizability != 0 (what a stated sweep order must cover exactly)
-    std::vector<std::pair<int, int>> holes;  // (first, count) of removed molecules, reusable by an insert of that size
-    std::vector<int> lrc_dirty_atoms;    // atoms inserted / removed since the long-range correction was summed
-    // ---- one MC step as a HIP graph (see graph_step())
-    int opt_side_after = 1;              // "side_after": feed the LJ/Ewald stream after this many sweeps are enqueued
-    int opt_graph = 0;                   // "step_graph": off by default, see graph_step()
-    int graph_mode = 0;                  // GM_DIRECT | GM_CAPTURE | GM_UPDATE
-    StepGraph sg;
-    unsigned long long config_rev = 1;   // bumped by everything that changes what an energy() call enqueues
-    int eligible_streak = 0;             // consecutive calls that met graph_eligible()
-    bool staged_copies = false;          // coordinates reached the device outside the MoveList since the last call
-    bool main_writes = false;            // the MAIN stream was given writes of coordinates / parameters / the slot map outside
-                                         // the MoveList since the last call (staged copies, an upload, edits, a new sweep
-                                         // order): the side stream must then wait for an event recorded behind them -- it may
-                                         // not just apply the queued move for itself (side_apply / side_carry)
-    unsigned long long graph_launches = 0;
-    double graph_update_s = 0.0, graph_launch_s = 0.0;
-    bool call_polar = false, call_timed = false;
-    int call_iterations = 0, call_iter_success = 0;
-    std::function<void()> enqueue_side;  // set while run_polarization() may feed the side stream (see energy())
-    double host_enqueue_s = 0.0, host_wait_s = 0.0;  // MPMC_HIP_HOST_PROFILE=1: printed at destroy
-    double coord_max = 0.0; // max |coordinate| of everything sent since the last upload (guards the fp32 screen)
-    bool box_ortho = false; // every off-diagonal basis entry is exactly zero
-    int num_cus = 256;
-    int opt_timing = 1;    // 0: no events, 1: sweep kernels + total only, 2: every kernel class
-    int opt_timing_interval = 32;  // timing 1 / -1: every how many calls
-    int opt_sym_mode = 0;  // bit 0: alternate sweep direction, bit 1: default-policy loads
-    int sweep_parity = 0;
-    PinnedBuf<int> h_dirty;         // pinned staging for dirty slots
-    PinnedBuf<double> h_stage;      // pinned staging ring for update_atoms() coordinates and scale_box() displacements
-    size_t stage_used = 0;
-    DevBuf<double> d_delta;         // scale_box(): per-molecule displacements [n_molecules][3]
-    int n_mol_uploaded = 0;         // molecules of the last upload (their ids are 0 .. n_mol_uploaded - 1)
-    bool edited = false;            // insert_molecule / remove_molecule since the last upload: ids no longer in upload order
-    HipStream stream2;              // pair / reciprocal kernels overlap the polarization chain
-    HipEvent ev_fork, ev_join;
-    // scratch
-    DevBuf<double> d_pairpart;      // [ntile*ntile][4]
-    DevBuf<double> d_fieldpart;     // [nchunk][3][npad]
-    DevBuf<KVec> d_kvec;
-    int nk = 0;
     DevBuf<KVecF> d_kvecf;          // k list weighted with polar_ewald_alpha (Ewald static field)
     DevBuf<double2> d_sf;
     int nkf = 0;
     double kvecf_alpha = -1.0;
     int kvecf_kmax = -1;
     bool kvecf_valid = false;
-    DevBuf<double> d_res;     // R_COUNT doubles
-    PinnedBuf<double> h_res;  // pinned, mapped
-    double *h_res_dev = nullptr;
-    PinnedBuf<double> h_res2;  // the side stream's part of the record (LJ / Ewald sums) with a sequence number of its own
-    double *h_res2_dev = nullptr;
-    PinnedBuf<unsigned long long> h_err;  // pinned, 1 word
-    PinnedBuf<unsigned> h_gserr;          // pinned: error words of the persistent Gauss-Seidel kernel (2 views)
-    bool gs_used[2] = {false, false};
+    // ---- ranking
+    DevBuf<double> d_rank;
+    DevBuf<double> d_rankpart;      // scratch of the ranking metric (per-tile minima)
     // polar_gs_ranked without a host round trip: the ranked view (1) is kept for the walk of the previous call and
     // the whole evaluation is enqueued on that assumption; the device compares the new ranking metric with the one
     // that walk was sorted from (d_rank_used) and energy_end() repeats the call the slow way if they differ
@@ -396,41 +406,58 @@ struct mpmc_hip_ctx {
     std::vector<double> rank_saved;       // host copy of the metric d_rank_used holds (download_ranking sorts it on demand)
     bool perm_ranked = false;             // the last call's sweeps used the ranked walk
     bool rank_used_valid = false;
+    bool force_host_rank = false;         // while energy_end() repeats a speculative call: no speculation
+    unsigned long long spec_redos = 0;
+    // ---- grand-canonical slots (insert_molecule / remove_molecule): c->n is the number of atom SLOTS in use,
+    // some of which may be holes left by removed molecules
+    int n_valid = 0;                     // atoms actually present
+    int next_mol = 0;                    // next unused molecule id
+    std::vector<char> slot_valid;        // per atom slot
+    std::vector<char> slot_polar;        // per atom slot: polarizability != 0 (what a stated sweep order must cover exactly)
+    std::vector<std::pair<int, int>> holes;  // (first, count) of removed molecules, reusable by an insert of that size
+    std::vector<int> lrc_dirty_atoms;    // atoms inserted / removed since the long-range correction was summed
+    int n_mol_uploaded = 0;         // molecules of the last upload (their ids are 0 .. n_mol_uploaded - 1)
+    bool edited = false;            // insert_molecule / remove_molecule since the last upload: ids no longer in upload order
     // Gauss-Seidel + grand-canonical edits: the sweep ORDER is part of the result, and after insert / remove the
     // engine's slot order is no longer the caller's atom order.  The caller then states the order of the polarizable
     // sites (mpmc_hip_set_sweep_order); until it has, energy() refuses to run.
     bool order_stale = false;
-    bool force_host_rank = false;         // this call: no speculation
-    bool call_spec_rank = false;          // the call in flight was enqueued speculatively
-    bool rank_on_side = false;            // this call: metric computed and copied to the host on the side stream
-    int opt_spec_rank = 1;
-    unsigned long long spec_redos = 0;
-    HipEvent ev_rank;
-    HipStream stream3;                     // the chain-data builder of the main stream's view runs here, beside that stream's next kernels
-    HipEvent ev_bfork, ev_bjoin;
-    bool build_join_pending = false;       // the main stream has not yet waited for the builder launch of this call
-    int opt_gs_build_fork = 1;             // "gs_build_fork": 0 = the builder in the main stream (A/B)
-    int opt_gs_side_waves = 0;             // "gs_side_waves": 16 = the OTHER view's rebuild in the side stream always with 16-wave workgroups;
-                                           // 0 = the fastest geometry that leaves the chain kernel its CUs
+    // ---- resident-solver fallback
+    bool resident_off = false;             // a resident launch gave up: this context keeps to the multi-launch path ...
+    long resident_retry_at = 0;            // ... until this many energy() calls have been made (then it tries once more),
+    long resident_backoff = 0;             // the interval doubling with every further give-up (4 096 ... 1 048 576 calls)
+    bool force_multi_launch = false;       // while energy_end() repeats a call whose resident launch gave up
+    bool res_attr_set = false;
+    unsigned long long resident_calls = 0, resident_fallbacks = 0;
+    // ---- one MC step as a HIP graph (see graph_step())
+    int graph_mode = 0;                  // GM_DIRECT | GM_CAPTURE | GM_UPDATE
+    StepGraph sg;
+    int eligible_streak = 0;             // consecutive calls that met graph_eligible()
+    unsigned long long graph_launches = 0;
+    double graph_update_s = 0.0, graph_launch_s = 0.0;
+    // ---- staging and pinned buffers
+    PinnedBuf<int> h_dirty;         // pinned staging for dirty slots
+    PinnedBuf<double> h_stage;      // pinned staging ring for update_atoms() coordinates and scale_box() displacements
+    size_t stage_used = 0;
+    DevBuf<double> d_delta;         // scale_box(): per-molecule displacements [n_molecules][3]
+    DevBuf<double> d_res;     // R_COUNT doubles
+    PinnedBuf<double> h_res;  // pinned, mapped
+    double *h_res_dev = nullptr;
+    PinnedBuf<double> h_res2;  // the side stream's part of the record (LJ / Ewald sums) with a sequence number of its own
+    double *h_res2_dev = nullptr;
+    PinnedBuf<unsigned long long> h_err;  // pinned, 1 word
+    PinnedBuf<unsigned> h_gserr;          // pinned: error words of the persistent Gauss-Seidel kernel (2 views)
     PinnedBuf<int> h_order;               // pinned staging of set_sweep_order (2 x max_npad ints)
-    HipEvent ev_order;
     PinnedBuf<double> h_rank;             // pinned, max_npad
     PinnedBuf<int> h_perm;                // pinned, max_npad
     PinnedBuf<int> h_slotmap;             // pinned, max_npad: an atom -> slot map on its way to the device
-    // host state
-    mpmc_hip_params par;
-    bool have_params = false, have_box = false, have_atoms = false;
-    double basis[3][3], recip[3][3];
-    double pbc_cutoff_in = 0.0, cutoff = 0.0, volume = 0.0, ewald_alpha = 0.0, polar_ewald_alpha = 0.0;
-    bool kvec_valid = false, lrc_valid = false;
-    double lrc_cached = 0.0;
-    int kvec_kmax = -1;
-    // timing
+    // ---- timing
     std::vector<HipEvent> ev_pool;
-    size_t ev_next = 0;
-    std::vector<TimeRec> recs;
+    size_t ev_next = 0;             // of the call in progress: begin_call() rewinds the pool and clears the records, whose
+    std::vector<TimeRec> recs;      //     storage is kept from call to call (get_timings reads them after energy_end)
     HipEvent ev_first, ev_last;
     bool timed = false;
+    double host_enqueue_s = 0.0, host_wait_s = 0.0;  // MPMC_HIP_HOST_PROFILE=1: printed at destroy
 };
 
 static DevAtoms dev_atoms(const mpmc_hip_ctx *c) {
@@ -499,8 +526,8 @@ static void note_coords(mpmc_hip_ctx *c, const double *x, const double *y, const
 // reading the events back stalls the host: sampling every 8th call cost 10 % of the step rate); 2: every call;
 // -1: only the first-launch / last-kernel pair of every 32nd call (length of the device chain)
 static inline bool is_timed_call(const mpmc_hip_ctx *c) {
-    return c->opt_timing >= 2 || ((c->opt_timing == 1 || c->opt_timing == -1) &&
-                                 (c->energy_calls % (unsigned long long)c->opt_timing_interval) == 0ull);
+    return c->opt.timing >= 2 || ((c->opt.timing == 1 || c->opt.timing == -1) &&
+                                 (c->energy_calls % (unsigned long long)c->opt.timing_interval) == 0ull);
 }
 
 // Launch of one of the GraphSlotId kernels: a plain launch (which stream capture records), or, while a
@@ -538,8 +565,8 @@ struct ScopedTimer {
     bool on;
     ScopedTimer(mpmc_hip_ctx *ctx, int cls, hipStream_t st = nullptr) : c(ctx), s(st ? st : ctx->stream), on(false) {
         const bool wanted = c->graph_mode == GM_DIRECT &&
-                            (c->opt_timing >= 2 ||
-                             (c->opt_timing == 1 && (cls == T_SWEEP || cls == T_EVPAIR) && is_timed_call(c)));
+                            (c->opt.timing >= 2 ||
+                             (c->opt.timing == 1 && (cls == T_SWEEP || cls == T_EVPAIR) && is_timed_call(c)));
         if (wanted && c->ev_next + 2 <= c->ev_pool.size()) {
             r.cls = cls;
             r.a = c->ev_pool[c->ev_next++];
@@ -571,7 +598,7 @@ static hipError_t launch_timed(mpmc_hip_ctx *c, int cls, void (*kernel)(KArgs...
         std::apply([&](auto &...v) { ((argv[k++] = (void *)&v), ...); }, vals);
     }
     const bool wanted = c->graph_mode == GM_DIRECT &&
-                        (c->opt_timing >= 2 || (c->opt_timing == 1 && cls == T_SWEEP && is_timed_call(c)));
+                        (c->opt.timing >= 2 || (c->opt.timing == 1 && cls == T_SWEEP && is_timed_call(c)));
     if (wanted && c->ev_next + 2 <= c->ev_pool.size()) {
         TimeRec r;
         r.cls = cls;
@@ -584,104 +611,79 @@ static hipError_t launch_timed(mpmc_hip_ctx *c, int cls, void (*kernel)(KArgs...
     return hipLaunchKernel((const void *)kernel, g, b, argv, shmem, s);
 }
 
+// The options of mpmc_hip_set_option(), in the order of the comment in include/mpmc_hip.h.  A row with a hook does more
+// than store the value: the hook stores it itself (and may refuse it: -1).
+struct OptionRow {
+    const char *name;
+    int EngineOptions::*member;
+    int (*hook)(mpmc_hip_ctx *c, int value);
+};
+static const OptionRow kOptions[] = {
+    // (the resident data were made the other way)
+    {"pair_coefficients", &EngineOptions::pair_coef, [](mpmc_hip_ctx *c, int v) { c->opt.pair_coef = v; c->all_dirty = true; return 0; }},
+    {"incremental_amatrix", &EngineOptions::incremental, [](mpmc_hip_ctx *c, int v) { c->opt.incremental = v; c->all_dirty = true; return 0; }},
+    {"incremental_pairs", &EngineOptions::incremental_pairs,
+     [](mpmc_hip_ctx *c, int v) { c->opt.incremental_pairs = v; c->all_dirty = true; return 0; }},
+    {"overlap_streams", &EngineOptions::overlap, nullptr},
+    {"side_after", &EngineOptions::side_after, [](mpmc_hip_ctx *c, int v) { c->opt.side_after = std::max(1, v); return 0; }},
+    {"symmetric_sweep", &EngineOptions::symmetric, nullptr},
+    {"sym_mode", &EngineOptions::sym_mode, nullptr},
+    {"timing", &EngineOptions::timing, nullptr},
+    {"timing_interval", &EngineOptions::timing_interval,
+     [](mpmc_hip_ctx *c, int v) { c->opt.timing_interval = std::max(1, v); return 0; }},
+    {"persistent_gs", &EngineOptions::persistent_gs, nullptr},
+    {"speculative_ranking", &EngineOptions::spec_rank, nullptr},
+    {"fuse_tensor", &EngineOptions::fuse_tensor, nullptr},
+    {"gs_lags", &EngineOptions::gs_lags,
+     [](mpmc_hip_ctx *c, int v) {
+         if (v < 2 || v > kGsMaxLag) return fail("mpmc_hip_set_option: gs_lags must be 2 .. %d", kGsMaxLag);
+         if (v != c->opt.gs_lags) c->view[0].M_epoch = c->view[1].M_epoch = 0;  // (the matrices of the new lags are not there)
+         c->opt.gs_lags = v;
+         return 0;
+     }},
+    {"gs_build_fork", &EngineOptions::gs_build_fork, nullptr},
+    {"gs_side_waves", &EngineOptions::gs_side_waves, [](mpmc_hip_ctx *c, int v) { c->opt.gs_side_waves = (v == 16) ? 16 : 0; return 0; }},
+    {"rank_view_side", &EngineOptions::rank_view_side, nullptr},
+    {"gs_fold_upper", &EngineOptions::gs_fold_upper, nullptr},
+    {"gs_fold_finish", &EngineOptions::gs_fold_finish, nullptr},
+    {"rank_late", &EngineOptions::rank_late, nullptr},
+    {"resident_jacobi", &EngineOptions::resident,
+     [](mpmc_hip_ctx *c, int v) {
+         c->opt.resident = v;  // 0: one sweep + one finish launch per iteration (A/B; bit-identical results)
+         if (v) c->resident_off = false;
+         return 0;
+     }},
+    {"resident_fold", &EngineOptions::res_fold, nullptr},
+    {"resident_side", &EngineOptions::res_side, nullptr},
+    {"sweep_alternate", &EngineOptions::sweep_alternate, nullptr},
+    {"sweep_nt", &EngineOptions::sweep_nt, nullptr},
+    {"sweep_split", &EngineOptions::sweep_split, nullptr},
+    {"fuse_moves", &EngineOptions::fuse_moves, nullptr},
+    {"gs_fuse_moves", &EngineOptions::gs_fuse_moves, nullptr},
+    {"fuse_field", &EngineOptions::fuse_field, nullptr},
+    {"fuse_recip", &EngineOptions::fuse_recip, nullptr},
+    {"split_record", &EngineOptions::split_record, nullptr},
+    {"side_moves", &EngineOptions::side_moves, nullptr},
+    {"resident_stamps", &EngineOptions::res_stamps, nullptr},
+    {"sweep_ablate", &EngineOptions::sweep_ablate, nullptr},
+    {"resident_fault", &EngineOptions::res_fault, nullptr},
+    {"gs_stamps", &EngineOptions::gs_stamps, nullptr},
+    {"inv_stamps", &EngineOptions::inv_stamps, nullptr},
+    {"gs_ablate", &EngineOptions::gs_ablate, nullptr},
+    {"gs_fault_sweep", &EngineOptions::gs_fault_sweep, nullptr},
+    {"step_graph", &EngineOptions::graph, nullptr},
+};
+
 extern "C" int mpmc_hip_set_option(mpmc_hip_ctx *c, const char *name, int value) {
     if (!c || !name) return fail("MPMC_HIP: set_option: null argument");
     ++c->config_rev;
-    if (!strcmp(name, "step_graph")) {
-        c->opt_graph = value;
+    for (const OptionRow &o : kOptions) {
+        if (strcmp(name, o.name)) continue;
+        if (o.hook) return o.hook(c, value);
+        c->opt.*o.member = value;
         return 0;
     }
-    if (!strcmp(name, "timing_interval")) {
-        c->opt_timing_interval = std::max(1, value);
-        return 0;
-    }
-    if (!strcmp(name, "side_after")) {
-        c->opt_side_after = std::max(1, value);
-        return 0;
-    }
-    if (!strcmp(name, "incremental_amatrix")) {
-        c->opt_incremental = value;
-        c->all_dirty = true;
-    } else if (!strcmp(name, "overlap_streams"))
-        c->opt_overlap = value;
-    else if (!strcmp(name, "symmetric_sweep"))
-        c->opt_symmetric = value;
-    else if (!strcmp(name, "timing"))
-        c->opt_timing = value;
-    else if (!strcmp(name, "sym_mode"))
-        c->opt_sym_mode = value;
-    else if (!strcmp(name, "persistent_gs"))
-        c->opt_persistent_gs = value;
-    else if (!strcmp(name, "speculative_ranking"))
-        c->opt_spec_rank = value;  // 0: polar_gs_ranked asks the host for the sweep order in every call (A/B)
-    else if (!strcmp(name, "gs_ablate"))
-        c->opt_gs_ablate = value;
-    else if (!strcmp(name, "gs_stamps"))
-        c->opt_gs_stamps = value;  // diagnostic: the next Gauss-Seidel sweeps print where a block's time goes (slow)
-    else if (!strcmp(name, "gs_fault_sweep"))
-        c->opt_gs_fault_sweep = value;  // test hook: in Gauss-Seidel sweep number `value` (1-based) block 1 never publishes
-    else if (!strcmp(name, "sweep_alternate"))
-        c->opt_sweep_alternate = value;
-    else if (!strcmp(name, "sweep_ablate"))
-        c->opt_sweep_ablate = value;
-    else if (!strcmp(name, "sweep_nt"))
-        c->opt_sweep_nt = value;
-    else if (!strcmp(name, "resident_jacobi")) {
-        c->opt_resident = value;  // 0: one sweep + one finish launch per iteration (A/B; bit-identical results)
-        if (value) c->resident_off = false;
-    } else if (!strcmp(name, "gs_fold_finish"))
-        c->opt_gs_fold_finish = value;  // 0: gs_finish_kernel as a launch of its own after every chain launch (A/B)
-    else if (!strcmp(name, "fuse_moves"))
-        c->opt_fuse_moves = value;  // 0: apply_moves_kernel + update_coef_kernel as two launches (A/B; bit-identical)
-    else if (!strcmp(name, "resident_fault"))
-        c->opt_res_fault = value;  // test hook: the next resident launch loses a hand-off (-> fallback)
-    else if (!strcmp(name, "gs_build_fork"))
-        c->opt_gs_build_fork = value;
-    else if (!strcmp(name, "gs_side_waves"))
-        c->opt_gs_side_waves = (value == 16) ? 16 : 0;
-    else if (!strcmp(name, "gs_lags")) {
-        if (value < 2 || value > kGsMaxLag) return fail("mpmc_hip_set_option: gs_lags must be 2 .. %d", kGsMaxLag);
-        if (value != c->opt_gs_lags) c->view[0].M_epoch = c->view[1].M_epoch = 0;  // (the matrices of the new lags are not there)
-        c->opt_gs_lags = value;
-    }
-    else if (!strcmp(name, "gs_fuse_moves"))
-        c->opt_gs_fuse_moves = value;
-    else if (!strcmp(name, "sweep_split"))
-        c->opt_sweep_split = value;
-    else if (!strcmp(name, "inv_stamps"))
-        c->opt_inv_stamps = value;
-    else if (!strcmp(name, "resident_stamps"))
-        c->opt_res_stamps = value;
-    else if (!strcmp(name, "split_record"))
-        c->opt_split_record = value;  // 0: the main stream waits for the side stream (join event) and publishes everything
-    else if (!strcmp(name, "fuse_recip"))
-        c->opt_fuse_recip = value;  // 0: recip_partial_kernel as a launch of its own behind the pair kernel
-    else if (!strcmp(name, "rank_view_side"))
-        c->opt_rank_view_side = value;  // 0: on the main stream, behind the first sweep (A/B; same results)
-    else if (!strcmp(name, "gs_fold_upper"))
-        c->opt_gs_fold_upper = value;  // 0: pair_upper_finish_kernel as a launch of its own in front of every chain launch
-    else if (!strcmp(name, "fuse_tensor"))
-        c->opt_fuse_tensor = value;  // (round 2's A/B switch; accepted and ignored: the chain no longer uses tensor tiles)
-    else if (!strcmp(name, "rank_late"))
-        c->opt_rank_late = value;  // 0: in front of the main stream's view set-up (A/B; same results)
-    else if (!strcmp(name, "fuse_field"))
-        c->opt_fuse_field = value;  // 0: update_coef_moves_kernel as a launch of its own in front of the field kernel
-    else if (!strcmp(name, "side_moves"))
-        c->opt_side_moves = value;  // 0: the side stream waits for an event recorded behind the main stream's move
-    else if (!strcmp(name, "resident_fold"))
-        c->opt_res_fold = value;   // largest view (blocks) solved by jacobi_folded_kernel; 0 = off (A/B; bit-identical results)
-    else if (!strcmp(name, "resident_side"))
-        c->opt_res_side = value;   // 1: the LJ/Ewald stream is fed before the resident launch instead of after it
-    else if (!strcmp(name, "pair_coefficients")) {
-        c->opt_pair_coef = value;
-        c->all_dirty = true;
-    } else if (!strcmp(name, "incremental_pairs")) {
-        c->opt_incremental_pairs = value;
-        c->all_dirty = true;
-    }
-    else
-        return fail("MPMC_HIP: set_option: unknown option '%s'", name);
-    return 0;
+    return fail("MPMC_HIP: set_option: unknown option '%s'", name);
 }
 
 extern "C" void mpmc_hip_default_params(mpmc_hip_params *p) {
@@ -1044,15 +1046,15 @@ static int flush_moves(mpmc_hip_ctx *c) {
 }
 
 static void side_wait_for_moves(mpmc_hip_ctx *c, hipStream_t s) {
-    if (c->side_apply.n > 0) {
+    if (c->call.side_apply.n > 0) {
         SweepView &v0 = c->view[0];
-        hipLaunchKernelGGL(apply_moves_kernel, dim3(1), dim3(64), 0, s, c->side_apply, c->d_x, c->d_y, c->d_z,
+        hipLaunchKernelGGL(apply_moves_kernel, dim3(1), dim3(64), 0, s, c->call.side_apply, c->d_x, c->d_y, c->d_z,
                            (const int *)v0.d_slot, v0.px, v0.py, v0.pz);
-        c->side_apply.n = 0;
-        c->side_applied = true;
+        c->call.side_apply.n = 0;
+        c->call.side_applied = true;
         return;
     }
-    if (c->side_applied) return;  // (already on this stream, earlier in the call)
+    if (c->call.side_applied) return;  // (already on this stream, earlier in the call)
     hipStreamWaitEvent(s, c->ev_fork, 0);
 }
 
@@ -1218,13 +1220,13 @@ extern "C" int mpmc_hip_scale_box(mpmc_hip_ctx *c, const double basis[9], double
 // ---------------------------------------------------------------------------------------------
 static bool gs_order_mode(const mpmc_hip_ctx *c) {  // Gauss-Seidel on the chain kernel: the view order is the caller's
     const mpmc_hip_params &P = c->par;
-    return !P.rd_only && P.polarization && !P.polar_zodid && (P.polar_gs || P.polar_gs_ranked) && c->opt_pair_coef != 0 &&
-           c->opt_persistent_gs != 0;
+    return !P.rd_only && P.polarization && !P.polar_zodid && (P.polar_gs || P.polar_gs_ranked) && c->opt.pair_coef != 0 &&
+           c->opt.persistent_gs != 0;
 }
 
 static bool edits_supported(const mpmc_hip_ctx *c) {
     const mpmc_hip_params &P = c->par;
-    if (!c->have_atoms || c->all_dirty || !c->opt_incremental || !c->opt_incremental_pairs || !c->opt_pair_coef) return false;
+    if (!c->have_atoms || c->all_dirty || !c->opt.incremental || !c->opt.incremental_pairs || !c->opt.pair_coef) return false;
     // Gauss-Seidel: only with the chain kernel, whose view is rebuilt from the order the caller states afterwards
     if (!P.rd_only && P.polarization && (P.polar_gs || P.polar_gs_ranked) && !gs_order_mode(c)) return false;
     return true;
@@ -1580,9 +1582,9 @@ static int ensure_view_coef(mpmc_hip_ctx *c, SweepView &v, int nt, hipStream_t s
 
 // cached block inverses M_t + neighbour matrices P_t = M_t D T(t,t-1) of the Gauss-Seidel chain, sized for the view's capacity
 static int ensure_view_chain(mpmc_hip_ctx *c, SweepView &v, hipStream_t st) {
-    if (v.Minv && v.Lnb_lags >= c->opt_gs_lags) return 0;
+    if (v.Minv && v.Lnb_lags >= c->opt.gs_lags) return 0;
     const size_t nbcap = (size_t)(v.cap + 63) / 64;
-    for (; v.Lnb_lags < c->opt_gs_lags; ++v.Lnb_lags) {
+    for (; v.Lnb_lags < c->opt.gs_lags; ++v.Lnb_lags) {
         HIPCHK(v.Lnb[v.Lnb_lags].alloc(nbcap * kPnbDoubles));
         v.M_epoch = 0;
     }
@@ -1645,7 +1647,7 @@ struct ResidentPlan {
 static ResidentPlan resident_plan(const mpmc_hip_ctx *c, const SweepView &v) {
     ResidentPlan r;
     const mpmc_hip_params &P = c->par;
-    if (!c->opt_resident || c->resident_off || c->force_multi_launch || !c->opt_pair_coef || !v.C_valid) return r;
+    if (!c->opt.resident || c->resident_off || c->force_multi_launch || !c->opt.pair_coef || !v.C_valid) return r;
     if (P.polar_zodid || P.polar_gs || P.polar_gs_ranked || P.polar_precision != 0.0) return r;
     if (P.polar_max_iter < 1 || P.polar_max_iter > kResMaxSweeps) return r;
     if (c->device < 64 && g_ctx_on_device[c->device].load() > 1) return r;  // co-residency needs the device to itself
@@ -1664,7 +1666,7 @@ static ResidentPlan resident_plan(const mpmc_hip_ctx *c, const SweepView &v) {
     r.nt = nt;
     r.ntiles = ntiles;
     r.ngroups = ntiles;
-    r.fold = nt <= std::min(c->opt_res_fold, kFoldMaxBlocks);
+    r.fold = nt <= std::min(c->opt.res_fold, kFoldMaxBlocks);
     const int need = resident_lds_bytes<1>();
     const bool one = true;
     r.lds = one ? std::max(need, kResidentLdsOnePerCu) : need;
@@ -1798,35 +1800,35 @@ static int launch_pair_kernel(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &
     pp.fh_order = P.feynman_hibbs ? P.feynman_hibbs_order : 0;
     pp.wolf = P.wolf;
     pp.erfaRoverR = std::erf(c->ewald_alpha * c->cutoff) / c->cutoff;
-    DirtyBlocks sel = c->dirty_blocks;
+    DirtyBlocks sel = c->call.dirty_blocks;
     if (!c->pair_part_valid) sel.n = 0;
     const dim3 grid(ntile, sel.n > 0 ? sel.n : ntile), block(64 * kPairWaves);
-    c->recip_fused = false;
+    c->call.recip_fused = false;
     if (c->pair_part_valid && c->dirty_atoms.empty()) return 0;  // nothing moved since the partials were made
     // the step's move, when this launch carries it (steps without polarization: enqueue_direct)
     MoveList mv;
     mv.n = 0;
     MoveTargets mt = {c->d_x, c->d_y, c->d_z, c->view[0].d_slot, c->view[0].px, c->view[0].py, c->view[0].pz};
-    if (c->moves_in_pair && c->pending.n > 0) {
+    if (c->call.moves_in_pair && c->pending.n > 0) {
         mv = c->pending;
         c->pending.n = 0;
-    } else if (c->side_carry && sb == c->stream2 && c->side_moves.n > 0) {
+    } else if (c->call.side_carry && sb == c->stream2 && c->call.side_moves.n > 0) {
         // A steady-state polarizable step: the main stream applies the move inside its coefficient update
         // (update_coef_moves_kernel) and this launch -- the first of the side stream that reads coordinates -- applies the
         // SAME move for itself: no thread of either kernel reads a moved atom's position from memory, both write the same
         // bits into the coordinate arrays, and each stream's later kernels come behind their own stream's writer.  So the
         // two streams need no fork event (recording one costs the main stream ~5 us between its first two launches).
-        mv = c->side_moves;
+        mv = c->call.side_moves;
     }
-    c->side_moves.n = 0;
-    c->moves_in_pair = false;
-    if (with_recip && c->opt_fuse_recip && c->graph_mode == GM_DIRECT && !c->opt_graph && c->nk > 0 &&
+    c->call.side_moves.n = 0;
+    c->call.moves_in_pair = false;
+    if (with_recip && c->opt.fuse_recip && c->call.plain_launches && c->nk > 0 &&
         (c->nk + 63) / 64 <= ntile) {
         // the reciprocal-space partials of the same blocks ride in a second z-slice of this launch (pair_recip_kernel) when
         // both passes are of the same kind: incremental over the same dirty blocks, or full
-        DirtyBlocks rsel = c->dirty_blocks;
-        if (!c->recip_part_valid || !c->pair_part_valid_before) rsel.n = 0;
-        const bool recip_skipped = c->recip_part_valid && c->pair_part_valid_before && c->dirty_atoms.empty();
+        DirtyBlocks rsel = c->call.dirty_blocks;
+        if (!c->recip_part_valid || !c->call.pair_part_valid_before) rsel.n = 0;
+        const bool recip_skipped = c->recip_part_valid && c->call.pair_part_valid_before && c->dirty_atoms.empty();
         if (!recip_skipped && rsel.n == sel.n) {
             const dim3 g2(grid.x, grid.y, 2);
             RecipJob rj = {(const KVec *)c->d_kvec, c->nk, c->d_sfpart};
@@ -1839,7 +1841,7 @@ static int launch_pair_kernel(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &
             HIPCHK(hipGetLastError());
             c->pair_part_valid = true;
             c->recip_part_valid = true;
-            c->recip_fused = true;
+            c->call.recip_fused = true;
             return 0;
         }
     }
@@ -1856,116 +1858,117 @@ static int launch_pair_kernel(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &
 // partial structure factors of the moved atoms' blocks (graph slot GS_RECIP), or of all blocks
 static int launch_recip_partial(mpmc_hip_ctx *c, const DevAtoms &a, hipStream_t sb) {
     const int ntile = c->npad / 64;
-    DirtyBlocks rsel = c->dirty_blocks;
-    if (!c->recip_part_valid || !c->pair_part_valid_before) rsel.n = 0;
-    if (c->recip_part_valid && c->pair_part_valid_before && c->dirty_atoms.empty()) return 0;  // nothing moved
+    DirtyBlocks rsel = c->call.dirty_blocks;
+    if (!c->recip_part_valid || !c->call.pair_part_valid_before) rsel.n = 0;
+    if (c->recip_part_valid && c->call.pair_part_valid_before && c->dirty_atoms.empty()) return 0;  // nothing moved
     HIPCHK(launch_slot(c, GS_RECIP, recip_partial_kernel, dim3((c->nk + 63) / 64, rsel.n > 0 ? rsel.n : ntile),
                        dim3(64 * kRecipWaves), sb, a, (const KVec *)c->d_kvec, c->nk, rsel, c->d_sfpart));
     c->recip_part_valid = true;
     return 0;
 }
 
-static int launch_publish(mpmc_hip_ctx *c, bool do_polar) {
+static int launch_publish(mpmc_hip_ctx *c) {
+    const bool do_polar = c->call.do_polar;
     // (one wave unless the kernel also has the pair kernel's tile partials to add up)
-    HIPCHK(launch_slot(c, GS_PUBLISH, publish_result_kernel, dim3(1), dim3(c->pair_rows_to_sum > 0 ? kReduceThreads : 64),
+    HIPCHK(launch_slot(c, GS_PUBLISH, publish_result_kernel, dim3(1), dim3(c->call.pair_rows_to_sum > 0 ? kReduceThreads : 64),
                        c->stream, c->d_res, c->h_res_dev,
                        (int)R_COUNT, (double)c->energy_calls, do_polar ? c->energy_part : (const double *)nullptr,
                        do_polar ? c->energy_nt : 0, c->n_valid,
-                       c->gs_used[0] ? (const unsigned *)(c->view[0].gsflags + 1) : (const unsigned *)nullptr,
-                       c->gs_used[1] ? (const unsigned *)(c->view[1].gsflags + 1) : (const unsigned *)nullptr,
-                       (const double *)c->d_recipsum, c->call_split ? 0 : c->recip_chunks, c->res_zero_mask,
-                       (const double *)c->d_pairpart, c->pair_rows_to_sum, (int)R_RD_PAIR, c->call_split ? kSideSlots : 0u));
+                       c->call.gs_used[0] ? (const unsigned *)(c->view[0].gsflags + 1) : (const unsigned *)nullptr,
+                       c->call.gs_used[1] ? (const unsigned *)(c->view[1].gsflags + 1) : (const unsigned *)nullptr,
+                       (const double *)c->d_recipsum, c->call.split ? 0 : c->call.recip_chunks, c->call.res_zero_mask,
+                       (const double *)c->d_pairpart, c->call.pair_rows_to_sum, (int)R_RD_PAIR, c->call.split ? kSideSlots : 0u));
     return 0;
+}
+
+// atoms -> the 64-atom blocks they are in, each once (unused entries zero); false: more blocks than the list holds
+static bool blocks_of(const std::vector<int> &atoms, DirtyBlocks &out) {
+    memset(&out, 0, sizeof(out));
+    for (int atom : atoms) {
+        const int b = atom / 64;
+        bool seen = false;
+        for (int k = 0; k < out.n; ++k) seen |= (out.blk[k] == b);
+        if (seen) continue;
+        if (out.n == kMaxDirtyBlocks) {
+            memset(&out, 0, sizeof(out));
+            return false;
+        }
+        out.blk[out.n++] = b;
+    }
+    return true;
 }
 
 // 64-atom blocks touched by the moves since the last call (n = 0: recompute every tile)
 static void collect_dirty_blocks(mpmc_hip_ctx *c) {
-    DirtyBlocks dirty_blocks;
-    dirty_blocks.n = 0;
-    if (c->all_dirty || !c->opt_incremental_pairs) {
+    DirtyBlocks &d = c->call.dirty_blocks;
+    if (c->all_dirty || !c->opt.incremental_pairs || !blocks_of(c->dirty_atoms, d)) {
         c->pair_part_valid = c->field_part_valid = false;
-    } else {
-        for (int atom : c->dirty_atoms) {
-            const int b = atom / 64;
-            bool seen = false;
-            for (int k = 0; k < dirty_blocks.n; ++k) seen |= (dirty_blocks.blk[k] == b);
-            if (seen) continue;
-            if (dirty_blocks.n == kMaxDirtyBlocks) {
-                c->pair_part_valid = c->field_part_valid = false;
-                dirty_blocks.n = 0;
-                break;
-            }
-            dirty_blocks.blk[dirty_blocks.n++] = b;
-        }
+        memset(&d, 0, sizeof(d));
     }
-    for (int k = dirty_blocks.n; k < kMaxDirtyBlocks; ++k) dirty_blocks.blk[k] = 0;
-    c->dirty_blocks = dirty_blocks;
-    c->pair_part_valid_before = c->pair_part_valid;  // false whenever the dirty-block list cannot be trusted
+    c->call.pair_part_valid_before = c->pair_part_valid;  // false whenever the dirty-block list cannot be trusted
+}
+
+// The one place an evaluation starts: energy_begin(), and energy_end() when it has to repeat a call.
+static void begin_call(mpmc_hip_ctx *c) {
+    ++c->energy_calls;
+    c->ev_next = 0;
+    c->recs.clear();
+    c->call = CallState();
+    collect_dirty_blocks(c);
 }
 
 // One evaluation, launch by launch (also what stream capture records for the step graph).
 static int enqueue_direct(mpmc_hip_ctx *c) {
-    c->recip_chunks = 0;
-    c->res_zero_mask = 0;
-    c->call_resident = false;
+    const mpmc_hip_params &P = c->par;
+    CallState &k = c->call;
+    k.do_polar = !P.rd_only && P.polarization;
+    k.gs_mode = P.polar_gs || P.polar_gs_ranked;
+    // ---- fork: LJ / Ewald kernels (fp64-VALU bound) run on stream2 while the polarization chain
+    // (HBM bound) runs on the main stream -- the device-side analogue of the reference starting its
+    // polarization worker before the other energy terms (energy.c:108-129, :181-186).
+    // (without polarization there is nothing to overlap with: one stream, and no fork / join events -- a cross-stream
+    //  dependency costs several microseconds each way, a quarter of an LJ-only step)
+    k.two_streams = c->opt.overlap && k.do_polar;
+    k.plain_launches = c->graph_mode == GM_DIRECT && !c->opt.graph;  // (neither changes while the call is enqueued)
+    const bool do_polar = k.do_polar, two_streams = k.two_streams;
     // A single-molecule move of a steady-state polarizable step is applied inside the coefficient update of view 0
     // (update_coef_moves_kernel) instead of by a launch of its own; setup_view() falls back to the plain way whenever
     // that update does not happen.  (Not in the Gauss-Seidel modes: their ranking kernels read the coordinates first.)
-    {
-        const mpmc_hip_params &Pm = c->par;
-        // (Gauss-Seidel modes, round 3: with the chain kernel's data -- whose maintenance follows the coefficient update
-        //  inside setup_view() -- the move rides in update_coef_moves_kernel too, as a launch of its own in front of the block
-        //  matrices instead of apply_moves_kernel + update_coef_kernel; the side stream, whose ranking kernels read the
-        //  coordinates, applies the same move for itself as before (side_apply).  Option "gs_fuse_moves".)
-        const bool gs = Pm.polar_gs || Pm.polar_gs_ranked;
-        c->moves_deferred = c->opt_fuse_moves && c->pending.n > 0 && c->graph_mode == GM_DIRECT && !c->opt_graph &&
-                            !Pm.rd_only && Pm.polarization && !Pm.polar_zodid && (!gs || (c->opt_gs_fuse_moves && gs_order_mode(c))) &&
-                            Pm.polar_precision == 0.0 && c->opt_overlap && c->opt_pair_coef && !c->all_dirty &&
-                            c->view[0].C_valid && c->view[0].pos_valid;
-    }
+    // (Gauss-Seidel modes, round 3: with the chain kernel's data -- whose maintenance follows the coefficient update
+    //  inside setup_view() -- the move rides in update_coef_moves_kernel too, as a launch of its own in front of the block
+    //  matrices instead of apply_moves_kernel + update_coef_kernel; the side stream, whose ranking kernels read the
+    //  coordinates, applies the same move for itself as before (side_apply).  Option "gs_fuse_moves".)
+    k.moves_deferred = c->opt.fuse_moves && c->pending.n > 0 && k.plain_launches && do_polar && !P.polar_zodid &&
+                       (!k.gs_mode || (c->opt.gs_fuse_moves && gs_order_mode(c))) && P.polar_precision == 0.0 && c->opt.overlap &&
+                       c->opt.pair_coef && !c->all_dirty && c->view[0].C_valid && c->view[0].pos_valid;
     // Without polarization the pair kernel is the first kernel of the step that reads coordinates: the move rides in it.
     // (The long-range-correction and self-term kernels in front of it read parameters only.)
-    c->moves_in_pair = !c->moves_deferred && c->opt_fuse_moves && c->pending.n > 0 && c->graph_mode == GM_DIRECT &&
-                       !c->opt_graph && !(!c->par.rd_only && c->par.polarization) && !c->dirty_atoms.empty();
-    c->side_apply.n = 0;
-    c->side_applied = false;
-    if (!c->moves_deferred && !c->moves_in_pair) {
-        const mpmc_hip_params &Pm = c->par;
-        if (c->opt_side_moves && !c->main_writes && c->pending.n > 0 && c->opt_overlap && !Pm.rd_only && Pm.polarization &&
-            c->graph_mode == GM_DIRECT && !c->opt_graph)
-            c->side_apply = c->pending;  // (the side stream applies it too: no fork event, see side_wait_for_moves)
+    k.moves_in_pair = !k.moves_deferred && c->opt.fuse_moves && c->pending.n > 0 && k.plain_launches && !do_polar &&
+                      !c->dirty_atoms.empty();
+    if (!k.moves_deferred && !k.moves_in_pair) {
+        if (c->opt.side_moves && !c->main_writes && c->pending.n > 0 && two_streams && k.plain_launches)
+            k.side_apply = c->pending;  // (the side stream applies it too: no fork event, see side_wait_for_moves)
         if (flush_moves(c)) return -1;
-    } else if (c->moves_deferred && (c->par.polar_gs || c->par.polar_gs_ranked)) {
-        if (c->opt_side_moves && !c->main_writes) c->side_apply = c->pending;  // (else: the fork event behind the coefficient job)
+    } else if (k.moves_deferred && k.gs_mode) {
+        if (c->opt.side_moves && !c->main_writes) k.side_apply = c->pending;  // (else: the fork event behind the coefficient job)
     }
     // (the pair kernel is launched whenever an atom moved; the long-range-correction kernels in front of it read
     //  parameters only)
-    c->side_carry = c->moves_deferred && !(c->par.polar_gs || c->par.polar_gs_ranked) && c->opt_side_moves && !c->main_writes &&
-                    !c->dirty_atoms.empty() && c->pending.n <= kMaxMoves;
-    c->side_moves.n = 0;
+    k.side_carry = k.moves_deferred && !k.gs_mode && c->opt.side_moves && !c->main_writes && !c->dirty_atoms.empty() &&
+                   c->pending.n <= kMaxMoves;
     if (is_timed_call(c)) hipEventRecord(c->ev_first, c->stream);
 
     const DevAtoms a = dev_atoms(c);
     const DevBox bx = dev_box(c);
     const int ntile = c->npad / 64;
     int polar_iterations = 0, iter_success = 0;
-    const mpmc_hip_params &P = c->par;
 
-    // ---- fork: LJ / Ewald kernels (fp64-VALU bound) run on stream2 while the polarization chain
-    // (HBM bound) runs on the main stream -- the device-side analogue of the reference starting its
-    // polarization worker before the other energy terms (energy.c:108-129, :181-186).
-    // (without polarization there is nothing to overlap with: one stream, and no fork / join events -- a cross-stream
-    //  dependency costs several microseconds each way, a quarter of an LJ-only step)
-    const bool two_streams = c->opt_overlap && !P.rd_only && P.polarization;
     hipStream_t sb = two_streams ? c->stream2 : c->stream;
     // The side stream publishes its own slots of the record (no join event) in the Jacobi-type modes; the Gauss-Seidel
     // modes keep the join (their ranking kernels share slots and streams with the chain), and so does graph capture.
-    c->call_split = two_streams && c->opt_split_record && !P.polar_gs && !P.polar_gs_ranked && c->graph_mode == GM_DIRECT &&
-                    !c->opt_graph;
-    if (two_streams && !c->moves_deferred && c->side_apply.n == 0)
+    k.split = two_streams && c->opt.split_record && !k.gs_mode && k.plain_launches;
+    if (two_streams && !k.moves_deferred && k.side_apply.n == 0)
         hipEventRecord(c->ev_fork, c->stream);  // (the side stream's wait is issued when it is fed)
-
-    const bool do_polar = !P.rd_only && P.polarization;
     // Enqueue order: the host needs ~3 us per launch and the polarization chain is the critical path, so
     // with a fixed iteration count the chain is enqueued up to its first sweep (by then the device has
     // ~40 us of work queued), then the side-stream kernels, then the remaining sweeps (option "side_after":
@@ -1979,27 +1982,14 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
         side_done = true;
         side_rc = [&]() -> int {
         // after apply_moves: the new coordinates are in place (unless this stream's pair kernel brings the move itself)
-        if (two_streams && !(c->side_carry && c->side_moves.n > 0)) side_wait_for_moves(c, sb);
+        if (two_streams && !(k.side_carry && k.side_moves.n > 0)) side_wait_for_moves(c, sb);
         // ---- LJ long-range correction: parameters + volume only => cached (lj.c:56-107)
         if (P.rd_lrc) {
             // depends on parameters, the volume and WHICH atoms exist -- not on coordinates: summed once, its
             // tile partials kept, and only the tiles of inserted / removed atoms' blocks redone afterwards
             DirtyBlocks lsel;
-            lsel.n = 0;
-            bool overflow = false;
-            for (int atom : c->lrc_dirty_atoms) {
-                const int b = atom / 64;
-                bool seen = false;
-                for (int k = 0; k < lsel.n; ++k) seen |= (lsel.blk[k] == b);
-                if (seen) continue;
-                if (lsel.n == kMaxDirtyBlocks) {
-                    overflow = true;
-                    break;
-                }
-                lsel.blk[lsel.n++] = b;
-            }
-            for (int k = lsel.n; k < kMaxDirtyBlocks; ++k) lsel.blk[k] = 0;
-            if (!c->lrc_valid || overflow) lsel.n = 0;
+            const bool overflow = !blocks_of(c->lrc_dirty_atoms, lsel);
+            if (!c->lrc_valid) lsel.n = 0;
             if (!c->lrc_valid || overflow || lsel.n > 0) {
                 ScopedTimer t(c, T_OTHER, sb);
                 hipLaunchKernelGGL(lj_lrc_kernel, dim3(ntile, lsel.n > 0 ? lsel.n : ntile), dim3(64 * kLrcWaves), 0, sb, a, bx, lsel,
@@ -2010,7 +2000,7 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
             }
             c->lrc_dirty_atoms.clear();
         } else {
-            c->res_zero_mask |= 1u << R_LRC;  // (zeroed by the publish kernel: a memset is a launch of its own)
+            k.res_zero_mask |= 1u << R_LRC;  // (zeroed by the publish kernel: a memset is a launch of its own)
             c->lrc_valid = false;
         }
 
@@ -2033,9 +2023,9 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
                 // beside the polarization chain the sum is free on the side stream, and would be 3.5 us of the main one
                 hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(kReduceThreads), 0, sb, c->d_pairpart, ntile * ntile,
                                    kPairChannels, c->d_res + R_RD_PAIR);
-                c->pair_rows_to_sum = 0;
+                k.pair_rows_to_sum = 0;
             } else {
-                c->pair_rows_to_sum = ntile * ntile;  // summed by the publish kernel (same arithmetic, one launch less)
+                k.pair_rows_to_sum = ntile * ntile;  // summed by the publish kernel (same arithmetic, one launch less)
             }
         }
 
@@ -2043,12 +2033,12 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
         if (!P.rd_only && !P.wolf) {
             ScopedTimer t(c, T_RECIP, sb);
             if (c->nk > 0) {
-                if (!c->recip_fused && launch_recip_partial(c, a, sb)) return -1;
+                if (!k.recip_fused && launch_recip_partial(c, a, sb)) return -1;
                 hipLaunchKernelGGL(recip_sum_kernel, dim3((c->nk + 63) / 64), dim3(64 * kRecipGroups), 0, sb, c->d_kvec,
                                    c->nk, ntile, c->d_sfpart, c->d_recipsum);
-                c->recip_chunks = (c->nk + 63) / 64;
+                k.recip_chunks = (c->nk + 63) / 64;
             } else {
-                c->res_zero_mask |= 1u << R_RECIP;
+                k.res_zero_mask |= 1u << R_RECIP;
             }
             // depends on the charges and alpha only: summed at upload / edit / parameter change, then kept in d_res
             if (!c->self_valid || c->self_alpha != c->ewald_alpha) {
@@ -2057,51 +2047,50 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
                 c->self_alpha = c->ewald_alpha;
             }
         } else {
-            c->res_zero_mask |= (1u << R_RECIP) | (1u << R_SELF);
+            k.res_zero_mask |= (1u << R_RECIP) | (1u << R_SELF);
             c->self_valid = false;
         }
-        if (c->call_split)
+        if (k.split)
             hipLaunchKernelGGL(publish_side_kernel, dim3(1), dim3(64), 0, sb, c->d_res, c->h_res2_dev, (int)R_COUNT,
-                               (double)c->energy_calls, (const double *)c->d_recipsum, c->recip_chunks, c->res_zero_mask,
+                               (double)c->energy_calls, (const double *)c->d_recipsum, k.recip_chunks, k.res_zero_mask,
                                kSideSlots);
         else if (two_streams)
             hipEventRecord(c->ev_join, sb);
         return 0;
         }();
     };
-    c->enqueue_side = polar_first ? std::function<void()>(enqueue_side) : std::function<void()>();
+    k.enqueue_side = polar_first ? std::function<void()>(enqueue_side) : std::function<void()>();
     if (!polar_first) enqueue_side();
     {
         // ---- polarization (main stream)
         if (do_polar) {
             if (run_polarization(c, a, bx, &polar_iterations, &iter_success)) {
-                c->enqueue_side = nullptr;
+                k.enqueue_side = nullptr;
                 return -1;
             }
-            if (c->moves_deferred) return fail("MPMC_HIP: internal: a deferred move was not applied");
+            if (k.moves_deferred) return fail("MPMC_HIP: internal: a deferred move was not applied");
         } else {
-            c->res_zero_mask |= (1u << R_UPOL) | (1u << R_RRMS);
+            k.res_zero_mask |= (1u << R_UPOL) | (1u << R_RRMS);
         }
         // the resident A only tracks moves while it is being maintained
         if (!do_polar || P.polar_zodid) c->view[0].A_valid = c->view[0].C_valid = false;
     }
-    c->enqueue_side = nullptr;
+    k.enqueue_side = nullptr;
     enqueue_side();
     if (side_rc) return -1;
     if (c->pending.n > 0 && flush_moves(c)) return -1;  // (a move no launch of this call carried: cannot happen, but cheap)
-    c->moves_in_pair = false;
-    if (c->build_join_pending) {  // (a builder launch no chain launch of this call waited for)
+    k.moves_in_pair = false;
+    if (k.build_join_pending) {  // (a builder launch no chain launch of this call waited for)
         hipStreamWaitEvent(c->stream, c->ev_bjoin, 0);
-        c->build_join_pending = false;
+        k.build_join_pending = false;
     }
-    if (two_streams && !c->call_split) hipStreamWaitEvent(c->stream, c->ev_join, 0);
+    if (two_streams && !k.split) hipStreamWaitEvent(c->stream, c->ev_join, 0);
     const bool timed_call = is_timed_call(c);
     if (timed_call) hipEventRecord(c->ev_last, c->stream);
-    if (launch_publish(c, do_polar)) return -1;
-    c->call_polar = do_polar;
-    c->call_iterations = polar_iterations;
-    c->call_iter_success = iter_success;
-    c->call_timed = timed_call;
+    if (launch_publish(c)) return -1;
+    k.iterations = polar_iterations;
+    k.iter_success = iter_success;
+    k.timed = timed_call;
     return 0;
 }
 
@@ -2119,13 +2108,13 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
 static bool graph_eligible(mpmc_hip_ctx *c) {
     const mpmc_hip_params &P = c->par;
     const SweepView &v = c->view[0];
-    if (!c->opt_graph || is_timed_call(c) || !c->opt_incremental || !c->opt_incremental_pairs ||
-        !c->opt_pair_coef)
+    if (!c->opt.graph || is_timed_call(c) || !c->opt.incremental || !c->opt.incremental_pairs ||
+        !c->opt.pair_coef)
         return false;
     if (P.rd_only || !P.polarization || P.polar_zodid || P.polar_gs || P.polar_gs_ranked || P.polar_precision != 0.0 ||
         P.polar_max_iter <= 0)
         return false;
-    if (c->all_dirty || c->staged_copies || c->pending.n <= 0 || c->dirty_blocks.n < 1) return false;
+    if (c->all_dirty || c->staged_copies || c->pending.n <= 0 || c->call.dirty_blocks.n < 1) return false;
     if (!v.C_valid || !v.pos_valid || !c->pair_part_valid || !c->field_part_valid) return false;
     if (P.rd_lrc && !c->lrc_valid) return false;
     if (P.polar_ewald && !c->kvecf_valid) return false;
@@ -2174,7 +2163,12 @@ static int graph_step(mpmc_hip_ctx *c) {
     timespec g0, g1, g2;
     clock_gettime(CLOCK_MONOTONIC, &g0);
     c->graph_mode = GM_UPDATE;
-    c->call_split = false;  // (a captured step joins its two streams and publishes one record)
+    // what the publish launch takes from the call: as the captured call left it (split stays false: a captured step joins
+    // its two streams and publishes one record)
+    c->call.do_polar = true;
+    c->call.recip_chunks = c->sg.recip_chunks;
+    c->call.res_zero_mask = c->sg.res_zero_mask;
+    c->call.pair_rows_to_sum = c->sg.pair_rows_to_sum;
     int rc = flush_moves(c);
     if (!rc) rc = setup_view(c, c->view[0], a, bx, true, true, false);
     if (!rc) rc = launch_field(c, a, bx);
@@ -2182,7 +2176,7 @@ static int graph_step(mpmc_hip_ctx *c) {
     if (!rc && c->sg.func[GS_RECIP]) rc = launch_recip_partial(c, a, c->stream2);
     c->energy_part = c->sg.energy_part;
     c->energy_nt = c->sg.energy_nt;
-    if (!rc) rc = launch_publish(c, true);
+    if (!rc) rc = launch_publish(c);
     c->graph_mode = GM_DIRECT;
     if (rc) return -1;
     clock_gettime(CLOCK_MONOTONIC, &g1);
@@ -2194,10 +2188,7 @@ static int graph_step(mpmc_hip_ctx *c) {
     c->result_mu = c->sg.result_mu;
     c->results_scattered = false;
     c->have_polar_result = true;
-    c->call_polar = true;
-    c->call_iterations = c->sg.iterations;
-    c->call_iter_success = 0;
-    c->call_timed = false;
+    c->call.iterations = c->sg.iterations;
     ++c->graph_launches;
     return 0;
 }
@@ -2227,12 +2218,9 @@ extern "C" int mpmc_hip_energy_begin(mpmc_hip_ctx *c) {
         if (build_kvectors(c)) return -1;
         c->kvec_kmax = P.ewald_kmax;
     }
-    c->ev_next = 0;
-    c->recs.clear();
-    ++c->energy_calls;
     timespec ts0, ts1;
     clock_gettime(CLOCK_MONOTONIC, &ts0);
-    collect_dirty_blocks(c);
+    begin_call(c);
     bool issued = false;
     if (graph_eligible(c)) {
         if (c->sg.valid && c->sg.rev == c->config_rev) {
@@ -2255,11 +2243,14 @@ extern "C" int mpmc_hip_energy_begin(mpmc_hip_ctx *c) {
             if (ok) {
                 c->sg.valid = true;
                 c->sg.rev = c->config_rev;
-                c->sg.iterations = c->call_iterations;
+                c->sg.iterations = c->call.iterations;
                 c->sg.result_view = c->result_view;
                 c->sg.result_mu = c->result_mu;
                 c->sg.energy_part = c->energy_part;
                 c->sg.energy_nt = c->energy_nt;
+                c->sg.recip_chunks = c->call.recip_chunks;
+                c->sg.res_zero_mask = c->call.res_zero_mask;
+                c->sg.pair_rows_to_sum = c->call.pair_rows_to_sum;
                 HIPCHK(hipGraphLaunch(c->sg.exec, c->stream));
                 ++c->graph_launches;
                 issued = true;
@@ -2267,8 +2258,10 @@ extern "C" int mpmc_hip_energy_begin(mpmc_hip_ctx *c) {
                 // could not record: keep working launch by launch
                 (void)hipGetLastError();
                 graph_destroy(c);
-                c->opt_graph = 0;
+                c->opt.graph = 0;
                 c->pending = saved;
+                c->call = CallState();  // (whatever the abandoned capture left)
+                collect_dirty_blocks(c);
             }
         }
     } else {
@@ -2285,6 +2278,35 @@ extern "C" int mpmc_hip_energy_begin(mpmc_hip_ctx *c) {
     return 0;
 }
 
+// spin on a sequence number a publish kernel writes last; fall back to a stream sync if it does not show up (also
+// surfaces launch errors)
+static int wait_sequence(volatile double *seq, double want, hipStream_t stream) {
+    for (unsigned long long spins = 0; spins < 2000000000ull; ++spins) {
+        if (*seq == want) return 0;
+        if ((spins & 0xfffffull) == 0xfffffull && hipStreamQuery(stream) != hipErrorNotReady) break;
+        __builtin_ia32_pause();
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+static int wait_record(mpmc_hip_ctx *c) {
+    const double want = (double)c->energy_calls;
+    if (wait_sequence(c->h_res + R_COUNT, want, c->stream)) return -1;
+    // the side stream's part has a sequence number of its own
+    return c->call.split ? wait_sequence(c->h_res2 + R_COUNT, want, c->stream2) : 0;
+}
+
+// energy_end(): the call it collected cannot be used; the same evaluation once more, with `flag` (what makes it take the
+// other path) held true while it is enqueued
+static int repeat_call(mpmc_hip_ctx *c, bool &flag) {
+    flag = true;
+    begin_call(c);
+    const int rc = enqueue_direct(c);
+    flag = false;
+    return rc ? -1 : wait_record(c);
+}
+
 extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
     if (!c || !out) return fail("MPMC_HIP: energy: null argument");
     if (!c->in_flight) return fail("MPMC_HIP: energy_end: no evaluation in flight");
@@ -2293,55 +2315,16 @@ extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
     const mpmc_hip_params &P = c->par;
     timespec ts1, ts2;
     clock_gettime(CLOCK_MONOTONIC, &ts1);
-    auto wait_record = [&]() -> int {
-        // spin on the sequence number the publish kernel writes last; fall back to a stream sync if it
-        // does not show up (also surfaces launch errors)
-        volatile double *seq = c->h_res + R_COUNT;
-        const double want = (double)c->energy_calls;
-        bool seen = false;
-        for (unsigned long long spins = 0; spins < 2000000000ull; ++spins) {
-            if (*seq == want) {
-                seen = true;
-                break;
-            }
-            if ((spins & 0xfffffull) == 0xfffffull && hipStreamQuery(c->stream) != hipErrorNotReady) break;
-            __builtin_ia32_pause();
-        }
-        if (!seen) HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->call_split) {  // the side stream's part has a sequence number of its own
-            volatile double *seq2 = c->h_res2 + R_COUNT;
-            seen = false;
-            for (unsigned long long spins = 0; spins < 2000000000ull; ++spins) {
-                if (*seq2 == want) {
-                    seen = true;
-                    break;
-                }
-                if ((spins & 0xfffffull) == 0xfffffull && hipStreamQuery(c->stream2) != hipErrorNotReady) break;
-                __builtin_ia32_pause();
-            }
-            if (!seen) HIPCHK(hipStreamSynchronize(c->stream2));
-        }
-        return 0;
-    };
-    if (wait_record()) return -1;
-    if (c->call_spec_rank && c->h_res[R_GS_ERR] == 0.0 && c->h_res[R_RANKCHG] != 0.0) {
+    if (wait_record(c)) return -1;
+    if (c->call.spec_rank && c->h_res[R_GS_ERR] == 0.0 && c->h_res[R_RANKCHG] != 0.0) {
         // polar_gs_ranked, speculative call: the ranking metric is not the one the resident ranked view was built
         // for (molecules came within 1.5 r_min of each other, or moved apart again).  Nothing that call produced is
         // used; the evaluation is repeated with the host sorting the new metric (which rebuilds the ranked view).
         // Everything else resident -- pair / field partials, view 0 -- is already up to date and is not redone.
         ++c->spec_redos;
-        c->force_host_rank = true;
-        ++c->energy_calls;
-        c->ev_next = 0;
-        c->recs.clear();
-        c->gs_used[0] = c->gs_used[1] = false;
-        collect_dirty_blocks(c);
-        const int rc = enqueue_direct(c);
-        c->force_host_rank = false;
-        if (rc) return -1;
-        if (wait_record()) return -1;
+        if (repeat_call(c, c->force_host_rank)) return -1;
     }
-    if (c->call_resident && c->h_res[R_GS_ERR] != 0.0) {
+    if (c->call.resident && c->h_res[R_GS_ERR] != 0.0) {
         // The resident Jacobi launch gave up on a hand-off (its workgroups were not all running at once: the device
         // is shared with another process, or a test asked for it).  Nothing it produced is used: the evaluation is
         // repeated on the multi-launch path, which this context then keeps to; the partial-sum slots are refilled
@@ -2353,26 +2336,16 @@ extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
         c->resident_backoff = c->resident_backoff ? std::min(2 * c->resident_backoff, 1L << 20) : 4096;
         c->resident_retry_at = (long)c->energy_calls + c->resident_backoff;
         c->view[0].resP_armed = false;
-        c->force_multi_launch = true;
-        ++c->energy_calls;
-        c->ev_next = 0;
-        c->recs.clear();
-        c->gs_used[0] = c->gs_used[1] = false;
-        collect_dirty_blocks(c);
-        const int rc = enqueue_direct(c);
-        c->force_multi_launch = false;
-        if (rc) return -1;
-        if (wait_record()) return -1;
+        if (repeat_call(c, c->force_multi_launch)) return -1;
     }
     clock_gettime(CLOCK_MONOTONIC, &ts2);
     c->host_wait_s += (ts2.tv_sec - ts1.tv_sec) + 1e-9 * (ts2.tv_nsec - ts1.tv_nsec);
-    const bool do_polar = c->call_polar, timed_call = c->call_timed;
-    const int polar_iterations = c->call_iterations, iter_success = c->call_iter_success;
+    const bool do_polar = c->call.do_polar, timed_call = c->call.timed;
+    const int polar_iterations = c->call.iterations, iter_success = c->call.iter_success;
     const int gs_err = (int)c->h_res[R_GS_ERR];
     c->h_gserr[0] = gs_err & 1;
     c->h_gserr[1] = (gs_err >> 1) & 1;
     const bool gs_timeout = gs_err != 0;
-    c->gs_used[0] = c->gs_used[1] = false;
     if (gs_timeout) {
         unsigned dbg[8] = {0};
         const SweepView &gv = c->view[c->h_gserr[1] ? 1 : 0];
@@ -2386,7 +2359,7 @@ extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
     c->stage_used = 0;
 
     double r[R_COUNT];
-    for (int k = 0; k < R_COUNT; ++k) r[k] = (c->call_split && ((kSideSlots >> k) & 1u)) ? c->h_res2[k] : c->h_res[k];
+    for (int k = 0; k < R_COUNT; ++k) r[k] = (c->call.split && ((kSideSlots >> k) & 1u)) ? c->h_res2[k] : c->h_res[k];
     const double rd = r[R_RD_PAIR] + r[R_LRC];
     const double real = r[R_ES_REAL] - r[R_ES_INTRA];
     const bool ewald = !P.rd_only && !P.wolf;

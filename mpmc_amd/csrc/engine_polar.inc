@@ -10,12 +10,12 @@ static constexpr bool kSweepSplitAuto = false;
 
 // the coefficient update setup_view() prepared, as a launch of its own (when it cannot ride in the field kernel's)
 static int launch_coef_job(mpmc_hip_ctx *c, const DevBox &bx) {
-    if (!c->coef_job_valid) return 0;
-    c->coef_job_valid = false;
-    const CoefJob &cj = c->coef_job;
+    if (!c->call.coef_job_valid) return 0;
+    c->call.coef_job_valid = false;
+    const CoefJob &cj = c->call.coef_job;
     hipLaunchKernelGGL(update_coef_moves_kernel, dim3(cj.nt, cj.dm.n), dim3(64), 0, c->stream, cj.pa, bx, cj.damp, cj.dm,
                        cj.ntld, cj.C, cj.m, cj.gx, cj.gy, cj.gz, cj.slot_of_atom, cj.px, cj.py, cj.pz);
-    if (c->coef_job_fork) hipEventRecord(c->ev_fork, c->stream);
+    if (c->call.coef_job_fork) hipEventRecord(c->ev_fork, c->stream);
     return 0;
 }
 
@@ -35,7 +35,7 @@ static int launch_field(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx) {
     // skipped, after a single-molecule move only the tiles of the moved atoms' blocks are recomputed.
     const int mode = P.polar_ewald ? kFieldEwald : (!P.polar_wolf ? kFieldBare : (P.polar_wolf_alpha == 0.0 ? kFieldWolf0 : kFieldWolfA));
     const int key = mode * 1000003 + chunk;
-    DirtyBlocks sel = c->dirty_blocks;
+    DirtyBlocks sel = c->call.dirty_blocks;
     const bool resident = c->field_part_valid && c->field_key == key;
     if (!resident) sel.n = 0;
     const bool skip = resident && sel.n == 0 && c->dirty_atoms.empty();
@@ -45,9 +45,9 @@ static int launch_field(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx) {
     // The step's coefficient update (and with it the move) rides in a third z-slice of the incremental grid when there
     // is one and it has room (8 units of 64 partners per workgroup); otherwise it is a launch of its own, here.
     bool fused = false;
-    if (c->coef_job_valid) {
-        const CoefJob &cj = c->coef_job;
-        fused = c->opt_fuse_field && !skip && sel.n > 0 && !P.polar_ewald && c->graph_mode == GM_DIRECT &&
+    if (c->call.coef_job_valid) {
+        const CoefJob &cj = c->call.coef_job;
+        fused = c->opt.fuse_field && !skip && sel.n > 0 && !P.polar_ewald && c->graph_mode == GM_DIRECT &&
                 (long)grid.x * sel.n * kFieldWaves >= (long)cj.nt * cj.dm.n;
         if (fused) grid.z = 3;
         else if (launch_coef_job(c, bx)) return -1;
@@ -70,8 +70,8 @@ static int launch_field(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx) {
         return 0;
     }
     if (fused) {
-        const CoefJob &cj = c->coef_job;
-        c->coef_job_valid = false;
+        const CoefJob &cj = c->call.coef_job;
+        c->call.coef_job_valid = false;
         if (!P.polar_wolf) {
             hipLaunchKernelGGL(field_coef_kernel<kFieldBare>, grid, block, 0, c->stream, a, bx, fp, sel, c->d_fieldpart, cj);
         } else if (P.polar_wolf_alpha == 0.0) {
@@ -82,7 +82,7 @@ static int launch_field(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx) {
             hipLaunchKernelGGL(field_coef_kernel<kFieldWolfA>, grid, block, 0, c->stream, a, bx, fp, sel, c->d_fieldpart, cj);
         }
         HIPCHK(hipGetLastError());
-        if (c->coef_job_fork) hipEventRecord(c->ev_fork, c->stream);
+        if (c->call.coef_job_fork) hipEventRecord(c->ev_fork, c->stream);
     } else if (!skip) {
         if (!P.polar_wolf) {
             HIPCHK(launch_slot(c, GS_FIELD, static_field_kernel<kFieldBare>, grid, block, c->stream, a, bx, fp, sel, c->d_fieldpart));
@@ -101,11 +101,11 @@ static int launch_field(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx) {
 
 // the pending move, the plain way (apply_moves_kernel), when it could not ride inside the coefficient update
 static int apply_deferred_moves(mpmc_hip_ctx *c) {
-    if (!c->moves_deferred) return 0;
-    c->moves_deferred = false;
-    c->side_carry = false;  // (the side stream waits for the event below)
+    if (!c->call.moves_deferred) return 0;
+    c->call.moves_deferred = false;
+    c->call.side_carry = false;  // (the side stream waits for the event below)
     if (flush_moves(c)) return -1;
-    if (c->opt_overlap) hipEventRecord(c->ev_fork, c->stream);
+    if (c->opt.overlap) hipEventRecord(c->ev_fork, c->stream);
     return 0;
 }
 
@@ -136,9 +136,9 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
     // The step's move may still be pending (enqueue_direct defers it when this call can apply it inside the coefficient
     // update of view 0, below); anything else that is about to read coordinates needs it applied first.
     bool fuse_moves = false;
-    if (c->moves_deferred && &v == &c->view[0]) {
+    if (c->call.moves_deferred && &v == &c->view[0]) {
         fuse_moves = !side && incremental && v.pos_valid && want_coef && v.C_valid && v.rebuild_from < 0 && !c->all_dirty &&
-                     c->opt_incremental;
+                     c->opt.incremental;
         if (!fuse_moves && apply_deferred_moves(c)) return -1;
     }
     if (!(incremental && v.pos_valid)) {
@@ -161,7 +161,7 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
     // that involve a moved atom are rewritten (bit-identical to a full rebuild).
     DirtyList dl;
     int nd = 0;
-    const bool can_update = incremental && !c->all_dirty && c->opt_incremental && collect_dirty_slots(c, v, dl, nd);
+    const bool can_update = incremental && !c->all_dirty && c->opt.incremental && collect_dirty_slots(c, v, dl, nd);
     const int nt = std::max(1, (v.nv + kCoefTile - 1) / kCoefTile);
     bool coef_updated = false;  // C was brought up to date by rewriting the dirty slots' entries only
     // a view whose ORDER changed from block `tail` on (set_sweep_order after a grand-canonical edit): the data of the
@@ -208,7 +208,7 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
                 if (all_found) {
                     // handed to launch_field(), the next launch of the chain, which lets it ride in the field kernel's
                     // grid (field_coef_kernel) or, when it cannot, launches update_coef_moves_kernel in front of it
-                    CoefJob &cj = c->coef_job;
+                    CoefJob &cj = c->call.coef_job;
                     cj.pa = pa;
                     cj.damp = c->par.polar_damp;
                     cj.dm = dm;
@@ -223,13 +223,13 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
                     cj.px = v.px;
                     cj.py = v.py;
                     cj.pz = v.pz;
-                    c->coef_job_valid = true;
-                    if (c->side_carry) c->side_moves = c->pending;  // the side stream's pair kernel applies it too
+                    c->call.coef_job_valid = true;
+                    if (c->call.side_carry) c->call.side_moves = c->pending;  // the side stream's pair kernel applies it too
                     c->pending.n = 0;
-                    c->moves_deferred = false;
+                    c->call.moves_deferred = false;
                     // the new coordinates are in place (no event when the side stream does not wait for them: it carries the
                     // move in its pair kernel, or -- Gauss-Seidel modes -- applies it for itself first)
-                    c->coef_job_fork = c->opt_overlap && !c->side_carry && c->side_apply.n == 0;
+                    c->call.coef_job_fork = c->opt.overlap && !c->call.side_carry && c->call.side_apply.n == 0;
                     // with chain data to maintain, the job cannot wait for launch_field(): the block matrices below are
                     // functions of the updated coefficients
                     if (want_chain && launch_coef_job(c, bx)) return -1;
@@ -239,14 +239,14 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
                                        c->par.polar_damp, dl, v.ntld, v.C));
                 }
             } else if (nd > 0) {
-                if (c->moves_deferred && &v == &c->view[0] && apply_deferred_moves(c)) return -1;
+                if (c->call.moves_deferred && &v == &c->view[0] && apply_deferred_moves(c)) return -1;
                 HIPCHK(launch_slot(c, GS_COEF, update_coef_kernel, dim3(nt, nd), dim3(64), c->stream, pa, bx,
                                    c->par.polar_damp, dl, v.ntld, v.C));
             }
-            if (c->moves_deferred && &v == &c->view[0] && apply_deferred_moves(c)) return -1;  // (nd == 0: nothing fused)
+            if (c->call.moves_deferred && &v == &c->view[0] && apply_deferred_moves(c)) return -1;  // (nd == 0: nothing fused)
             coef_updated = true;
         } else {
-            if (c->moves_deferred && &v == &c->view[0] && apply_deferred_moves(c)) return -1;
+            if (c->call.moves_deferred && &v == &c->view[0] && apply_deferred_moves(c)) return -1;
             hipLaunchKernelGGL(build_coef_kernel, dim3(nt, nt), dim3(64 * kCoefWaves), 0, st, pa, bx,
                                c->par.polar_damp, v.ntld, v.C, 0);
             v.C_valid = true;
@@ -264,11 +264,11 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
         // How many lags a view caches is decided when it is rebuilt as a whole: the option's value -- unless the view was rebuilt
         // as a whole in the previous call too (a grand-canonical chain rebuilds its ranked view every step: the rebuild, not
         // the sweeps, bounds such a step, and a third lag costs it more than the shorter sweeps return: 1 380 vs 1 425 steps/s).
-        if (!fresh || v.nlag < 2 || v.nlag > c->opt_gs_lags) {
+        if (!fresh || v.nlag < 2 || v.nlag > c->opt.gs_lags) {
             // (three calls in a row: a ranked walk that changes and changes back in consecutive NVT steps keeps the full count)
             const bool again = v.last_full_call >= 0 && (unsigned long long)v.last_full_call + 1 >= c->energy_calls;
             v.full_streak = again ? v.full_streak + 1 : 0;
-            v.nlag = (v.full_streak >= 2) ? std::min(2, c->opt_gs_lags) : c->opt_gs_lags;
+            v.nlag = (v.full_streak >= 2) ? std::min(2, c->opt.gs_lags) : c->opt.gs_lags;
         }
         const int nlag = v.nlag;
         GsBuild gb;
@@ -344,7 +344,7 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
             int waves;
             if (st == c->stream)
                 waves = (48 * nsolve <= 256) ? 4 : ((24 * nsolve <= 256) ? 8 : 16);
-            else if (c->opt_gs_side_waves == 16)
+            else if (c->opt.gs_side_waves == 16)
                 waves = 16;
             else
                 waves = (48 * nsolve + chain_wgs <= 256) ? 4 : ((24 * nsolve + chain_wgs <= 256) ? 8 : 16);
@@ -354,7 +354,7 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
             // (Only for views of 24 blocks or more: below that the launches in between are short, the front of the step is bound
             //  by the host's launch rate, and the four event calls of the fork cost more than it hides -- 4 400 vs 4 650 steps/s
             //  at 1 024 atoms, +3 % at 4 096; option gs_build_fork = 2 forces it.)
-            if (st == c->stream && c->opt_inv_stamps <= 0 && (c->opt_gs_build_fork == 2 || (c->opt_gs_build_fork == 1 && nt >= 24))) {
+            if (st == c->stream && c->opt.inv_stamps <= 0 && (c->opt.gs_build_fork == 2 || (c->opt.gs_build_fork == 1 && nt >= 24))) {
                 HIPCHK(hipEventRecord(c->ev_bfork, c->stream));
                 HIPCHK(hipStreamWaitEvent(c->stream3, c->ev_bfork, 0));
                 bst = c->stream3;
@@ -362,7 +362,7 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
             const dim3 gi(192 / waves, nblk, full ? 2 : 2 + nlag), bi(64 * waves);
             unsigned long long *istamps = nullptr;
             const size_t nwg = (size_t)gi.x * gi.y * gi.z;
-            if (c->opt_inv_stamps > 0 && st == c->stream) {
+            if (c->opt.inv_stamps > 0 && st == c->stream) {
                 if (!c->d_istamps) HIPCHK(c->d_istamps.alloc((size_t)16 * 256 * 3 * 4));
                 if (nwg <= (size_t)16 * 256 * 3) {
                     HIPCHK(hipMemsetAsync(c->d_istamps, 0, nwg * 4 * sizeof(unsigned long long), st));
@@ -384,10 +384,10 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
 #undef MPMC_LAUNCH_INVERSE
             if (bst != st) {
                 HIPCHK(hipEventRecord(c->ev_bjoin, bst));
-                c->build_join_pending = true;
+                c->call.build_join_pending = true;
             }
             if (istamps) {  // diagnostic only: block, then print where the launch's time went
-                --c->opt_inv_stamps;
+                --c->opt.inv_stamps;
                 std::vector<unsigned long long> h(nwg * 4);
                 HIPCHK(hipStreamSynchronize(st));
                 HIPCHK(hipMemcpy(h.data(), istamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -460,13 +460,13 @@ static int launch_sweep(mpmc_hip_ctx *c, SweepView &v, const DevBox &bx, const d
             // the pass over the pair coefficients alone; on timed calls the kernel's own begin / end timestamps
             const int ntiles = nt * (nt + 1) / 2;
             // half-tile workgroups where a CU gets only a few tiles (beyond the resident solver's range, below ~8 per CU)
-            const bool split = c->opt_sweep_split > 0 || (c->opt_sweep_split < 0 && kSweepSplitAuto && nt > 21 && ntiles < 8 * c->num_cus);
+            const bool split = c->opt.sweep_split > 0 || (c->opt.sweep_split < 0 && kSweepSplitAuto && nt > 21 && ntiles < 8 * c->num_cus);
             half_plane = split ? 2 * (3 * (size_t)kCoefTile * nt) * (size_t)nt : 0;
             const dim3 g(split ? 16 * ((ntiles + 7) / 8) : ntiles), b(64 * kCoefWaves);
             // a tile set that fits the Infinity Cache is re-read from it sweep after sweep (default-policy loads: 32 vs
             // 38 us per sweep at 8192 atoms, 191 MB); one that does not is streamed (non-temporal: 145 vs 150 us at 16384)
             const size_t tile_bytes = (size_t)nt * (nt + 1) / 2 * kCoefTile * kCoefTile * sizeof(double2);
-            const bool sweep_nt = c->opt_sweep_nt > 0 || (c->opt_sweep_nt < 0 && tile_bytes > ((size_t)224 << 20));
+            const bool sweep_nt = c->opt.sweep_nt > 0 || (c->opt.sweep_nt < 0 && tile_bytes > ((size_t)224 << 20));
             void (*kern)(const double2 *, int, int, const double *, const double *, const double *, const double *, DevBox,
                          double *, double *, int, size_t) =
                 c->box_ortho ? (sweep_nt ? pair_sweep_kernel<1, 1> : pair_sweep_kernel<1, 0>)
@@ -474,12 +474,12 @@ static int launch_sweep(mpmc_hip_ctx *c, SweepView &v, const DevBox &bx, const d
             if (split)
                 kern = c->box_ortho ? (sweep_nt ? pair_sweep_kernel<1, 1, 0, 1> : pair_sweep_kernel<1, 0, 0, 1>)
                                     : (sweep_nt ? pair_sweep_kernel<0, 1, 0, 1> : pair_sweep_kernel<0, 0, 0, 1>);
-            if (c->opt_sweep_ablate == 1) kern = pair_sweep_kernel<1, 0, 1>;  // timing-only experiments (ortho boxes)
-            if (c->opt_sweep_ablate == 2) kern = pair_sweep_kernel<1, 0, 2>;
-            if (c->opt_sweep_ablate) half_plane = 0;
+            if (c->opt.sweep_ablate == 1) kern = pair_sweep_kernel<1, 0, 1>;  // timing-only experiments (ortho boxes)
+            if (c->opt.sweep_ablate == 2) kern = pair_sweep_kernel<1, 0, 2>;
+            if (c->opt.sweep_ablate) half_plane = 0;
             HIPCHK(launch_timed(c, timer_class, kern, g, b, 0, c->stream, (const double2 *)v.C, nt, v.ntld,
                                 (const double *)v.px, (const double *)v.py, (const double *)v.pz, mu_in, bx, v.Srow, v.Zcol,
-                                c->opt_sweep_alternate ? (c->sweep_parity++ & 1) : 0, half_plane));
+                                c->opt.sweep_alternate ? (c->sweep_parity++ & 1) : 0, half_plane));
         }
         {
             ScopedTimer t2(c, T_OTHER);
@@ -492,13 +492,13 @@ static int launch_sweep(mpmc_hip_ctx *c, SweepView &v, const DevBox &bx, const d
     }
     c->energy_nt = 0;
     // below ~2k polarizable atoms the triangle has too few 32x128-atom units to fill 256 CUs
-    if (c->opt_symmetric && (nvpad >= 2048 || c->opt_symmetric > 1)) {
+    if (c->opt.symmetric && (nvpad >= 2048 || c->opt.symmetric > 1)) {
         if (ensure_sym_scratch(v)) return -1;
         {
             ScopedTimer t(c, timer_class);  // the HBM-bound pass alone, so it can be held against rocprof
             const dim3 g(nvpad / kSymChunkAtoms, nvpad / kSymRowAtoms);
-            const int rev = (c->opt_sym_mode & 1) ? (c->sweep_parity++ & 1) : 0;
-            if (c->opt_sym_mode & 2)
+            const int rev = (c->opt.sym_mode & 1) ? (c->sweep_parity++ & 1) : 0;
+            if (c->opt.sym_mode & 2)
                 hipLaunchKernelGGL(symv_kernel<1>, g, dim3(64), 0, c->stream, v.A, lda, nvpad, mu_in, v.Srow, v.Zcol, rev,
                                    v.nv);
             else
@@ -520,7 +520,7 @@ static void (*chain_kernel_of(int ortho))(GsChain) { return ortho ? gs_chain_ker
 
 // Gauss-Seidel runs on the chain kernel (pair coefficients + cached block inverses) unless the A/B options say
 // otherwise; the older path walks the expanded matrix with two launches per block.
-static bool gs_uses_chain(const mpmc_hip_ctx *c) { return c->opt_pair_coef != 0 && c->opt_persistent_gs != 0; }
+static bool gs_uses_chain(const mpmc_hip_ctx *c) { return c->opt.pair_coef != 0 && c->opt.persistent_gs != 0; }
 
 // One exact Gauss-Seidel sweep in the view's order -- see kernels_gs_chain.h (default) / kernels_gs.h.
 struct GsFinishArgs {  // the end-of-sweep bookkeeping, for the chain kernel's tail (or gs_finish_kernel)
@@ -533,7 +533,7 @@ static int launch_gs_sweep(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, con
     if (finished) *finished = false;
     const int nvpad = v.nvpad, lda = 3 * nvpad;
     (void)a;
-    ++c->gs_sweeps_this_call;
+    ++c->call.gs_sweeps;
     if (gs_uses_chain(c) && v.C_valid) {
         // upper-triangle product with the old dipoles from the pair coefficients (fully parallel) ...
         const int nt = std::max(1, (v.nv + kCoefTile - 1) / kCoefTile);
@@ -541,11 +541,11 @@ static int launch_gs_sweep(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, con
         // (fold_upper: the chain's workgroups add up the row sums of their blocks themselves while they wait for their turn --
         //  no pair_upper_finish_kernel launch; the upper kernel then arms the hand-off buffer.  Only with the end-of-sweep
         //  bookkeeping folded into the chain as well: gs_finish_kernel reads y for the padding blocks too.)
-        const bool fold_upper = c->opt_gs_fold_upper && fin && c->opt_gs_fold_finish && !c->opt_gs_ablate;
+        const bool fold_upper = c->opt.gs_fold_upper && fin && c->opt.gs_fold_finish && !c->opt.gs_ablate;
         {
             ScopedTimer tu(c, T_OTHER);
             const dim3 g(nt * (nt + 1) / 2), b(64 * kCoefWaves);
-            const int rev = c->opt_sweep_alternate ? (c->sweep_parity++ & 1) : 0;
+            const int rev = c->opt.sweep_alternate ? (c->sweep_parity++ & 1) : 0;
             if (c->box_ortho)
                 hipLaunchKernelGGL(pair_upper_kernel<1>, g, b, 0, c->stream, v.C, nt, v.ntld, v.px, v.py, v.pz, mu_old, bx, v.Srow, rev,
                                    fold_upper ? nt : 0, v.mupub, v.gsflags, c->gs_qoff);
@@ -572,18 +572,18 @@ static int launch_gs_sweep(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, con
             gp.Lnb[k] = v.Lnb[k];
             gp.pub[k] = v.mupub + k * (size_t)c->gs_qoff;
         }
-        gp.nlag = v.nlag >= 2 ? v.nlag : c->opt_gs_lags;
+        gp.nlag = v.nlag >= 2 ? v.nlag : c->opt.gs_lags;
         gp.y = v.y;
         gp.mu_new = v.mupub;
         gp.flags = v.gsflags;
         gp.bx = bx;
-        gp.fault_block = (c->opt_gs_fault_sweep > 0 && c->gs_sweeps_this_call == c->opt_gs_fault_sweep) ? std::min(1, nt - 1) : -1;
+        gp.fault_block = (c->opt.gs_fault_sweep > 0 && c->call.gs_sweeps == c->opt.gs_fault_sweep) ? std::min(1, nt - 1) : -1;
         gp.stamps = nullptr;
         gp.Srow = fold_upper ? v.Srow : nullptr;
         gp.nt_upper = nt;
-        gp.ablate = c->opt_gs_ablate;
+        gp.ablate = c->opt.gs_ablate;
         memset(&gp.fin, 0, sizeof(gp.fin));
-        if (fin && c->opt_gs_fold_finish && !c->opt_gs_ablate) {
+        if (fin && c->opt.gs_fold_finish && !c->opt.gs_ablate) {
             gp.fin.on = 1;
             gp.fin.flags = v.pflags;
             gp.fin.mu_old = mu_old;
@@ -598,7 +598,7 @@ static int launch_gs_sweep(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, con
             gp.fin.errmax = c->d_errmax;
             if (finished) *finished = true;
         }
-        if (c->opt_gs_stamps > 0) {
+        if (c->opt.gs_stamps > 0) {
             const size_t need = (size_t)(c->max_npad / 64 + 1) * 16;
             if (c->d_stamps.size() < need) HIPCHK(c->d_stamps.alloc(need));
             HIPCHK(hipMemsetAsync(c->d_stamps, 0, (size_t)nt * 16 * sizeof(unsigned long long), c->stream));
@@ -606,9 +606,9 @@ static int launch_gs_sweep(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, con
         }
         {
             void (*kern)(GsChain) = chain_kernel_of(c->box_ortho ? 1 : 0);
-            if (c->build_join_pending) {  // the chain data of this call's move (built beside the launches in front of this one)
+            if (c->call.build_join_pending) {  // the chain data of this call's move (built beside the launches in front of this one)
                 HIPCHK(hipStreamWaitEvent(c->stream, c->ev_bjoin, 0));
-                c->build_join_pending = false;
+                c->call.build_join_pending = false;
             }
             // (main workgroups of all blocks + an auxiliary one per lag 2 .. nlag of the blocks t >= lag; roles by ticket)
             const int grid = gs_chain_ticket_base(nt, gp.nlag);
@@ -616,7 +616,7 @@ static int launch_gs_sweep(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, con
         }
         if (gp.stamps) {
             // diagnostic only: block until the sweep is done and print, per block, the stamps relative to the launch
-            --c->opt_gs_stamps;
+            --c->opt.gs_stamps;
             std::vector<unsigned long long> h((size_t)nt * 16);
             HIPCHK(hipStreamSynchronize(c->stream));
             HIPCHK(hipMemcpy(h.data(), c->d_stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -624,7 +624,7 @@ static int launch_gs_sweep(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, con
             for (int b = 0; b < nt; ++b) t0 = std::min(t0, h[(size_t)b * 16]);
             fprintf(stderr, "GS_STAMPS sweep %d (us since the first workgroup started; 0 start, 1 staged, 2/3 and 4/5 the last two far tiles, "
                             "6 far sums in LDS, 7 w_t done, 8 mu(t-1) in LDS, 9 P product summed, 10 published, 11 end)\n",
-                    c->gs_sweeps_this_call);
+                    c->call.gs_sweeps);
             for (int b = 0; b < nt; ++b) {
                 fprintf(stderr, "GS_STAMPS b%02d", b);
                 for (int k = 0; k < 12; ++k)
@@ -636,7 +636,7 @@ static int launch_gs_sweep(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, con
                 fprintf(stderr, "  clk %6.0f MHz\n", dt > 0 ? 100.0 * (double)(h[(size_t)b * 16 + 13] - h[(size_t)b * 16 + 12]) / dt : 0.0);
             }
         }
-        c->gs_used[&v == &c->view[1] ? 1 : 0] = true;  // its error word is checked at the end of energy()
+        c->call.gs_used[&v == &c->view[1] ? 1 : 0] = true;  // its error word is checked at the end of energy()
         return 0;
     }
     ScopedTimer t(c, T_SWEEP);
@@ -701,24 +701,24 @@ static int launch_resident(mpmc_hip_ctx *c, SweepView &v, const DevBox &bx, cons
         rs.w_old[k - 1] = w_old;
     }
     rs.bx = bx;
-    rs.fault = c->opt_res_fault;
-    c->opt_res_fault = 0;
+    rs.fault = c->opt.res_fault;
+    c->opt.res_fault = 0;
     rs.stamps = nullptr;
     const int nrole = rp.fold ? rp.ngroups : rp.nt + rp.ngroups;
     const size_t nstamp = (size_t)nrole * (kResMaxSweeps + 1) * 4;
-    if (c->opt_res_stamps > 0) {
+    if (c->opt.res_stamps > 0) {
         const size_t need = (size_t)768 * (kResMaxSweeps + 1) * 4;
         if (c->d_stamps.size() < need) HIPCHK(c->d_stamps.alloc(need));
         HIPCHK(hipMemsetAsync(c->d_stamps, 0, nstamp * sizeof(unsigned long long), c->stream));
         rs.stamps = c->d_stamps;
     }
-    if (c->opt_res_side && c->enqueue_side) c->enqueue_side();
+    if (c->opt.res_side && c->call.enqueue_side) c->call.enqueue_side();
     ResidentKernel kern = resident_kernel_of(c->box_ortho ? 1 : 0, rp.K, rp.fold);
     HIPCHK(launch_timed(c, T_SWEEP, kern, dim3(nrole), dim3(kResThreads), (size_t)rp.lds, c->stream, rs));
     if (rs.stamps) {
         // diagnostic only: per sweep, when the tile groups had their dipoles / finished multiplying / had published, and
         // when the finishers had their partial sums / had published (us since the first workgroup started; mean and max)
-        --c->opt_res_stamps;
+        --c->opt.res_stamps;
         std::vector<unsigned long long> h(nstamp);
         HIPCHK(hipStreamSynchronize(c->stream));
         HIPCHK(hipMemcpy(h.data(), c->d_stamps, nstamp * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -763,9 +763,9 @@ static int launch_resident(mpmc_hip_ctx *c, SweepView &v, const DevBox &bx, cons
                     mean[4], mx[4]);
         }
     }
-    if (c->enqueue_side) c->enqueue_side();
+    if (c->call.enqueue_side) c->call.enqueue_side();
     ++c->resident_calls;
-    c->gs_used[0] = true;  // the sticky error word travels with the result record (publish_result_kernel)
+    c->call.gs_used[0] = true;  // the sticky error word travels with the result record (publish_result_kernel)
     c->energy_part = v.energy_part;
     c->energy_nt = rp.nt;
     return 0;
@@ -774,12 +774,12 @@ static int launch_resident(mpmc_hip_ctx *c, SweepView &v, const DevBox &bx, cons
 static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, int *n_iter, int *iter_success) {
     const mpmc_hip_params &P = c->par;
     const int npad = c->npad, n = c->n;
-    const bool gs = P.polar_gs || P.polar_gs_ranked;
+    const bool gs = c->call.gs_mode;
     const bool want_rrms = P.polar_rrms || P.polar_precision > 0.0;
     *n_iter = 0;
     *iter_success = 0;
     c->energy_nt = 0;
-    c->gs_sweeps_this_call = 0;
+    c->call.gs_sweeps = 0;
     // ---- ranking metric (pairs.c:337-360), needed from the 2nd sweep on.
     // Speculative form: the ranked view (1) of the previous call is assumed to be still the right walk (a single-
     // molecule move changes the metric only when molecules come within 1.5 r_min of each other); its data are brought
@@ -788,11 +788,11 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
     const bool ranked = P.polar_gs_ranked && !P.polar_zodid;
     SweepView &W = c->view[1];
     const bool chain_mode = gs && gs_uses_chain(c);
-    const bool spec_rank = ranked && chain_mode && c->opt_spec_rank && c->opt_overlap && !c->force_host_rank &&
+    const bool spec_rank = ranked && chain_mode && c->opt.spec_rank && c->opt.overlap && !c->force_host_rank &&
                            P.polar_precision == 0.0 && P.polar_max_iter >= 2 && c->rank_used_valid && W.C_valid &&
                            W.ranked_call + 1 == c->energy_calls && W.nvpad == c->view[0].nvpad &&
                            W.nv == c->view[0].nv && (int)c->rank_saved.size() == n && !c->all_dirty;
-    c->call_spec_rank = spec_rank;
+    c->call.spec_rank = spec_rank;
     c->perm_ranked = spec_rank;  // mpmc_hip_download_ranking sorts the saved metric when asked (else: identity)
     // (Enqueued AFTER the first sweep's launches -- enqueue_rank() below: the host needs ~4 us per launch, and with these
     //  8-9 side-stream launches in front the main stream sat idle for ~35 us at the head of every step, waiting for its
@@ -801,7 +801,7 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
     // host's sort, and the event the main stream waits for at the view switch.
     bool rank_enqueued = false, rank_metric_enqueued = false;
     int rank_rc = 0;
-    const bool rank_side = ranked && (spec_rank || (c->opt_overlap && chain_mode));
+    const bool rank_side = ranked && (spec_rank || (c->opt.overlap && chain_mode));
     const hipStream_t rs = rank_side ? c->stream2 : c->stream;
     auto enqueue_rank_metric = [&]() {
         if (rank_metric_enqueued || !ranked) return;
@@ -848,13 +848,13 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
         } else {
             enqueue_rank_metric();  // (one stream: the metric's kernels in line, the host copies it at the view switch)
         }
-        c->rank_on_side = rank_side && !spec_rank;
+        c->call.rank_on_side = rank_side && !spec_rank;
         return 0;
         }();
     };
     // (only the speculative form waits: when the host has to sort the metric in the middle of the call, the sooner the
     //  rank kernels start the sooner it can)
-    if (!(c->opt_rank_late && spec_rank)) {
+    if (!(c->opt.rank_late && spec_rank)) {
         enqueue_rank();
         if (rank_rc) return -1;
     }
@@ -865,7 +865,7 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
         // Jacobi-type solves run on pair coefficients alone; the Gauss-Seidel kernels walk rows of the expanded
         // matrix, and take their upper-triangle product from the coefficients as well
         const bool chain = gs && gs_uses_chain(c);
-        if (setup_view(c, *V, a, bx, true, c->opt_pair_coef != 0, (gs && !chain) || !c->opt_pair_coef, chain)) return -1;
+        if (setup_view(c, *V, a, bx, true, c->opt.pair_coef != 0, (gs && !chain) || !c->opt.pair_coef, chain)) return -1;
     } else {
         const dim3 g((V->nvpad + 255) / 256), b(256);
         hipLaunchKernelGGL(gather_atoms_kernel, g, b, 0, c->stream, V->nv, V->nvpad, V->d_idx, a, V->px, V->py, V->pz,
@@ -875,7 +875,7 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
     // (rank_late = 2: the metric's four kernels go out here, behind the main stream's first launches -- the moved blocks'
     //  coefficient update and block inverse keep the device busy for ~25 us while the host enqueues them -- so that the
     //  heavy ranking kernels run beside the view set-up rather than beside the latency-bound chain of the first sweep)
-    if (ranked && spec_rank && c->opt_rank_late >= 2) enqueue_rank_metric();
+    if (ranked && spec_rank && c->opt.rank_late >= 2) enqueue_rank_metric();
 
     // ---- static field for every atom (thole_field.c:14-36)
     if (launch_field(c, a, bx)) return -1;
@@ -885,7 +885,7 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
     // a fixed-count Jacobi-type solve that fits the chip runs as ONE launch with its tiles in registers
     const ResidentPlan rp = resident_plan(c, *V);
     if (rp.ok && ensure_view_resident(c, *V)) return -1;
-    c->call_resident = rp.ok;
+    c->call.resident = rp.ok;
     {
         const double scale = (!P.polar_sor && !P.polar_esor) ? P.polar_gamma : 1.0;
         hipLaunchKernelGGL(init_view_kernel, dim3(V->nvpad / 64), dim3(64 * kFieldGroups), 0, c->stream, V->nv,
@@ -935,7 +935,7 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
                 if (launch_sweep<kSweepJacobi>(c, *V, bx, mu_in, mu_out, sp, T_SWEEP)) return -1;
                 // the device is busy now: feed the LJ/Ewald stream (its ~55 us of kernels only have to be done by the
                 // time the last sweep is)
-                if (c->enqueue_side && (iteration_counter == c->opt_side_after || P.polar_max_iter < c->opt_side_after)) c->enqueue_side();
+                if (c->call.enqueue_side && (iteration_counter == c->opt.side_after || P.polar_max_iter < c->opt.side_after)) c->call.enqueue_side();
             } else {
                 GsFinishArgs gfa;
                 gfa.w_new = w_new;
@@ -993,7 +993,7 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
                     // the walk of the previous call, already maintained on the side stream
                     hipStreamWaitEvent(c->stream, c->ev_rank, 0);
                 } else {
-                    if (c->rank_on_side) {
+                    if (c->call.rank_on_side) {
                         HIPCHK(hipEventSynchronize(c->ev_rank));           // the metric is on the host
                         hipStreamWaitEvent(c->stream, c->ev_rank, 0);      // and d_rank is complete for the main stream
                     } else {
@@ -1005,7 +1005,7 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
                     // tiles, block inverses, tensor tiles: ~100 us at 4096 atoms), which used to wait in the main stream's
                     // queue behind that sweep and then run alone.  (The side stream has nothing else queued yet: the LJ /
                     // Ewald kernels are fed at the end of the call.)
-                    const bool view_on_side = c->rank_on_side && chain_mode && c->opt_rank_view_side;
+                    const bool view_on_side = c->call.rank_on_side && chain_mode && c->opt.rank_view_side;
                     const hipStream_t ws = view_on_side ? c->stream2 : c->stream;
                     const double *rk = c->h_rank;
                     c->rank_saved.assign(rk, rk + n);  // for mpmc_hip_download_ranking (the full ranked_array is made there)
@@ -1042,7 +1042,7 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
                     // A single-molecule move rarely changes the ranked order: if the walk is the one of the previous
                     // call, the ranked view's data are still resident and only what the moved atoms touch is redone
                     // (the reference rebuilds everything; so did this engine: 118 us at 4096 atoms).
-                    const bool same_walk = (chain_mode ? W.C_valid : (W.A_valid && (W.C_valid || !c->opt_pair_coef))) &&
+                    const bool same_walk = (chain_mode ? W.C_valid : (W.A_valid && (W.C_valid || !c->opt.pair_coef))) &&
                                            W.ranked_call + 1 == c->energy_calls && W.nv == nv &&
                                            W.nvpad == V->nvpad && std::equal(c->h_perm.get(), c->h_perm + nv, W.h_idx.begin());
                     W.ranked_call = c->energy_calls;
@@ -1063,7 +1063,7 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
                         W.A_valid = false;
                         W.C_valid = false;
                     }
-                    if (setup_view(c, W, a, bx, same_walk, c->opt_pair_coef != 0, !chain_mode, chain_mode,
+                    if (setup_view(c, W, a, bx, same_walk, c->opt.pair_coef != 0, !chain_mode, chain_mode,
                                    view_on_side ? ws : (hipStream_t) nullptr))
                         return -1;
                     // what later speculative calls are checked against: the metric this walk was sorted from

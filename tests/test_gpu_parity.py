@@ -1187,3 +1187,43 @@ def test_16384_atoms_polarizable_invariances():
     assert rel(e3["polarization_energy"], e2["polarization_energy"]) < 1e-11
     eng.close()
     fresh.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# mpmc_hip_set_option: the accepted names and their defaults (the engine's option table, in its order)
+# ---------------------------------------------------------------------------------------------
+OPTION_DEFAULTS = [
+    ("pair_coefficients", 1), ("incremental_amatrix", 1), ("incremental_pairs", 1), ("overlap_streams", 1), ("side_after", 1),
+    ("symmetric_sweep", 1), ("sym_mode", 0), ("timing", 1), ("timing_interval", 32), ("persistent_gs", 1),
+    ("speculative_ranking", 1), ("fuse_tensor", 1), ("gs_lags", 3), ("gs_build_fork", 1), ("gs_side_waves", 0),
+    ("rank_view_side", 1), ("gs_fold_upper", 1), ("gs_fold_finish", 1), ("rank_late", 1), ("resident_jacobi", 1),
+    ("resident_fold", 16), ("resident_side", 0), ("sweep_alternate", 1), ("sweep_nt", -1), ("sweep_split", -1),
+    ("fuse_moves", 1), ("gs_fuse_moves", 1), ("fuse_field", 1), ("fuse_recip", 1), ("split_record", 1), ("side_moves", 1),
+    ("resident_stamps", 0), ("sweep_ablate", 0), ("resident_fault", 0), ("gs_stamps", 0), ("inv_stamps", 0), ("gs_ablate", 0),
+    ("gs_fault_sweep", 0), ("step_graph", 0),
+]
+
+
+def test_set_option_accepts_exactly_the_table_names():
+    import re
+
+    src = open(os.path.join(os.path.dirname(GOLD), os.pardir, "mpmc_amd", "csrc", "engine.hip")).read()
+    assert re.findall(r'^\s*\{"(\w+)", &EngineOptions::', src, re.M) == [n for n, _ in OPTION_DEFAULTS]
+    sysm, flags = synth.s_pol(320), dict(synth.FLAGS_POL_JACOBI)
+    want = run_engine(sysm, flags)
+    eng = engine.Engine(320)
+    try:
+        for name, default in OPTION_DEFAULTS:
+            eng.set_option(name, default)  # (raises unless the call returns 0)
+        with pytest.raises(engine.EngineError, match="unknown option 'no_such_option'"):
+            eng.set_option("no_such_option", 1)
+        for lags in (1, 5):
+            with pytest.raises(engine.EngineError, match=r"gs_lags must be 2 \.\. 4"):
+                eng.set_option("gs_lags", lags)
+        # every knob at its default is the fresh context: same bits
+        eng.load_system(sysm, flags)
+        got = eng.energy()
+        for k in ("energy", "rd_energy", "coulombic_energy", "polarization_energy"):
+            assert got[k] == want[k], (k, got[k], want[k])
+    finally:
+        eng.close()
