@@ -125,7 +125,8 @@ void mpmc_hip_destroy(mpmc_hip_ctx *ctx);
  *   "incremental_amatrix" (default 1): after mpmc_hip_update_atoms() rewrite only the entries (coefficients,
  *                          or block-rows/-columns of A) of pairs that involve a moved atom instead of rebuilding;
  *   "incremental_pairs"   (default 1): the 64x64-atom tile partial sums of the LJ/Ewald pair kernel and of the
- *                          static field persist between calls; only tiles of moved atoms' blocks are recomputed;
+ *                          static field (and, under disp_expansion, of the dense repulsion / dispersion tile kernel) persist between
+ *                          calls; only tiles of moved atoms' blocks are recomputed;
  *   "overlap_streams"     (default 1): run the LJ/Ewald kernels on a second HIP stream beside the
  *                          polarization chain;
  *   "side_after"          (default 1; at least 1): the LJ/Ewald stream is fed after this many sweeps have been enqueued;
@@ -229,6 +230,33 @@ int mpmc_hip_scale_box(mpmc_hip_ctx *ctx, const double basis[9], double pbc_cuto
 int mpmc_hip_upload(mpmc_hip_ctx *ctx, int n, const double *x, const double *y, const double *z,
                     const double *charge, const double *polarizability, const double *epsilon,
                     const double *sigma, const double *mass, const int *molecule, const uint8_t *frozen);
+
+/* disp_expansion, the PHAHST force-field family (reference src/energy/disp_expansion.c:40-103, mixing pairs.c:142-193):
+ * rd_energy = sum over ALL pairs that are neither on one molecule, nor frozen-frozen, nor null (one of the four epsilon /
+ * sigma values 0 AND all six c6 / c8 / c10 0) -- there is no cutoff in this sum -- of
+ *     315.7750382111558 exp(-b_ij (r - rho_ij)) - f6 c6_ij / r^6 - f8 c8_ij / r^8 - f10 c10_ij / r^10
+ * at the minimum-image distance r, plus the long-range correction under rd_lrc.  The per-atom epsilon of the upload is
+ * the exponent b (1/A), the per-atom sigma the range rho (A).  Field names are the reference's keywords:
+ *   disp_expansion           1 = this potential instead of Lennard-Jones; 0 = back to Lennard-Jones (arrays ignored);
+ *   damp_dispersion          f_n = Tang-Toennies damping 1 - exp(-x) sum_{k<=n} x^k / k!, x = b_ij r, exactly 0 unless
+ *                            > 1e-9; 0 = f_n = 1;
+ *   extrapolate_disp_coeffs  c10_ij = (49/40) c8_ij^2 / c6_ij (0 when c6_ij or c8_ij is 0) instead of the mixed c10;
+ *   schmidt_mixing           b_ij = (b_i + b_j) b_i b_j / (b_i^2 + b_j^2) instead of 2 b_i b_j / (b_i + b_j).
+ * rho_ij = (rho_i + rho_j) / 2; c6_ij = sqrt(c6_i c6_j) * 0.021958709 / 3.166811429e-6 (c8: 0.0061490647, c10:
+ * 0.0017219135).  There is no Feynman-Hibbs term in this potential (feynman_hibbs still acts on the Ewald real term). */
+typedef struct mpmc_hip_disp_params {
+    int disp_expansion;
+    int damp_dispersion;
+    int extrapolate_disp_coeffs;
+    int schmidt_mixing;
+} mpmc_hip_disp_params;
+
+/* c6 / c8 / c10: per atom, in upload order, in atomic units (as a PQR file carries them); n = the upload's atom count.
+ * Called after mpmc_hip_upload(); a later upload without it returns the context to Lennard-Jones.  update_atoms,
+ * scale_box, energy_begin / _end and several contexts work as before; in this mode insert_molecule / remove_molecule
+ * answer 1 (upload the whole configuration again). */
+int mpmc_hip_set_dispersion(mpmc_hip_ctx *ctx, const mpmc_hip_disp_params *p, int n, const double *c6, const double *c8,
+                            const double *c10);
 
 /* New coordinates for atoms [first, first+count): the delta after one MC move
  * (make_move perturbs one molecule, mc_moves.c:567). */

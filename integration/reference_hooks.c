@@ -33,7 +33,9 @@ int hook_do_command(system_t *system, char **token) {
 }
 
 /* src/io/check_input.c: the twin of the `cuda` guard (:325-341); energy_hip() repeats these checks on every
- * call and fails (never computes something else) when an option it does not implement is on */
+ * call and fails (never computes something else) when an option it does not implement is on.  `disp_expansion` is no
+ * longer among them (default and Schmidt mixing, with or without damp_dispersion / extrapolate_disp_coeffs); the other
+ * mixing rules and disp_expansion_mbvdw are refused there, each by name */
 int hook_check_system(system_t *system) {
     if (system->hip && system->polarization) {
         if (!system->polar_iterative) {

@@ -36,6 +36,7 @@
 
 #include "device_common.h"
 #include "kernels_pair.h"
+#include "kernels_disp.h"
 #include "kernels_polar.h"
 #include "kernels_gs.h"
 #include "kernels_gs_chain.h"
@@ -168,6 +169,8 @@ enum ResSlot {
     R_GS_ERR = 9,  // bit 0 / 1: the persistent Gauss-Seidel kernel of view 0 / 1 gave up on a hand-off
     R_RMIN = 10,
     R_RANKCHG = 11,  // speculative ranked call: 1 = the ranking metric differs from the one the ranked view was built for
+    R_DISP = 12,      // disp_expansion: the dense pair sum (kernels_disp.h) ...
+    R_DISP_LRC = 13,  // ... and its long-range correction; both read as zero outside that mode
     R_COUNT = 16
 };
 
@@ -297,6 +300,7 @@ struct CallState {
     bool moves_in_pair = false;   // ... or inside the pair kernel's launch (steps without polarization)
     bool side_carry = false;      // ... and the side stream's pair kernel carries the same move itself (side_moves):
     MoveList side_moves;          //     no fork event between the two streams in a steady-state polarizable step
+    MoveList disp_moves;          // the move the pair kernel's launch carried: the disp_expansion tile kernel behind it takes it too
     MoveList side_apply;          // a move the main stream applied with apply_moves_kernel: the side stream applies it
     bool side_applied = false;    //     too (a launch of its own, in front of its first kernel) instead of waiting for an event
     bool coef_job_valid = false;  // setup_view() left the coefficient update of this step for launch_field()
@@ -378,6 +382,15 @@ struct mpmc_hip_ctx {
     bool field_part_valid = false;  // same for d_fieldpart (real-space static field)
     int field_key = -1;             // mode / chunking the resident field partials were made with
     DevBuf<double> d_lrcpart;       // tile partials of the (cached) long-range correction
+    // ---- disp_expansion (PHAHST, mpmc_hip_set_dispersion): d_eps / d_sig then hold the exponent b and the range rho, the
+    // LJ kernels are handed d_zero in their place (every LJ pair and the LJ long-range correction give exactly 0)
+    bool disp_on = false;
+    DispParams disp_par = {0, 0, 0};
+    DevBuf<double> d_c6, d_c8, d_c10, d_zero;
+    DevBuf<double> d_disppart;      // [ntile*ntile] tile partials of the dense pair sum
+    bool disp_part_valid = false;   // ... of the configuration before the pending moves
+    DevBuf<double> d_displrcpart;   // [ntile*ntile] tile partials of its long-range correction
+    bool disp_lrc_valid = false;    // d_res[R_DISP_LRC] is that of the current parameters, cutoff and volume
     bool lrc_valid = false;
     double lrc_cached = 0.0;
     DevBuf<KVec> d_kvec;
@@ -467,8 +480,8 @@ static DevAtoms dev_atoms(const mpmc_hip_ctx *c) {
     a.z = c->d_z;
     a.q = c->d_q;
     a.alpha = c->d_alpha;
-    a.eps = c->d_eps;
-    a.sig = c->d_sig;
+    a.eps = c->disp_on ? c->d_zero : c->d_eps;
+    a.sig = c->disp_on ? c->d_zero : c->d_sig;
     a.molmass = c->d_molmass;
     a.mol = c->d_mol;
     a.flags = c->d_flags;
@@ -864,7 +877,7 @@ extern "C" int mpmc_hip_set_params(mpmc_hip_ctx *c, const mpmc_hip_params *p) {
         if (p->polar_gamma < 0.0) return fail("MPMC_HIP: invalid Pre-cond/SOR/ESOR gamma set");
     }
     if (p->polar_damp != c->par.polar_damp) c->all_dirty = true;
-    c->pair_part_valid = c->field_part_valid = false;
+    c->pair_part_valid = c->field_part_valid = c->disp_part_valid = false;
     ++c->config_rev;
     c->par = *p;
     c->have_params = true;
@@ -920,6 +933,7 @@ static int apply_box(mpmc_hip_ctx *c, const double basis[9], double pbc_cutoff) 
     c->kvecf_valid = false;
     c->kvec_valid = false;
     c->lrc_valid = false;
+    c->disp_lrc_valid = false;
     c->all_dirty = true;
     return 0;
 }
@@ -996,6 +1010,8 @@ extern "C" int mpmc_hip_upload(mpmc_hip_ctx *c, int n, const double *x, const do
     c->have_atoms = true;
     c->have_polar_result = false;
     c->lrc_valid = false;
+    c->disp_on = false;  // an upload brings Lennard-Jones parameters until set_dispersion() says otherwise
+    c->disp_part_valid = c->disp_lrc_valid = false;
     c->rank_saved.clear();
     c->perm_ranked = false;
     c->pending.n = 0;
@@ -1026,6 +1042,55 @@ extern "C" int mpmc_hip_upload(mpmc_hip_ctx *c, int n, const double *x, const do
     c->view[0].rebuild_from = c->view[1].rebuild_from = -1;
     ++c->config_rev;
     if (v0.nv > 0) HIPCHK(hipMemcpy(v0.d_idx, v0.h_idx.data(), v0.nv * sizeof(int), hipMemcpyHostToDevice));
+    return 0;
+}
+
+static int flush_moves(mpmc_hip_ctx *c);
+// disp_expansion (PHAHST): the resident epsilon / sigma become the exponent b and the range rho of the exponential
+// repulsion, and c6 / c8 / c10 (atomic units, upload order) arrive here.  Until the next upload the LJ kernels see zero
+// parameters and the dense kernels of kernels_disp.h form rd_energy.
+extern "C" int mpmc_hip_set_dispersion(mpmc_hip_ctx *c, const mpmc_hip_disp_params *p, int n, const double *c6,
+                                       const double *c8, const double *c10) {
+    if (!c || !p) return fail("MPMC_HIP: set_dispersion: null argument");
+    if (c->in_flight) return fail("MPMC_HIP: set_dispersion between energy_begin() and energy_end()");
+    if (!c->have_atoms) return fail("MPMC_HIP: set_dispersion: no configuration uploaded");
+    if (c->edited) return fail("MPMC_HIP: set_dispersion: molecules were inserted or removed since the upload");
+    if (n != c->n) return fail("MPMC_HIP: set_dispersion: %d coefficients for the %d atoms of the upload", n, c->n);
+    HIPCHK(hipSetDevice(c->device));
+    if (flush_moves(c)) return -1;  // keep the order of the caller's operations
+    c->disp_part_valid = c->disp_lrc_valid = false;
+    c->pair_part_valid = false;
+    c->lrc_valid = false;
+    c->all_dirty = true;
+    ++c->config_rev;
+    if (!p->disp_expansion) {
+        c->disp_on = false;
+        return 0;
+    }
+    if (!c6 || !c8 || !c10) return fail("MPMC_HIP: set_dispersion: null array");
+    const size_t nall = c->max_npad, ntile = nall / 64;
+    if (!c->d_c6) {
+        HIPCHK(c->d_c6.alloc(nall));
+        HIPCHK(c->d_c8.alloc(nall));
+        HIPCHK(c->d_c10.alloc(nall));
+        HIPCHK(c->d_zero.alloc(nall));
+        HIPCHK(c->d_disppart.alloc(ntile * ntile));
+        HIPCHK(c->d_displrcpart.alloc(ntile * ntile));
+        HIPCHK(hipMemsetAsync(c->d_zero, 0, nall * sizeof(double), c->stream));
+    }
+    std::vector<double> h6(nall, 0.0), h8(nall, 0.0), h10(nall, 0.0);  // pad atoms: zeros
+    std::copy(c6, c6 + n, h6.begin());
+    std::copy(c8, c8 + n, h8.begin());
+    std::copy(c10, c10 + n, h10.begin());
+    const size_t bd = nall * sizeof(double);
+    HIPCHK(hipMemcpyAsync(c->d_c6, h6.data(), bd, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_c8, h8.data(), bd, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_c10, h10.data(), bd, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->disp_par.damp = p->damp_dispersion != 0;
+    c->disp_par.extrapolate = p->extrapolate_disp_coeffs != 0;
+    c->disp_par.schmidt = p->schmidt_mixing != 0;
+    c->disp_on = true;
     return 0;
 }
 
@@ -1227,6 +1292,7 @@ static bool gs_order_mode(const mpmc_hip_ctx *c) {  // Gauss-Seidel on the chain
 static bool edits_supported(const mpmc_hip_ctx *c) {
     const mpmc_hip_params &P = c->par;
     if (!c->have_atoms || c->all_dirty || !c->opt.incremental || !c->opt.incremental_pairs || !c->opt.pair_coef) return false;
+    if (c->disp_on) return false;  // disp_expansion: no device-side insert / remove (the caller uploads again)
     // Gauss-Seidel: only with the chain kernel, whose view is rebuilt from the order the caller states afterwards
     if (!P.rd_only && P.polarization && (P.polar_gs || P.polar_gs_ranked) && !gs_order_mode(c)) return false;
     return true;
@@ -1349,7 +1415,7 @@ extern "C" int mpmc_hip_insert_molecule(mpmc_hip_ctx *c, int count, const double
         const int npad = round_up(c->n, 128);
         if (npad != c->npad) {  // the tile grids of the pair / field / LRC partials change shape
             c->npad = npad;
-            c->pair_part_valid = c->field_part_valid = false;
+            c->pair_part_valid = c->field_part_valid = c->disp_part_valid = false;
             c->lrc_valid = false;
         }
     }
@@ -1785,7 +1851,7 @@ __global__ __launch_bounds__(64) void publish_side_kernel(double *__restrict__ d
     if (threadIdx.x == 0) h_res2[n] = seq;
 }
 constexpr unsigned kSideSlots = (1u << R_RD_PAIR) | (1u << R_ES_REAL) | (1u << R_ES_INTRA) | (1u << 3) | (1u << R_LRC) |
-                                (1u << R_RECIP) | (1u << R_SELF);
+                                (1u << R_RECIP) | (1u << R_SELF) | (1u << R_DISP) | (1u << R_DISP_LRC);
 
 // LJ / real-space Ewald tile kernel (graph slot GS_PAIR).  Tile partials persist: after a single-molecule
 // move only the tiles of the moved atoms' blocks are recomputed.
@@ -1822,6 +1888,7 @@ static int launch_pair_kernel(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &
     }
     c->call.side_moves.n = 0;
     c->call.moves_in_pair = false;
+    c->call.disp_moves = mv;
     if (with_recip && c->opt.fuse_recip && c->call.plain_launches && c->nk > 0 &&
         (c->nk + 63) / 64 <= ntile) {
         // the reciprocal-space partials of the same blocks ride in a second z-slice of this launch (pair_recip_kernel) when
@@ -1867,6 +1934,38 @@ static int launch_recip_partial(mpmc_hip_ctx *c, const DevAtoms &a, hipStream_t 
     return 0;
 }
 
+// disp_expansion: the dense tile kernel behind the pair kernel (same stream, same dirty blocks, same move) and the fixed-order
+// sum of its tile partials; the long-range correction when the parameters, the cutoff or the volume changed.
+static int launch_disp(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipStream_t sb) {
+    const int ntile = c->npad / 64;
+    const DispAtoms da = {c->d_eps, c->d_sig, c->d_c6, c->d_c8, c->d_c10};
+    if (c->par.rd_lrc) {
+        if (!c->disp_lrc_valid) {
+            ScopedTimer t(c, T_OTHER, sb);
+            hipLaunchKernelGGL(disp_lrc_kernel, dim3(ntile, ntile), dim3(64 * kDispLrcWaves), 0, sb, a, da, bx, c->disp_par,
+                               c->d_displrcpart);
+            hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(kReduceThreads), 0, sb, c->d_displrcpart, ntile * ntile, 1,
+                               c->d_res + R_DISP_LRC);
+            HIPCHK(hipGetLastError());
+            c->disp_lrc_valid = true;
+        }
+    } else {
+        c->call.res_zero_mask |= 1u << R_DISP_LRC;
+        c->disp_lrc_valid = false;
+    }
+    DirtyBlocks sel = c->call.dirty_blocks;
+    if (!c->disp_part_valid) sel.n = 0;
+    if (c->disp_part_valid && c->dirty_atoms.empty()) return 0;  // nothing moved: d_res[R_DISP] is still that sum
+    ScopedTimer t(c, T_PAIR, sb);
+    hipLaunchKernelGGL(disp_tile_kernel, dim3(ntile, sel.n > 0 ? sel.n : ntile), dim3(64 * kDispWaves), 0, sb, a, da, bx,
+                       c->disp_par, sel, c->d_disppart, c->call.disp_moves);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(kReduceThreads), 0, sb, c->d_disppart, ntile * ntile, 1,
+                       c->d_res + R_DISP);
+    HIPCHK(hipGetLastError());
+    c->disp_part_valid = true;
+    return 0;
+}
+
 static int launch_publish(mpmc_hip_ctx *c) {
     const bool do_polar = c->call.do_polar;
     // (one wave unless the kernel also has the pair kernel's tile partials to add up)
@@ -1902,7 +2001,7 @@ static bool blocks_of(const std::vector<int> &atoms, DirtyBlocks &out) {
 static void collect_dirty_blocks(mpmc_hip_ctx *c) {
     DirtyBlocks &d = c->call.dirty_blocks;
     if (c->all_dirty || !c->opt.incremental_pairs || !blocks_of(c->dirty_atoms, d)) {
-        c->pair_part_valid = c->field_part_valid = false;
+        c->pair_part_valid = c->field_part_valid = c->disp_part_valid = false;
         memset(&d, 0, sizeof(d));
     }
     c->call.pair_part_valid_before = c->pair_part_valid;  // false whenever the dirty-block list cannot be trusted
@@ -2028,6 +2127,12 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
                 k.pair_rows_to_sum = ntile * ntile;  // summed by the publish kernel (same arithmetic, one launch less)
             }
         }
+        // ---- disp_expansion: exp repulsion + damped C6 / C8 / C10 over ALL pairs, and its long-range correction
+        if (c->disp_on) {
+            if (launch_disp(c, a, bx, sb)) return -1;
+        } else {
+            k.res_zero_mask |= (1u << R_DISP) | (1u << R_DISP_LRC);
+        }
 
         // ---- reciprocal + self (absent under Wolf summation, coulombic.c:27-28)
         if (!P.rd_only && !P.wolf) {
@@ -2109,7 +2214,7 @@ static bool graph_eligible(mpmc_hip_ctx *c) {
     const mpmc_hip_params &P = c->par;
     const SweepView &v = c->view[0];
     if (!c->opt.graph || is_timed_call(c) || !c->opt.incremental || !c->opt.incremental_pairs ||
-        !c->opt.pair_coef)
+        !c->opt.pair_coef || c->disp_on)
         return false;
     if (P.rd_only || !P.polarization || P.polar_zodid || P.polar_gs || P.polar_gs_ranked || P.polar_precision != 0.0 ||
         P.polar_max_iter <= 0)
@@ -2360,7 +2465,8 @@ extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
 
     double r[R_COUNT];
     for (int k = 0; k < R_COUNT; ++k) r[k] = (c->call.split && ((kSideSlots >> k) & 1u)) ? c->h_res2[k] : c->h_res[k];
-    const double rd = r[R_RD_PAIR] + r[R_LRC];
+    // (disp_expansion: the LJ kernels ran on zero parameters, both of their slots are exactly 0)
+    const double rd = c->disp_on ? (r[R_RD_PAIR] + r[R_LRC]) + (r[R_DISP] + r[R_DISP_LRC]) : r[R_RD_PAIR] + r[R_LRC];
     const double real = r[R_ES_REAL] - r[R_ES_INTRA];
     const bool ewald = !P.rd_only && !P.wolf;
     const double recip = ewald ? r[R_RECIP] * (4.0 * kPI / c->volume) : 0.0;  // coulombic.c:92

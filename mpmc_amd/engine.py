@@ -16,7 +16,7 @@ EXPORTS = [
     "mpmc_hip_last_error", "mpmc_hip_abi_version", "mpmc_hip_device_count", "mpmc_hip_create",
     "mpmc_hip_destroy", "mpmc_hip_set_option", "mpmc_hip_default_params", "mpmc_hip_set_params", "mpmc_hip_set_box",
     "mpmc_hip_scale_box",
-    "mpmc_hip_upload", "mpmc_hip_update_atoms", "mpmc_hip_insert_molecule", "mpmc_hip_remove_molecule",
+    "mpmc_hip_upload", "mpmc_hip_set_dispersion", "mpmc_hip_update_atoms", "mpmc_hip_insert_molecule", "mpmc_hip_remove_molecule",
     "mpmc_hip_slot_count", "mpmc_hip_set_sweep_order", "mpmc_hip_energy", "mpmc_hip_energy_begin", "mpmc_hip_energy_end",
     "mpmc_hip_download_dipoles",
     "mpmc_hip_download_amatrix", "mpmc_hip_download_ranking", "mpmc_hip_get_timings",
@@ -99,7 +99,18 @@ class Timings(C.Structure):
     ]
 
 
+class DispParams(C.Structure):
+    """mpmc_hip_disp_params: the PHAHST switches (reference keywords)."""
+    _fields_ = [
+        ("disp_expansion", C.c_int),
+        ("damp_dispersion", C.c_int),
+        ("extrapolate_disp_coeffs", C.c_int),
+        ("schmidt_mixing", C.c_int),
+    ]
+
+
 PARAM_NAMES = [f[0] for f in Params._fields_]
+DISP_NAMES = [f[0] for f in DispParams._fields_]
 
 _lib = None
 
@@ -129,6 +140,7 @@ def load():
     lib.mpmc_hip_set_box.argtypes = [vp, dp, C.c_double]
     lib.mpmc_hip_scale_box.argtypes = [vp, dp, C.c_double, C.c_int, vp]
     lib.mpmc_hip_upload.argtypes = [vp, C.c_int] + [vp] * 10
+    lib.mpmc_hip_set_dispersion.argtypes = [vp, C.POINTER(DispParams), C.c_int, vp, vp, vp]
     lib.mpmc_hip_update_atoms.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     lib.mpmc_hip_insert_molecule.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
     lib.mpmc_hip_remove_molecule.argtypes = [vp, C.c_int, C.c_int]
@@ -170,6 +182,8 @@ def make_params(**kw):
     for k, v in kw.items():
         if k == "pbc_cutoff":
             continue  # a box property at this boundary (set_box)
+        if k in DISP_NAMES:
+            continue  # mpmc_hip_set_dispersion's record (Engine.load_system)
         if k not in PARAM_NAMES:
             raise KeyError(k)
         setattr(p, k, v)
@@ -219,7 +233,8 @@ class Engine:
         return rc == 0
 
     def upload(self, system):
-        """system: dict with pos[n,3], charge, alpha, epsilon, sigma, mass, molecule, frozen."""
+        """system: dict with pos[n,3], charge, alpha, epsilon, sigma, mass, molecule, frozen (and, for set_dispersion(),
+        optional c6, c8, c10)."""
         pos = np.ascontiguousarray(system["pos"], dtype=np.float64)
         n = pos.shape[0]
         cols = [np.ascontiguousarray(pos[:, k]) for k in range(3)]
@@ -230,11 +245,25 @@ class Engine:
         _chk(self.lib.mpmc_hip_upload(self.ctx, n, *[a.ctypes.data for a in arrs], mol.ctypes.data, frz.ctypes.data))
         self.n = n
 
+    def set_dispersion(self, system, **flags):
+        """PHAHST (mpmc_hip_set_dispersion), after upload(): the four switches and the per-atom c6 / c8 / c10 of
+        `system` (atomic units; a missing array reads as zeros)."""
+        p = DispParams(**{k: int(flags.get(k, 0)) for k in DISP_NAMES})
+        n = self.n
+        arrs = [np.ascontiguousarray(system.get(k, np.zeros(n)), dtype=np.float64) for k in ("c6", "c8", "c10")]
+        for a in arrs:
+            if a.shape != (n,):
+                raise ValueError("c6 / c8 / c10 must have one entry per uploaded atom")
+        _chk(self.lib.mpmc_hip_set_dispersion(self.ctx, C.byref(p), n, *[a.ctypes.data for a in arrs]))
+
     def load_system(self, system, params):
-        """Convenience: params (incl. optional pbc_cutoff) + box + atoms."""
+        """Convenience: params (incl. optional pbc_cutoff) + box + atoms (+ the dispersion record when the flags carry
+        disp_expansion)."""
         self.set_params(**params)
         self.set_box(system["basis"], params.get("pbc_cutoff", 0.0))
         self.upload(system)
+        if params.get("disp_expansion"):
+            self.set_dispersion(system, **{k: params[k] for k in DISP_NAMES if k in params})
 
     def update_atoms(self, first, pos):
         pos = np.ascontiguousarray(pos, dtype=np.float64)

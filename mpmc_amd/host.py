@@ -71,6 +71,14 @@ def load():
     lib.host_force_volume_move.restype = None
     lib.host_init_chain_no_energy.argtypes = [vp]
     lib.host_init_chain_no_energy.restype = None
+    lib.host_get_disp_flags.argtypes = [vp, vp]
+    lib.host_get_disp_flags.restype = None
+    lib.host_get_dispersion.argtypes = [vp, vp, vp, vp]
+    lib.host_get_dispersion.restype = None
+    lib.host_set_dispersion.argtypes = [vp, vp, vp, vp]
+    lib.host_set_dispersion.restype = None
+    lib.host_unsupported.argtypes = [vp]
+    lib.host_unsupported.restype = C.c_char_p
     lib.volume_change.argtypes = [vp]
     lib.volume_change.restype = None
     lib.revert_volume_change.argtypes = [vp]
@@ -82,7 +90,8 @@ def load():
 def config_text(flags, extra=None):
     """flags in C-ABI / oracle naming -> the reference's keyword lines."""
     onoff = {"rd_only", "rd_lrc", "feynman_hibbs", "polarization", "polar_gs", "polar_gs_ranked", "polar_sor",
-             "polar_esor", "polar_palmo", "polar_rrms", "polar_zodid", "polar_wolf", "polar_ewald", "wolf"}
+             "polar_esor", "polar_palmo", "polar_rrms", "polar_zodid", "polar_wolf", "polar_ewald", "wolf",
+             "disp_expansion", "damp_dispersion", "extrapolate_disp_coeffs", "schmidt_mixing"}
     lines = []
     for k, v in flags.items():
         if k in onoff:
@@ -131,6 +140,9 @@ class HostSystem:
         arrs += [np.ascontiguousarray(system[k], dtype=np.int32) for k in ("molecule", "frozen")]
         arrs += [np.ascontiguousarray(system["basis"], dtype=np.float64).reshape(9)]
         self.ptr = C.c_void_p(self.lib.system_from_arrays(n, *[a.ctypes.data for a in arrs]))
+        if "c6" in system:  # PHAHST: per-atom dispersion coefficients (atomic units)
+            c = [np.ascontiguousarray(system.get(k, np.zeros(n)), dtype=np.float64) for k in ("c6", "c8", "c10")]
+            self.lib.host_set_dispersion(self.ptr, *[a.ctypes.data for a in c])
         extra = dict({"move_factor": move_factor, "rot_factor": rot_factor}, **(extra or {}))
         if self.lib.host_apply_config(self.ptr, config_text(flags, extra).encode()) != 0:
             raise ValueError("host layer rejected the configuration")

@@ -199,6 +199,39 @@ void host_get_system(system_t *system, double *pos, double *charge, double *alph
 }
 void host_set_ensemble(system_t *system, int ensemble) { system->ensemble = ensemble; }
 
+/* ---- disp_expansion (PHAHST) ---------------------------------------------------------------------------------- */
+/* what the readers left: the four keywords the engine takes and the four it refuses, and the per-atom coefficients */
+void host_get_disp_flags(system_t *system, int out[8]) {
+    out[0] = system->disp_expansion;
+    out[1] = system->damp_dispersion;
+    out[2] = system->extrapolate_disp_coeffs;
+    out[3] = system->schmidt_mixing;
+    out[4] = system->disp_expansion_mbvdw;
+    out[5] = system->gilbert_smith_mixing;
+    out[6] = system->bohm_ahlrichs_mixing;
+    out[7] = system->wilson_popelier_mixing;
+}
+void host_get_dispersion(system_t *system, double *c6, double *c8, double *c10) {
+    int i = 0;
+    for (molecule_t *m = system->molecules; m; m = m->next)
+        for (atom_t *a = m->atoms; a; a = a->next, i++) {
+            c6[i] = a->c6;
+            c8[i] = a->c8;
+            c10[i] = a->c10;
+        }
+}
+void host_set_dispersion(system_t *system, const double *c6, const double *c8, const double *c10) {
+    int i = 0;
+    for (molecule_t *m = system->molecules; m; m = m->next)
+        for (atom_t *a = m->atoms; a; a = a->next, i++) {
+            a->c6 = c6[i];
+            a->c8 = c8[i];
+            a->c10 = c10[i];
+        }
+}
+/* the reason energy() would refuse this system, or NULL */
+const char *host_unsupported(system_t *system) { return energy_hip_unsupported(system); }
+
 /* ---- npt ---------------------------------------------------------------------------------------------------- */
 void host_get_basis(system_t *system, double basis[9]) {
     for (int p = 0; p < 3; p++)

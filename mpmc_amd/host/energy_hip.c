@@ -54,6 +54,8 @@ typedef struct shim_state {
      * or removed): coordinates as last sent, and the parameters that tell species apart */
     int cap;
     double *x, *y, *z, *q, *alpha, *eps, *sig, *mass;
+    double *c6, *c8, *c10; /* disp_expansion: sent with every full upload (mpmc_hip_set_dispersion) */
+    mpmc_hip_disp_params disp; /* as last sent */
     /* the resident molecules in LIST order */
     resident_t *res, *res2;
     int nres, res_cap;
@@ -91,7 +93,9 @@ static shim_state *state_of(system_t *system, int create) {
 
 static void free_image(shim_state *st) {
     free(st->x); free(st->y); free(st->z); free(st->q); free(st->alpha); free(st->eps); free(st->sig); free(st->mass);
+    free(st->c6); free(st->c8); free(st->c10);
     st->x = st->y = st->z = st->q = st->alpha = st->eps = st->sig = st->mass = NULL;
+    st->c6 = st->c8 = st->c10 = NULL;
     st->cap = 0;
 }
 
@@ -208,13 +212,25 @@ static void fill_params(const system_t *s, mpmc_hip_params *p) {
     p->wolf = s->wolf;
 }
 
+static void fill_disp_params(const system_t *s, mpmc_hip_disp_params *d) {
+    memset(d, 0, sizeof(*d));
+    d->disp_expansion = s->disp_expansion;
+    d->damp_dispersion = s->damp_dispersion;
+    d->extrapolate_disp_coeffs = s->extrapolate_disp_coeffs;
+    d->schmidt_mixing = s->schmidt_mixing;
+}
+
 /* What the engine does not compute must not be asked of it silently (the twin of the `cuda on` guard,
  * src/io/check_input.c:325-341, extended to the whole of energy()). */
 static const char *unsupported(const system_t *s) {
 #ifndef MPMC_SHIM_HOST_MIRROR
-    if (s->sg || s->dreiding || s->lj_buffered_14_7 || s->disp_expansion || s->rd_anharmonic || s->cdvdw_exp_repulsion ||
+    if (s->sg || s->dreiding || s->lj_buffered_14_7 || s->rd_anharmonic || s->cdvdw_exp_repulsion ||
         s->axilrod_teller || s->gwp || s->spectre)
-        return "only Lennard-Jones repulsion / dispersion with point charges is on the device";
+        return "only Lennard-Jones or disp_expansion repulsion / dispersion with point charges is on the device";
+    /* pairs.c:85-141: these mixing branches come before the disp_expansion one (sg, cdvdw_sig_repulsion, polarvdw and
+     * cdvdw_exp_repulsion are refused above and below) */
+    if (s->disp_expansion && (s->waldmanhagler || s->halgren_mixing || s->cdvdw_9th_repulsion))
+        return "disp_expansion with waldmanhagler / halgren_mixing / cdvdw_9th_repulsion is not on the device";
     if (s->polarvdw || s->cdvdw_sig_repulsion) return "coupled-dipole van der Waals is not on the device";
     if (s->rd_crystal) return "rd_crystal is not on the device";
     if (s->cavity_autoreject_absolute) return "cavity_autoreject_absolute needs the pair list";
@@ -222,11 +238,15 @@ static const char *unsupported(const system_t *s) {
     if (s->polarization && s->damp_type != DAMPING_EXPONENTIAL) return "exponential Thole damping only";
     if (s->polarization && (s->polar_ewald_full || s->polar_wolf_full)) return "polar_ewald_full / polar_wolf_full are not on the device";
     if (s->ensemble == ENSEMBLE_NVE) return "ensemble nve is not supported";
-#else
-    (void)s;
 #endif
+    /* disp_expansion: the default and the Schmidt mixing of the exponent are on the device; the rest is refused by name */
+    if (s->disp_expansion_mbvdw) return "disp_expansion_mbvdw (many-body van der Waals) is not on the device";
+    if (s->disp_expansion && s->gilbert_smith_mixing) return "gilbert_smith_mixing is not on the device";
+    if (s->disp_expansion && s->bohm_ahlrichs_mixing) return "bohm_ahlrichs_mixing is not on the device";
+    if (s->disp_expansion && s->wilson_popelier_mixing) return "wilson_popelier_mixing is not on the device";
     return NULL;
 }
+const char *energy_hip_unsupported(const system_t *system) { return unsupported(system); }
 
 static int hip_fail(const char *what) {
     char buf[2 * MAXLINE];
@@ -257,7 +277,9 @@ static int image_reserve(shim_state *st, int cap) {
     const size_t b = (size_t)cap * sizeof(double);
     st->x = malloc(b); st->y = malloc(b); st->z = malloc(b); st->q = malloc(b); st->alpha = malloc(b);
     st->eps = malloc(b); st->sig = malloc(b); st->mass = malloc(b);
-    if (!(st->x && st->y && st->z && st->q && st->alpha && st->eps && st->sig && st->mass)) return -1;
+    st->c6 = malloc(b); st->c8 = malloc(b); st->c10 = malloc(b);
+    if (!(st->x && st->y && st->z && st->q && st->alpha && st->eps && st->sig && st->mass && st->c6 && st->c8 && st->c10))
+        return -1;
     st->cap = cap;
     return 0;
 }
@@ -318,6 +340,7 @@ static int full_upload(shim_state *st, system_t *system) {
             st->x[i] = a->pos[0]; st->y[i] = a->pos[1]; st->z[i] = a->pos[2];
             st->q[i] = a->charge; st->alpha[i] = a->polarizability; st->eps[i] = a->epsilon; st->sig[i] = a->sigma;
             st->mass[i] = a->mass;
+            st->c6[i] = a->c6; st->c8[i] = a->c8; st->c10[i] = a->c10;
             mol[i] = mi; /* list position: distinct per molecule even if PQR ids repeat */
             fz[i] = (uint8_t)(a->frozen != 0);
         }
@@ -333,6 +356,10 @@ static int full_upload(shim_state *st, system_t *system) {
     if (!rc) rc = mpmc_hip_upload(st->ctx, n, st->x, st->y, st->z, st->q, st->alpha, st->eps, st->sig, st->mass, mol, fz);
     free(mol); free(fz);
     if (rc) return hip_fail("upload");
+    fill_disp_params(system, &st->disp);
+    /* (an upload leaves the context on Lennard-Jones: nothing to say unless the PHAHST potential is asked for) */
+    if (st->disp.disp_expansion && mpmc_hip_set_dispersion(st->ctx, &st->disp, n, st->c6, st->c8, st->c10))
+        return hip_fail("set_dispersion");
     st->uploaded = 1;
     st->in_sync = 1;
     st->nnotes = 0;
@@ -425,7 +452,8 @@ static int same_species(const shim_state *st, const molecule_t *m, const residen
     for (const atom_t *a = m->atoms; a; a = a->next, k++) {
         if (k == r->natoms) return 0;
         if (a->charge != st->q[s + k] || a->polarizability != st->alpha[s + k] || a->epsilon != st->eps[s + k] ||
-            a->sigma != st->sig[s + k] || a->mass != st->mass[s + k])
+            a->sigma != st->sig[s + k] || a->mass != st->mass[s + k] || a->c6 != st->c6[s + k] || a->c8 != st->c8[s + k] ||
+            a->c10 != st->c10[s + k])
             return 0;
     }
     return k == r->natoms;
@@ -603,6 +631,9 @@ int energy_hip_begin(system_t *system) {
         mpmc_hip_params now;
         fill_params(system, &now); /* simulated annealing moves the temperature, surface fits the charges ... */
         if (memcmp(&now, &st->params, sizeof(now))) need_upload = 1;
+        mpmc_hip_disp_params dnow;
+        fill_disp_params(system, &dnow);
+        if (memcmp(&dnow, &st->disp, sizeof(dnow))) need_upload = 1;
     }
     if (!need_upload && scale_box) {
         const int rc = apply_volume_notes(st, system);

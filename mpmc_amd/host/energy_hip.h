@@ -34,6 +34,8 @@ double energy_hip_end(system_t *system);
  * right after energy() and stops; only a call that succeeded and produced a non-finite energy is a bad contact
  * (src/mc/mc.c:315-318). */
 int energy_hip_failed(system_t *system);
+/* NULL when the device computes everything this system asks of energy(), else the reason it is refused */
+const char *energy_hip_unsupported(const system_t *system);
 
 /* Optional notes from mc_moves.c (worth one list walk per step): molecule `now` sits in the list where `was`
  * sat when the device last saw it -- make_move()'s displacement: (altered, altered); restore()'s relinked

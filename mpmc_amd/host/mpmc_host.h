@@ -36,6 +36,7 @@ typedef struct _atom {
     char atomtype[MAXLINE];
     int frozen;
     double mass, charge, polarizability, epsilon, sigma;
+    double c6, c8, c10; /* disp_expansion: dispersion coefficients in atomic units (structs.h:54, read_pqr.c:255-257) */
     double pos[3], wrapped_pos[3];
     double ef_static[3], ef_static_self[3], ef_induced[3], ef_induced_change[3];
     double mu[3], old_mu[3], new_mu[3];
@@ -107,6 +108,10 @@ typedef struct _system {
     int polarization, polar_iterative, polar_ewald, polar_zodid, polar_palmo, polar_gs, polar_gs_ranked, polar_sor,
         polar_esor, polar_max_iter, polar_wolf, polar_rrms, damp_type;
     double polar_gamma, polar_damp, polar_precision, polar_wolf_alpha;
+    /* the PHAHST family (structs.h:420-421): exp repulsion + C6 / C8 / C10 dispersion instead of Lennard-Jones; the last
+     * four are read so that energy_hip.c can refuse them by name */
+    int disp_expansion, extrapolate_disp_coeffs, damp_dispersion, schmidt_mixing;
+    int disp_expansion_mbvdw, gilbert_smith_mixing, bohm_ahlrichs_mixing, wilson_popelier_mixing;
     int iter_success; /* the reference's convergence-FAILURE flag */
     int natoms;
     char job_name[MAXLINE], pqr_input[MAXLINE], energy_output[MAXLINE], pqr_output[MAXLINE];

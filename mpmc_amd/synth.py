@@ -1,4 +1,4 @@
-"""Synthetic periodic boxes: S-LJ(N), S-ES(N), S-POL(N).
+"""Synthetic periodic boxes: S-LJ(N), S-ES(N), S-POL(N), and S-PHAHST(N) for disp_expansion.
 
 Deterministic (seeded) inputs of the shapes BASELINE.json names, used by bench.py and the
 parity tests.  Units as the reference reads them: Angstrom, K, charges already multiplied by
@@ -103,11 +103,59 @@ def s_pol(n, seed=None, spacing=3.6):
     return _finish(np.array(pos), q, alpha, eps, sig, mass, mol, np.zeros(n), L)
 
 
+# A three-site PHAHST sorbate in the style of the reference group's H2 models (exponent b in 1/A in the epsilon column,
+# range rho in A in the sigma column, C6 / C8 / C10 in atomic units): a centre with repulsion, dispersion and a charge, a
+# dispersion-only site (epsilon = sigma = 0) and a charge-only site.  Round numbers of the right magnitude, not a
+# published parameter set.
+# (site, offset along the molecular axis, mass, charge/e, alpha, b, rho, c6, c8, c10)
+PHAHST_SITES = [
+    ("H2G", 0.0, 2.016, -0.7464, 0.69380, 3.5, 2.6, 9.0, 160.0, 4000.0),
+    ("H2N", 0.363, 0.0, 0.0, 0.0, 0.0, 0.0, 1.5, 20.0, 300.0),
+    ("H2E", -0.371, 0.0, 0.7464, 0.00044, 0.0, 0.0, 0.0, 0.0, 0.0),
+]
+# a frozen framework atom: repulsion, dispersion, charge and polarizability
+PHAHST_FRAMEWORK = (12.011, 0.1, 1.2, 3.2, 3.1, 25.0, 600.0, 18000.0)
+
+
+def s_phahst(n, seed=None, spacing=3.6):
+    """s_pol's geometry for the PHAHST potential: the first third of the lattice sites (rounded down) holds single frozen
+    framework atoms (charges alternate in sign), the rest of the atoms are three-site sorbate molecules, plus single movable
+    centre sites so that the atom count is exactly N.  Carries c6, c8, c10 (atomic units) next to the usual arrays."""
+    rng = np.random.default_rng(4234 + n if seed is None else seed)
+    nfr = n // 3
+    nmol = (n - nfr) // 3
+    extra = n - nfr - 3 * nmol
+    com, L = _lattice(nfr + nmol + extra, spacing, 0.3, rng)
+    com = com[rng.permutation(len(com))]  # framework and sorbate interleaved in space
+    ax = _random_axes(nmol, rng)
+    rows, pos = [], []
+    ms, qq, al, b, rho, c6, c8, c10 = PHAHST_FRAMEWORK
+    for f in range(nfr):
+        pos.append(com[f])
+        rows.append((qq if f % 2 == 0 else -qq, al, b, rho, ms, f + 1, 1, c6, c8, c10))
+    if nfr % 2:  # keep the cell neutral
+        rows[-1] = (0.0,) + rows[-1][1:]
+    for m in range(nmol):
+        for (_, off, ms, qq, al, b, rho, c6, c8, c10) in PHAHST_SITES:
+            pos.append(com[nfr + m] + off * ax[m])
+            rows.append((qq, al, b, rho, ms, nfr + m + 1, 0, c6, c8, c10))
+    _, _, ms, _, al, b, rho, c6, c8, c10 = PHAHST_SITES[0]
+    for e in range(extra):
+        pos.append(com[nfr + nmol + e])
+        rows.append((0.0, al, b, rho, ms, nfr + nmol + e + 1, 0, c6, c8, c10))
+    r = np.array(rows, dtype=np.float64)
+    out = _finish(np.array(pos), r[:, 0], r[:, 1], r[:, 2], r[:, 3], r[:, 4], r[:, 5], r[:, 6], L)
+    out.update(c6=r[:, 7].copy(), c8=r[:, 8].copy(), c10=r[:, 9].copy())
+    return out
+
+
 # flag sets (reference config keywords) used with the synthetic polarizable boxes
 FLAGS_POL_JACOBI = dict(temperature=77.0, polarization=1, polar_damp=2.1304, polar_max_iter=10,
                         feynman_hibbs=1, feynman_hibbs_order=4)
 FLAGS_POL_PRODUCTION = dict(temperature=77.0, polarization=1, polar_damp=2.1304, polar_wolf=1,
                             polar_wolf_alpha=0.13, polar_gs_ranked=1, polar_palmo=1, polar_gamma=1.03,
                             polar_max_iter=4)
+# the polarizable set with the PHAHST repulsion / dispersion (Tang-Toennies damping, C10 extrapolated, default mixing)
+FLAGS_PHAHST = dict(FLAGS_POL_JACOBI, disp_expansion=1, damp_dispersion=1, extrapolate_disp_coeffs=1, schmidt_mixing=0)
 FLAGS_LJ = dict(temperature=100.0, rd_only=1)
 FLAGS_ES = dict(temperature=100.0)
