@@ -258,6 +258,25 @@ typedef struct mpmc_hip_disp_params {
 int mpmc_hip_set_dispersion(mpmc_hip_ctx *ctx, const mpmc_hip_disp_params *p, int n, const double *c6, const double *c8,
                             const double *c10);
 
+/* axilrod_teller, the triple-dipole three-body dispersion term (reference src/energy/axilrod_teller.cpp:85-179; added to
+ * potential_energy at energy.c:194 and reported as observables->three_body_energy).  The sum runs over every unordered
+ * triple of distinct atoms that are not all three on one molecule -- frozen atoms included, no cutoff -- with three
+ * independent minimum images d_ij, d_ik, d_jk (which need not close a triangle in a periodic box; kept as the reference has it):
+ *     E_ijk = c9_ijk (1 - 3 (e_ij.e_ik)(e_ij.e_jk)(e_ik.e_jk)) / (r_ij r_ik r_jk)^3,        e = d / r,
+ *     c9_ijk = a_i a_j a_k * 3 / (a_i^3 / c9_i + a_j^3 / c9_j + a_k^3 / c9_k) * 0.0032539449 / 3.166811429e-6,
+ * a = polarizability * 6.7483345; exactly 0 when one of the three polarizabilities or coefficients is 0.
+ * c9: per atom, in upload order, in atomic units, n = the upload's atom count.  It is the EFFECTIVE coefficient: under the
+ * reference's midzuno_kihara_approx the caller passes 3/4 * polarizability * 6.7483345 * c6 in its place.  The
+ * polarizabilities are the upload's; a negative one is an error.  Called after mpmc_hip_upload(), independent of
+ * mpmc_hip_set_dispersion(); enable = 0 (c9 ignored), or a later upload without this call, switches the term off.
+ * While it is on, mpmc_hip_result.energy includes the term (a non-finite term sets status bit 0), insert_molecule /
+ * remove_molecule answer 1 (upload the whole configuration again), and update_atoms, scale_box, energy_begin / _end
+ * and several contexts work as before: after a move only the block triples that hold a moved block are summed again,
+ * with the bits of a from-scratch evaluation. */
+int mpmc_hip_set_axilrod_teller(mpmc_hip_ctx *ctx, int enable, int n, const double *c9);
+/* observables->three_body_energy of the last completed energy() / energy_end(); 0 while the term is off. */
+int mpmc_hip_get_three_body_energy(mpmc_hip_ctx *ctx, double *out);
+
 /* New coordinates for atoms [first, first+count): the delta after one MC move
  * (make_move perturbs one molecule, mc_moves.c:567). */
 int mpmc_hip_update_atoms(mpmc_hip_ctx *ctx, int first, int count, const double *x, const double *y,

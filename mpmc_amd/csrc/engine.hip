@@ -37,6 +37,7 @@
 #include "device_common.h"
 #include "kernels_pair.h"
 #include "kernels_disp.h"
+#include "kernels_at.h"
 #include "kernels_polar.h"
 #include "kernels_gs.h"
 #include "kernels_gs_chain.h"
@@ -171,6 +172,7 @@ enum ResSlot {
     R_RANKCHG = 11,  // speculative ranked call: 1 = the ranking metric differs from the one the ranked view was built for
     R_DISP = 12,      // disp_expansion: the dense pair sum (kernels_disp.h) ...
     R_DISP_LRC = 13,  // ... and its long-range correction; both read as zero outside that mode
+    R_AT = 14,        // axilrod_teller: the triple-dipole sum (kernels_at.h); reads as zero outside that mode
     R_COUNT = 16
 };
 
@@ -391,6 +393,12 @@ struct mpmc_hip_ctx {
     bool disp_part_valid = false;   // ... of the configuration before the pending moves
     DevBuf<double> d_displrcpart;   // [ntile*ntile] tile partials of its long-range correction
     bool disp_lrc_valid = false;    // d_res[R_DISP_LRC] is that of the current parameters, cutoff and volume
+    // ---- axilrod_teller (mpmc_hip_set_axilrod_teller): the triple-dipole term, kernels_at.h
+    bool at_on = false;
+    DevBuf<double> d_at_a, d_at_g;  // per atom: alpha * 6.7483345 and 1 / (c9 / a^3)
+    DevBuf<double> d_atpart;        // [at_unit_count(ntile)][kAtSplit] block-triple partials
+    bool at_part_valid = false;     // ... of the configuration (and box) before the pending moves
+    double three_body = 0.0;        // the term of the last completed energy_end() (0 outside the mode)
     bool lrc_valid = false;
     double lrc_cached = 0.0;
     DevBuf<KVec> d_kvec;
@@ -1012,6 +1020,8 @@ extern "C" int mpmc_hip_upload(mpmc_hip_ctx *c, int n, const double *x, const do
     c->lrc_valid = false;
     c->disp_on = false;  // an upload brings Lennard-Jones parameters until set_dispersion() says otherwise
     c->disp_part_valid = c->disp_lrc_valid = false;
+    c->at_on = false;  // ... and no three-body term until set_axilrod_teller() says otherwise
+    c->at_part_valid = false;
     c->rank_saved.clear();
     c->perm_ranked = false;
     c->pending.n = 0;
@@ -1091,6 +1101,58 @@ extern "C" int mpmc_hip_set_dispersion(mpmc_hip_ctx *c, const mpmc_hip_disp_para
     c->disp_par.extrapolate = p->extrapolate_disp_coeffs != 0;
     c->disp_par.schmidt = p->schmidt_mixing != 0;
     c->disp_on = true;
+    return 0;
+}
+
+// axilrod_teller: the triple-dipole term.  c9 (atomic units, upload order) is the EFFECTIVE per-atom coefficient: under
+// midzuno_kihara_approx the caller has already replaced it by 3/4 alpha 6.7483345 c6.  The polarizabilities are the upload's.
+extern "C" int mpmc_hip_set_axilrod_teller(mpmc_hip_ctx *c, int enable, int n, const double *c9) {
+    if (!c) return fail("MPMC_HIP: set_axilrod_teller: null context");
+    if (c->in_flight) return fail("MPMC_HIP: set_axilrod_teller between energy_begin() and energy_end()");
+    if (!c->have_atoms) return fail("MPMC_HIP: set_axilrod_teller: no configuration uploaded");
+    if (c->edited) return fail("MPMC_HIP: set_axilrod_teller: molecules were inserted or removed since the upload");
+    HIPCHK(hipSetDevice(c->device));
+    if (!enable) {
+        if (flush_moves(c)) return -1;
+        c->at_on = false;
+        c->at_part_valid = false;
+        ++c->config_rev;
+        return 0;
+    }
+    if (n != c->n) return fail("MPMC_HIP: set_axilrod_teller: %d coefficients for the %d atoms of the upload", n, c->n);
+    if (!c9) return fail("MPMC_HIP: set_axilrod_teller: null array");
+    if (flush_moves(c)) return -1;  // keep the order of the caller's operations
+    const size_t nall = c->max_npad;
+    std::vector<double> ha(nall, 0.0), hg(nall, 1.0);  // pad atoms: no three-body site
+    HIPCHK(hipMemcpyAsync(ha.data(), c->d_alpha, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < n; ++i) {
+        const double alpha = ha[i];
+        if (alpha < 0.0) return fail("MPMC_HIP: set_axilrod_teller: negative polarizability %g of atom %d", alpha, i);
+        const double ai = alpha * kAtAlpha;
+        ha[i] = ai;
+        // 1 / (c / p) with the reference's own p = pow(alpha * 6.7483345, 3) (axilrod_teller.cpp:121-122); c = 0 gives inf
+        hg[i] = (ai != 0.0) ? 1.0 / (c9[i] / std::pow(ai, 3)) : 1.0;
+    }
+    if (!c->d_at_a) {
+        HIPCHK(c->d_at_a.alloc(nall));
+        HIPCHK(c->d_at_g.alloc(nall));
+        HIPCHK(c->d_atpart.alloc((size_t)at_unit_count((int)(nall / 64)) * kAtSplit));
+    }
+    const size_t bd = nall * sizeof(double);
+    HIPCHK(hipMemcpyAsync(c->d_at_a, ha.data(), bd, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_at_g, hg.data(), bd, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->at_part_valid = false;
+    c->at_on = true;
+    ++c->config_rev;
+    return 0;
+}
+
+extern "C" int mpmc_hip_get_three_body_energy(mpmc_hip_ctx *c, double *out) {
+    if (!c || !out) return fail("MPMC_HIP: get_three_body_energy: null argument");
+    if (c->in_flight) return fail("MPMC_HIP: get_three_body_energy between energy_begin() and energy_end()");
+    *out = c->at_on ? c->three_body : 0.0;
     return 0;
 }
 
@@ -1293,6 +1355,7 @@ static bool edits_supported(const mpmc_hip_ctx *c) {
     const mpmc_hip_params &P = c->par;
     if (!c->have_atoms || c->all_dirty || !c->opt.incremental || !c->opt.incremental_pairs || !c->opt.pair_coef) return false;
     if (c->disp_on) return false;  // disp_expansion: no device-side insert / remove (the caller uploads again)
+    if (c->at_on) return false;    // axilrod_teller: the same
     // Gauss-Seidel: only with the chain kernel, whose view is rebuilt from the order the caller states afterwards
     if (!P.rd_only && P.polarization && (P.polar_gs || P.polar_gs_ranked) && !gs_order_mode(c)) return false;
     return true;
@@ -1851,7 +1914,7 @@ __global__ __launch_bounds__(64) void publish_side_kernel(double *__restrict__ d
     if (threadIdx.x == 0) h_res2[n] = seq;
 }
 constexpr unsigned kSideSlots = (1u << R_RD_PAIR) | (1u << R_ES_REAL) | (1u << R_ES_INTRA) | (1u << 3) | (1u << R_LRC) |
-                                (1u << R_RECIP) | (1u << R_SELF) | (1u << R_DISP) | (1u << R_DISP_LRC);
+                                (1u << R_RECIP) | (1u << R_SELF) | (1u << R_DISP) | (1u << R_DISP_LRC) | (1u << R_AT);
 
 // LJ / real-space Ewald tile kernel (graph slot GS_PAIR).  Tile partials persist: after a single-molecule
 // move only the tiles of the moved atoms' blocks are recomputed.
@@ -1966,6 +2029,27 @@ static int launch_disp(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hip
     return 0;
 }
 
+// axilrod_teller: the block-triple kernel behind the pair (and dispersion) launch -- same stream, same dirty blocks, same
+// move -- and the fixed-order sum of all its partials (an order that is a function of the block count only).
+static int launch_at(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipStream_t sb) {
+    const int ntile = c->npad / 64;
+    const AtAtoms ta = {c->d_at_a, c->d_at_g};
+    DirtyBlocks sel = c->call.dirty_blocks;
+    if (!c->at_part_valid) sel.n = 0;
+    if (c->at_part_valid && c->dirty_atoms.empty()) return 0;  // nothing moved: d_res[R_AT] is still that sum
+    const long units = at_unit_count(ntile);
+    const dim3 grid = sel.n > 0 ? dim3((unsigned)(ntile * (ntile + 1) / 2 * kAtSplit), (unsigned)sel.n)
+                                : dim3((unsigned)(units * kAtSplit));
+    ScopedTimer t(c, T_PAIR, sb);
+    hipLaunchKernelGGL(at_triple_kernel, grid, dim3(64 * kAtWaves), 0, sb, a, ta, bx, sel, ntile, c->d_atpart,
+                       c->call.disp_moves);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(kReduceThreads), 0, sb, c->d_atpart, (int)(units * kAtSplit), 1,
+                       c->d_res + R_AT);
+    HIPCHK(hipGetLastError());
+    c->at_part_valid = true;
+    return 0;
+}
+
 static int launch_publish(mpmc_hip_ctx *c) {
     const bool do_polar = c->call.do_polar;
     // (one wave unless the kernel also has the pair kernel's tile partials to add up)
@@ -2001,7 +2085,7 @@ static bool blocks_of(const std::vector<int> &atoms, DirtyBlocks &out) {
 static void collect_dirty_blocks(mpmc_hip_ctx *c) {
     DirtyBlocks &d = c->call.dirty_blocks;
     if (c->all_dirty || !c->opt.incremental_pairs || !blocks_of(c->dirty_atoms, d)) {
-        c->pair_part_valid = c->field_part_valid = c->disp_part_valid = false;
+        c->pair_part_valid = c->field_part_valid = c->disp_part_valid = c->at_part_valid = false;
         memset(&d, 0, sizeof(d));
     }
     c->call.pair_part_valid_before = c->pair_part_valid;  // false whenever the dirty-block list cannot be trusted
@@ -2133,6 +2217,12 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
         } else {
             k.res_zero_mask |= (1u << R_DISP) | (1u << R_DISP_LRC);
         }
+        // ---- axilrod_teller: the triple-dipole sum over ALL triples that are not on one molecule
+        if (c->at_on) {
+            if (launch_at(c, a, bx, sb)) return -1;
+        } else {
+            k.res_zero_mask |= 1u << R_AT;
+        }
 
         // ---- reciprocal + self (absent under Wolf summation, coulombic.c:27-28)
         if (!P.rd_only && !P.wolf) {
@@ -2214,7 +2304,7 @@ static bool graph_eligible(mpmc_hip_ctx *c) {
     const mpmc_hip_params &P = c->par;
     const SweepView &v = c->view[0];
     if (!c->opt.graph || is_timed_call(c) || !c->opt.incremental || !c->opt.incremental_pairs ||
-        !c->opt.pair_coef || c->disp_on)
+        !c->opt.pair_coef || c->disp_on || c->at_on)
         return false;
     if (P.rd_only || !P.polarization || P.polar_zodid || P.polar_gs || P.polar_gs_ranked || P.polar_precision != 0.0 ||
         P.polar_max_iter <= 0)
@@ -2480,6 +2570,8 @@ extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
     out->coulombic_energy = coul;
     out->polarization_energy = upol;
     out->energy = rd + coul + upol;  // energy.c:196
+    c->three_body = c->at_on ? r[R_AT] : 0.0;
+    if (c->at_on) out->energy += c->three_body;  // energy.c:194: behind the other terms (vdw_energy is 0 on this path)
     out->dipole_rrms = do_polar ? r[R_RRMS] : 0.0;
     out->volume = c->volume;
     out->cutoff = c->cutoff;

@@ -16,7 +16,8 @@ EXPORTS = [
     "mpmc_hip_last_error", "mpmc_hip_abi_version", "mpmc_hip_device_count", "mpmc_hip_create",
     "mpmc_hip_destroy", "mpmc_hip_set_option", "mpmc_hip_default_params", "mpmc_hip_set_params", "mpmc_hip_set_box",
     "mpmc_hip_scale_box",
-    "mpmc_hip_upload", "mpmc_hip_set_dispersion", "mpmc_hip_update_atoms", "mpmc_hip_insert_molecule", "mpmc_hip_remove_molecule",
+    "mpmc_hip_upload", "mpmc_hip_set_dispersion", "mpmc_hip_set_axilrod_teller", "mpmc_hip_get_three_body_energy",
+    "mpmc_hip_update_atoms", "mpmc_hip_insert_molecule", "mpmc_hip_remove_molecule",
     "mpmc_hip_slot_count", "mpmc_hip_set_sweep_order", "mpmc_hip_energy", "mpmc_hip_energy_begin", "mpmc_hip_energy_end",
     "mpmc_hip_download_dipoles",
     "mpmc_hip_download_amatrix", "mpmc_hip_download_ranking", "mpmc_hip_get_timings",
@@ -111,6 +112,8 @@ class DispParams(C.Structure):
 
 PARAM_NAMES = [f[0] for f in Params._fields_]
 DISP_NAMES = [f[0] for f in DispParams._fields_]
+AT_NAMES = ["axilrod_teller", "midzuno_kihara_approx"]  # mpmc_hip_set_axilrod_teller (reference keywords)
+AT_ALPHA_AU = 6.7483345  # A^3 -> Bohr^3, as the reference writes it (axilrod_teller.cpp:115)
 
 _lib = None
 
@@ -141,6 +144,8 @@ def load():
     lib.mpmc_hip_scale_box.argtypes = [vp, dp, C.c_double, C.c_int, vp]
     lib.mpmc_hip_upload.argtypes = [vp, C.c_int] + [vp] * 10
     lib.mpmc_hip_set_dispersion.argtypes = [vp, C.POINTER(DispParams), C.c_int, vp, vp, vp]
+    lib.mpmc_hip_set_axilrod_teller.argtypes = [vp, C.c_int, C.c_int, vp]
+    lib.mpmc_hip_get_three_body_energy.argtypes = [vp, dp]
     lib.mpmc_hip_update_atoms.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     lib.mpmc_hip_insert_molecule.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
     lib.mpmc_hip_remove_molecule.argtypes = [vp, C.c_int, C.c_int]
@@ -184,10 +189,23 @@ def make_params(**kw):
             continue  # a box property at this boundary (set_box)
         if k in DISP_NAMES:
             continue  # mpmc_hip_set_dispersion's record (Engine.load_system)
+        if k in AT_NAMES:
+            continue  # mpmc_hip_set_axilrod_teller's arguments (Engine.load_system)
         if k not in PARAM_NAMES:
             raise KeyError(k)
         setattr(p, k, v)
     return p
+
+
+def effective_c9(system, midzuno_kihara_approx=False):
+    """Per-atom c9 as mpmc_hip_set_axilrod_teller() takes it: the array as read, or the Midzuno-Kihara replacement
+    3/4 * alpha * 6.7483345 * c6 evaluated left to right as the reference does (axilrod_teller.cpp:115)."""
+    n = len(system["alpha"])
+    if midzuno_kihara_approx:
+        alpha = np.asarray(system["alpha"], dtype=np.float64)
+        c6 = np.asarray(system.get("c6", np.zeros(n)), dtype=np.float64)
+        return np.ascontiguousarray(3.0 / 4.0 * alpha * AT_ALPHA_AU * c6)
+    return np.ascontiguousarray(system.get("c9", np.zeros(n)), dtype=np.float64)
 
 
 class Engine:
@@ -256,14 +274,34 @@ class Engine:
                 raise ValueError("c6 / c8 / c10 must have one entry per uploaded atom")
         _chk(self.lib.mpmc_hip_set_dispersion(self.ctx, C.byref(p), n, *[a.ctypes.data for a in arrs]))
 
+    def set_axilrod_teller(self, system, enable=True, midzuno_kihara_approx=False):
+        """The three-body term (mpmc_hip_set_axilrod_teller), after upload(): the per-atom c9 of `system` (atomic units; a
+        missing array reads as zeros), or under midzuno_kihara_approx 3/4 alpha 6.7483345 c6 in its place
+        (axilrod_teller.cpp:114-118).  enable=False switches the term off."""
+        if not enable:
+            _chk(self.lib.mpmc_hip_set_axilrod_teller(self.ctx, 0, 0, None))
+            return
+        c9 = effective_c9(system, midzuno_kihara_approx)
+        if c9.shape != (self.n,):
+            raise ValueError("c9 (c6, alpha) must have one entry per uploaded atom")
+        _chk(self.lib.mpmc_hip_set_axilrod_teller(self.ctx, 1, self.n, c9.ctypes.data))
+
+    def three_body_energy(self):
+        """observables->three_body_energy of the last completed energy(); 0 while the term is off."""
+        v = C.c_double(0.0)
+        _chk(self.lib.mpmc_hip_get_three_body_energy(self.ctx, C.byref(v)))
+        return v.value
+
     def load_system(self, system, params):
         """Convenience: params (incl. optional pbc_cutoff) + box + atoms (+ the dispersion record when the flags carry
-        disp_expansion)."""
+        disp_expansion, + the three-body coefficients when they carry axilrod_teller)."""
         self.set_params(**params)
         self.set_box(system["basis"], params.get("pbc_cutoff", 0.0))
         self.upload(system)
         if params.get("disp_expansion"):
             self.set_dispersion(system, **{k: params[k] for k in DISP_NAMES if k in params})
+        if params.get("axilrod_teller"):
+            self.set_axilrod_teller(system, midzuno_kihara_approx=bool(params.get("midzuno_kihara_approx")))
 
     def update_atoms(self, first, pos):
         pos = np.ascontiguousarray(pos, dtype=np.float64)

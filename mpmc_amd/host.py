@@ -77,6 +77,14 @@ def load():
     lib.host_get_dispersion.restype = None
     lib.host_set_dispersion.argtypes = [vp, vp, vp, vp]
     lib.host_set_dispersion.restype = None
+    lib.host_get_at_flags.argtypes = [vp, vp]
+    lib.host_get_at_flags.restype = None
+    lib.host_get_c9.argtypes = [vp, vp]
+    lib.host_get_c9.restype = None
+    lib.host_set_c9.argtypes = [vp, vp]
+    lib.host_set_c9.restype = None
+    lib.host_get_three_body_energy.argtypes = [vp]
+    lib.host_get_three_body_energy.restype = C.c_double
     lib.host_unsupported.argtypes = [vp]
     lib.host_unsupported.restype = C.c_char_p
     lib.volume_change.argtypes = [vp]
@@ -91,7 +99,8 @@ def config_text(flags, extra=None):
     """flags in C-ABI / oracle naming -> the reference's keyword lines."""
     onoff = {"rd_only", "rd_lrc", "feynman_hibbs", "polarization", "polar_gs", "polar_gs_ranked", "polar_sor",
              "polar_esor", "polar_palmo", "polar_rrms", "polar_zodid", "polar_wolf", "polar_ewald", "wolf",
-             "disp_expansion", "damp_dispersion", "extrapolate_disp_coeffs", "schmidt_mixing"}
+             "disp_expansion", "damp_dispersion", "extrapolate_disp_coeffs", "schmidt_mixing", "axilrod_teller",
+             "midzuno_kihara_approx"}
     lines = []
     for k, v in flags.items():
         if k in onoff:
@@ -143,6 +152,9 @@ class HostSystem:
         if "c6" in system:  # PHAHST: per-atom dispersion coefficients (atomic units)
             c = [np.ascontiguousarray(system.get(k, np.zeros(n)), dtype=np.float64) for k in ("c6", "c8", "c10")]
             self.lib.host_set_dispersion(self.ptr, *[a.ctypes.data for a in c])
+        if "c9" in system:  # axilrod_teller: per-atom three-body coefficient (atomic units)
+            c9 = np.ascontiguousarray(system["c9"], dtype=np.float64)
+            self.lib.host_set_c9(self.ptr, c9.ctypes.data)
         extra = dict({"move_factor": move_factor, "rot_factor": rot_factor}, **(extra or {}))
         if self.lib.host_apply_config(self.ptr, config_text(flags, extra).encode()) != 0:
             raise ValueError("host layer rejected the configuration")
@@ -162,6 +174,10 @@ class HostSystem:
         """Engine A/B knob (mpmc_hip_set_option); the device context exists after the first energy()."""
         if self.lib.host_set_option(self.ptr, name.encode(), int(value)) != 0:
             raise engine.EngineError(engine.load().mpmc_hip_last_error().decode())
+
+    def three_body_energy(self):
+        """observables->three_body_energy of the last energy() (0 unless axilrod_teller is on)."""
+        return self.lib.host_get_three_body_energy(self.ptr)
 
     def observables(self):
         out = np.zeros(8)

@@ -229,6 +229,22 @@ void host_set_dispersion(system_t *system, const double *c6, const double *c8, c
             a->c10 = c10[i];
         }
 }
+/* ---- axilrod_teller ------------------------------------------------------------------------------------------- */
+void host_get_at_flags(system_t *system, int out[2]) {
+    out[0] = system->axilrod_teller;
+    out[1] = system->midzuno_kihara_approx;
+}
+void host_get_c9(system_t *system, double *c9) {
+    int i = 0;
+    for (molecule_t *m = system->molecules; m; m = m->next)
+        for (atom_t *a = m->atoms; a; a = a->next, i++) c9[i] = a->c9;
+}
+void host_set_c9(system_t *system, const double *c9) {
+    int i = 0;
+    for (molecule_t *m = system->molecules; m; m = m->next)
+        for (atom_t *a = m->atoms; a; a = a->next, i++) a->c9 = c9[i];
+}
+double host_get_three_body_energy(system_t *system) { return system->observables->three_body_energy; }
 /* the reason energy() would refuse this system, or NULL */
 const char *host_unsupported(system_t *system) { return energy_hip_unsupported(system); }
 

@@ -55,6 +55,7 @@ typedef struct shim_state {
     int cap;
     double *x, *y, *z, *q, *alpha, *eps, *sig, *mass;
     double *c6, *c8, *c10; /* disp_expansion: sent with every full upload (mpmc_hip_set_dispersion) */
+    double *c9;            /* axilrod_teller: per atom as read; its effective value goes with every full upload */
     mpmc_hip_disp_params disp; /* as last sent */
     /* the resident molecules in LIST order */
     resident_t *res, *res2;
@@ -93,9 +94,9 @@ static shim_state *state_of(system_t *system, int create) {
 
 static void free_image(shim_state *st) {
     free(st->x); free(st->y); free(st->z); free(st->q); free(st->alpha); free(st->eps); free(st->sig); free(st->mass);
-    free(st->c6); free(st->c8); free(st->c10);
+    free(st->c6); free(st->c8); free(st->c10); free(st->c9);
     st->x = st->y = st->z = st->q = st->alpha = st->eps = st->sig = st->mass = NULL;
-    st->c6 = st->c8 = st->c10 = NULL;
+    st->c6 = st->c8 = st->c10 = st->c9 = NULL;
     st->cap = 0;
 }
 
@@ -225,8 +226,9 @@ static void fill_disp_params(const system_t *s, mpmc_hip_disp_params *d) {
 static const char *unsupported(const system_t *s) {
 #ifndef MPMC_SHIM_HOST_MIRROR
     if (s->sg || s->dreiding || s->lj_buffered_14_7 || s->rd_anharmonic || s->cdvdw_exp_repulsion ||
-        s->axilrod_teller || s->gwp || s->spectre)
-        return "only Lennard-Jones or disp_expansion repulsion / dispersion with point charges is on the device";
+        s->gwp || s->spectre)
+        return "only Lennard-Jones or disp_expansion repulsion / dispersion (with or without axilrod_teller) and point "
+               "charges are on the device";
     /* pairs.c:85-141: these mixing branches come before the disp_expansion one (sg, cdvdw_sig_repulsion, polarvdw and
      * cdvdw_exp_repulsion are refused above and below) */
     if (s->disp_expansion && (s->waldmanhagler || s->halgren_mixing || s->cdvdw_9th_repulsion))
@@ -277,8 +279,9 @@ static int image_reserve(shim_state *st, int cap) {
     const size_t b = (size_t)cap * sizeof(double);
     st->x = malloc(b); st->y = malloc(b); st->z = malloc(b); st->q = malloc(b); st->alpha = malloc(b);
     st->eps = malloc(b); st->sig = malloc(b); st->mass = malloc(b);
-    st->c6 = malloc(b); st->c8 = malloc(b); st->c10 = malloc(b);
-    if (!(st->x && st->y && st->z && st->q && st->alpha && st->eps && st->sig && st->mass && st->c6 && st->c8 && st->c10))
+    st->c6 = malloc(b); st->c8 = malloc(b); st->c10 = malloc(b); st->c9 = malloc(b);
+    if (!(st->x && st->y && st->z && st->q && st->alpha && st->eps && st->sig && st->mass && st->c6 && st->c8 && st->c10 &&
+          st->c9))
         return -1;
     st->cap = cap;
     return 0;
@@ -340,7 +343,7 @@ static int full_upload(shim_state *st, system_t *system) {
             st->x[i] = a->pos[0]; st->y[i] = a->pos[1]; st->z[i] = a->pos[2];
             st->q[i] = a->charge; st->alpha[i] = a->polarizability; st->eps[i] = a->epsilon; st->sig[i] = a->sigma;
             st->mass[i] = a->mass;
-            st->c6[i] = a->c6; st->c8[i] = a->c8; st->c10[i] = a->c10;
+            st->c6[i] = a->c6; st->c8[i] = a->c8; st->c10[i] = a->c10; st->c9[i] = a->c9;
             mol[i] = mi; /* list position: distinct per molecule even if PQR ids repeat */
             fz[i] = (uint8_t)(a->frozen != 0);
         }
@@ -360,6 +363,20 @@ static int full_upload(shim_state *st, system_t *system) {
     /* (an upload leaves the context on Lennard-Jones: nothing to say unless the PHAHST potential is asked for) */
     if (st->disp.disp_expansion && mpmc_hip_set_dispersion(st->ctx, &st->disp, n, st->c6, st->c8, st->c10))
         return hip_fail("set_dispersion");
+    if (system->axilrod_teller) {
+        /* the engine takes the EFFECTIVE per-atom coefficient: c9 as read, or the Midzuno-Kihara replacement
+         * (axilrod_teller.cpp:114-118, the same expression left to right) */
+        double *eff = malloc((n > 0 ? n : 1) * sizeof(double));
+        if (!eff) {
+            error("ENERGY: HIP engine: out of host memory\n");
+            return -1;
+        }
+        for (int k = 0; k < n; k++)
+            eff[k] = system->midzuno_kihara_approx ? 3.0 / 4.0 * st->alpha[k] * 6.7483345 * st->c6[k] : st->c9[k];
+        rc = mpmc_hip_set_axilrod_teller(st->ctx, 1, n, eff);
+        free(eff);
+        if (rc) return hip_fail("set_axilrod_teller");
+    }
     st->uploaded = 1;
     st->in_sync = 1;
     st->nnotes = 0;
@@ -453,7 +470,7 @@ static int same_species(const shim_state *st, const molecule_t *m, const residen
         if (k == r->natoms) return 0;
         if (a->charge != st->q[s + k] || a->polarizability != st->alpha[s + k] || a->epsilon != st->eps[s + k] ||
             a->sigma != st->sig[s + k] || a->mass != st->mass[s + k] || a->c6 != st->c6[s + k] || a->c8 != st->c8[s + k] ||
-            a->c10 != st->c10[s + k])
+            a->c10 != st->c10[s + k] || a->c9 != st->c9[s + k])
             return 0;
     }
     return k == r->natoms;
@@ -564,11 +581,13 @@ static int sync_walk(shim_state *st, system_t *system) {
     for (int f = 0; f < nfresh; f++) {
         resident_t *r = &out[fresh[f]];
         double tx[64], ty[64], tz[64], q[64], al[64], ep[64], sg[64], ms[64];
+        double d6[64], d8[64], d10[64], d9[64]; /* not sent (Lennard-Jones mode), but part of the image same_species() reads */
         int k = 0;
         for (atom_t *a = r->mol->atoms; a; a = a->next, k++) {
             if (k == 64) return 1;
             tx[k] = a->pos[0]; ty[k] = a->pos[1]; tz[k] = a->pos[2];
             q[k] = a->charge; al[k] = a->polarizability; ep[k] = a->epsilon; sg[k] = a->sigma; ms[k] = a->mass;
+            d6[k] = a->c6; d8[k] = a->c8; d10[k] = a->c10; d9[k] = a->c9;
         }
         int s = -1;
         const int rc = mpmc_hip_insert_molecule(st->ctx, k, tx, ty, tz, q, al, ep, sg, ms, r->frozen, &s);
@@ -577,6 +596,7 @@ static int sync_walk(shim_state *st, system_t *system) {
         for (int a = 0; a < k; a++) {
             st->x[s + a] = tx[a]; st->y[s + a] = ty[a]; st->z[s + a] = tz[a];
             st->q[s + a] = q[a]; st->alpha[s + a] = al[a]; st->eps[s + a] = ep[a]; st->sig[s + a] = sg[a]; st->mass[s + a] = ms[a];
+            st->c6[s + a] = d6[a]; st->c8[s + a] = d8[a]; st->c10[s + a] = d10[a]; st->c9[s + a] = d9[a];
         }
         r->slot = s;
     }
@@ -738,6 +758,12 @@ double energy_hip_end(system_t *system) {
     o->coulombic_energy = r.coulombic_energy;
     o->polarization_energy = r.polarization_energy;
     o->energy = r.energy;
+    o->three_body_energy = 0.0; /* energy.c:148-151, :194: part of o->energy when axilrod_teller is on */
+    if (system->axilrod_teller && mpmc_hip_get_three_body_energy(st->ctx, &o->three_body_energy)) {
+        hip_fail("get_three_body_energy");
+        device_failed(st);
+        return NAN;
+    }
     o->dipole_rrms = r.dipole_rrms;
     system->nodestats->polarization_iterations = (double)r.polar_iterations;
     if (r.iter_success) system->iter_success = 1; /* thole_iterative.c:207; mc.c:347 resets it */

@@ -151,6 +151,8 @@ int do_command(system_t *system, char **token) {
     FLAG("extrapolate_disp_coeffs", extrapolate_disp_coeffs);
     FLAG("damp_dispersion", damp_dispersion);
     FLAG("schmidt_mixing", schmidt_mixing);
+    FLAG("axilrod_teller", axilrod_teller); /* input.c:992-1013 */
+    FLAG("midzuno_kihara_approx", midzuno_kihara_approx);
     FLAG("disp_expansion_mbvdw", disp_expansion_mbvdw); /* these four are refused by energy_hip.c, each by name */
     FLAG("gilbert_smith_mixing", gilbert_smith_mixing);
     FLAG("bohm_ahlrichs_mixing", bohm_ahlrichs_mixing);
@@ -289,11 +291,12 @@ molecule_t *read_molecules(FILE *fp, system_t *system) {
         a->polarizability = atof(t[11]);
         a->epsilon = atof(t[12]);
         a->sigma = atof(t[13]);
-        /* t[14], t[15]: omega and gwp_alpha (not used here); then c6, c8, c10 in atomic units (read_pqr.c:216, :255-257);
-         * absent columns read as 0 */
+        /* t[14], t[15]: omega and gwp_alpha (not used here); then c6, c8, c10 and c9 in atomic units (read_pqr.c:216,
+         * :255-258); absent columns read as 0 */
         a->c6 = atof(t[16]);
         a->c8 = atof(t[17]);
         a->c10 = atof(t[18]);
+        a->c9 = atof(t[19]);
         molecule_ptr->mass += a->mass;
         if (atom_tail)
             atom_tail->next = a;
@@ -507,13 +510,13 @@ int write_molecules(system_t *system, const char *filename) {
     int i = 1;
     for (molecule_t *m = system->molecules; m; m = m->next)
         for (atom_t *a = m->atoms; a; a = a->next, i++)
-            /* omega and gwp_alpha (not held here: 0), then c6 c8 c10, as output.c:436-445 writes them: a restart from this
-             * file keeps the dispersion coefficients of a disp_expansion run */
+            /* omega and gwp_alpha (not held here: 0), then c6 c8 c10 c9, as output.c:436-447 writes them: a restart from
+             * this file keeps the dispersion coefficients of a disp_expansion / axilrod_teller run */
             fprintf(fp, "ATOM  %5d %-4.45s %-3.3s %-1.1s %4d   %8.3f%8.3f%8.3f %8.5f %8.5f %8.5f %8.5f %8.5f %8.5f %8.5f %8.5f "
-                        "%8.5f %8.5f\n", i,
+                        "%8.5f %8.5f %8.5f\n", i,
                     a->atomtype[0] ? a->atomtype : "X", m->moleculetype[0] ? m->moleculetype : "M",
                     m->frozen ? "F" : "M", m->id, a->pos[0], a->pos[1], a->pos[2], a->mass, a->charge / E2REDUCED,
-                    a->polarizability, a->epsilon, a->sigma, 0.0, 0.0, a->c6, a->c8, a->c10);
+                    a->polarizability, a->epsilon, a->sigma, 0.0, 0.0, a->c6, a->c8, a->c10, a->c9);
     fprintf(fp, "END\n");
     fclose(fp);
     return 0;

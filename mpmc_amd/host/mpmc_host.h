@@ -37,6 +37,7 @@ typedef struct _atom {
     int frozen;
     double mass, charge, polarizability, epsilon, sigma;
     double c6, c8, c10; /* disp_expansion: dispersion coefficients in atomic units (structs.h:54, read_pqr.c:255-257) */
+    double c9;          /* axilrod_teller: three-body coefficient in atomic units (read_pqr.c:258) */
     double pos[3], wrapped_pos[3];
     double ef_static[3], ef_static_self[3], ef_induced[3], ef_induced_change[3];
     double mu[3], old_mu[3], new_mu[3];
@@ -112,6 +113,8 @@ typedef struct _system {
      * four are read so that energy_hip.c can refuse them by name */
     int disp_expansion, extrapolate_disp_coeffs, damp_dispersion, schmidt_mixing;
     int disp_expansion_mbvdw, gilbert_smith_mixing, bohm_ahlrichs_mixing, wilson_popelier_mixing;
+    /* the triple-dipole three-body term (structs.h:422); midzuno_kihara_approx: c9 = 3/4 alpha c6 per atom */
+    int axilrod_teller, midzuno_kihara_approx;
     int iter_success; /* the reference's convergence-FAILURE flag */
     int natoms;
     char job_name[MAXLINE], pqr_input[MAXLINE], energy_output[MAXLINE], pqr_output[MAXLINE];

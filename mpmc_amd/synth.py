@@ -1,4 +1,5 @@
-"""Synthetic periodic boxes: S-LJ(N), S-ES(N), S-POL(N), and S-PHAHST(N) for disp_expansion.
+"""Synthetic periodic boxes: S-LJ(N), S-ES(N), S-POL(N), S-PHAHST(N) for disp_expansion and S-AT(N) for
+axilrod_teller.
 
 Deterministic (seeded) inputs of the shapes BASELINE.json names, used by bench.py and the
 parity tests.  Units as the reference reads them: Angstrom, K, charges already multiplied by
@@ -149,6 +150,62 @@ def s_phahst(n, seed=None, spacing=3.6):
     return out
 
 
+# Sites of the three-body box (Angstrom^3, K, Angstrom, atomic units): an argon-like atom, the two sites of a rigid
+# nitrogen-like dimer and a carbon-like framework atom.  Magnitudes of the published values, not a parameter set.
+# (mass, charge/e, alpha, epsilon, sigma, c6, c9)
+AT_ATOM = (39.948, 0.0, 1.6411, 119.8, 3.405, 64.3, 518.3)
+AT_DIMER = ((14.0067, 0.2, 0.80, 36.0, 3.31, 24.0, 100.0), (14.0067, -0.2, 0.80, 36.0, 3.31, 24.0, 100.0))
+AT_DIMER_BOND = 1.10
+AT_FRAMEWORK = (12.011, 0.0, 1.20, 50.0, 3.40, 40.0, 250.0)
+
+
+def s_at(n, seed=None, spacing=3.8):
+    """A box for the Axilrod-Teller term (axilrod_teller): the first third of the atoms (rounded down) is ONE frozen
+    multi-atom framework molecule on a slab of the lattice; then (n - n/3) / 4 rigid two-site sorbates with both sites
+    active -- preceded by one single atom when that makes a dimer sit on atoms 127 / 128, across a 64-atom block
+    boundary --; the rest are single argon-like atoms, of which every 7th has polarizability 0 and every 5th has a
+    polarizability but c9 = 0.  Carries c6 and c9 (atomic units) next to the usual arrays."""
+    rng = np.random.default_rng(5234 + n if seed is None else seed)
+    nfr = n // 3
+    ndim = (n - nfr) // 4
+    lead = 1 if nfr % 2 == 0 else 0  # dimers then start on an odd atom index: one of them straddles every block boundary
+    nsingle = n - nfr - 2 * ndim
+    com, L = _lattice(nfr + ndim + nsingle, spacing, 0.3, rng)
+    rest = nfr + rng.permutation(ndim + nsingle)  # sorbate sites in random order; the framework keeps its slab
+    ax = _random_axes(ndim, rng)
+    rows, pos = [], []
+
+    def add(p, site, mol, frozen, alpha=None, c9=None):
+        ms, qq, al, ep, sg, c6, c9_ = site
+        pos.append(p)
+        rows.append((qq, al if alpha is None else alpha, ep, sg, ms, mol, frozen, c6, c9_ if c9 is None else c9))
+
+    for f in range(nfr):
+        add(com[f], AT_FRAMEWORK, 1, 1)
+    site, mol = 0, 2
+    singles = 0
+
+    def single():
+        nonlocal site, mol, singles
+        kind = singles % 7 == 3, singles % 5 == 2
+        add(com[rest[site]], AT_ATOM, mol, 0, alpha=0.0 if kind[0] else None, c9=0.0 if (kind[1] and not kind[0]) else None)
+        site, mol, singles = site + 1, mol + 1, singles + 1
+
+    for _ in range(lead):
+        single()
+    for m in range(ndim):
+        c = com[rest[site]]
+        add(c + 0.5 * AT_DIMER_BOND * ax[m], AT_DIMER[0], mol, 0)
+        add(c - 0.5 * AT_DIMER_BOND * ax[m], AT_DIMER[1], mol, 0)
+        site, mol = site + 1, mol + 1
+    for _ in range(nsingle - lead):
+        single()
+    r = np.array(rows, dtype=np.float64)
+    out = _finish(np.array(pos), r[:, 0], r[:, 1], r[:, 2], r[:, 3], r[:, 4], r[:, 5], r[:, 6], L)
+    out.update(c6=r[:, 7].copy(), c9=r[:, 8].copy())
+    return out
+
+
 # flag sets (reference config keywords) used with the synthetic polarizable boxes
 FLAGS_POL_JACOBI = dict(temperature=77.0, polarization=1, polar_damp=2.1304, polar_max_iter=10,
                         feynman_hibbs=1, feynman_hibbs_order=4)
@@ -158,4 +215,6 @@ FLAGS_POL_PRODUCTION = dict(temperature=77.0, polarization=1, polar_damp=2.1304,
 # the polarizable set with the PHAHST repulsion / dispersion (Tang-Toennies damping, C10 extrapolated, default mixing)
 FLAGS_PHAHST = dict(FLAGS_POL_JACOBI, disp_expansion=1, damp_dispersion=1, extrapolate_disp_coeffs=1, schmidt_mixing=0)
 FLAGS_LJ = dict(temperature=100.0, rd_only=1)
+# Lennard-Jones + Ewald with the three-body term (per-atom c9 as read; add midzuno_kihara_approx=1 for 3/4 alpha c6)
+FLAGS_AT = dict(temperature=100.0, axilrod_teller=1)
 FLAGS_ES = dict(temperature=100.0)
