@@ -277,6 +277,27 @@ int mpmc_hip_set_axilrod_teller(mpmc_hip_ctx *ctx, int enable, int n, const doub
 /* observables->three_body_energy of the last completed energy() / energy_end(); 0 while the term is off. */
 int mpmc_hip_get_three_body_energy(mpmc_hip_ctx *ctx, double *out);
 
+/* rd_crystal, Lennard-Jones summed over lattice images beyond the minimum image (reference src/energy/lj.c:109-276).
+ * order = rd_crystal_order: 0 switches the mode off, 1 .. 4 switch it on; anything else is an error.  With
+ * cutoff_c = 2.0 * cutoff * ((double)order - 0.5) (cutoff: mpmc_hip_result.cutoff) and n in {-(order-1) .. order-1}^3,
+ * rd_energy becomes the sum of
+ *   - the pair part: every unordered pair that is not frozen-frozen, same-molecule pairs included, with
+ *     rimg - 1e-12 < cutoff_c: 4 eps_ij (s12 - s6), s6 = sum_n (|sigma_ij| / r_n)^6 over the images with
+ *     !(r_n > cutoff_c), r_n from the RAW resident coordinates pos_i - pos_j + n.basis (not the minimum image: moving
+ *     a molecule by a lattice vector changes the sum, as in the reference), n = 0 skipped for a same-molecule pair;
+ *     under feynman_hibbs lj_fh_corr once per pair, with the summed terms, at rimg;
+ *   - the self part: every atom (frozen ones included) with its own images n != 0, |n.basis| <= cutoff_c, half weight;
+ *   - with rd_lrc the long-range correction evaluated at cutoff_c.
+ * The decision `r_n > cutoff_c` is taken in fp64 in the reference's operation order, so an image exactly at the cutoff
+ * counts here when it counts there.  The mixing is the Lennard-Jones path's.
+ * A setting of the context like mpmc_hip_set_params(): it carries no per-atom data and persists across uploads.  Not
+ * allowed between energy_begin() and energy_end().  energy() refuses the combination with disp_expansion
+ * (mpmc_hip_set_dispersion), whose sum in the reference ignores rd_crystal.  While it is on, insert_molecule /
+ * remove_molecule answer 1 (upload the whole configuration again); update_atoms, scale_box, energy_begin / _end,
+ * several contexts, rd_only, polarization, Ewald / Wolf and axilrod_teller work as before, and after a move only the
+ * tiles of the moved atoms' blocks are summed again, with the bits of a from-scratch evaluation. */
+int mpmc_hip_set_rd_crystal(mpmc_hip_ctx *ctx, int order);
+
 /* New coordinates for atoms [first, first+count): the delta after one MC move
  * (make_move perturbs one molecule, mc_moves.c:567). */
 int mpmc_hip_update_atoms(mpmc_hip_ctx *ctx, int first, int count, const double *x, const double *y,

@@ -38,6 +38,7 @@
 #include "kernels_pair.h"
 #include "kernels_disp.h"
 #include "kernels_at.h"
+#include "kernels_crystal.h"
 #include "kernels_polar.h"
 #include "kernels_gs.h"
 #include "kernels_gs_chain.h"
@@ -173,6 +174,8 @@ enum ResSlot {
     R_DISP = 12,      // disp_expansion: the dense pair sum (kernels_disp.h) ...
     R_DISP_LRC = 13,  // ... and its long-range correction; both read as zero outside that mode
     R_AT = 14,        // axilrod_teller: the triple-dipole sum (kernels_at.h); reads as zero outside that mode
+    R_RDC_SELF = 15,  // rd_crystal: the self part (kernels_crystal.h); its pair part and long-range correction take R_DISP and
+                      // R_DISP_LRC, which the two modes cannot both want (energy() refuses the combination)
     R_COUNT = 16
 };
 
@@ -399,6 +402,14 @@ struct mpmc_hip_ctx {
     DevBuf<double> d_atpart;        // [at_unit_count(ntile)][kAtSplit] block-triple partials
     bool at_part_valid = false;     // ... of the configuration (and box) before the pending moves
     double three_body = 0.0;        // the term of the last completed energy_end() (0 outside the mode)
+    // ---- rd_crystal (mpmc_hip_set_rd_crystal): Lennard-Jones over lattice images, kernels_crystal.h.  A context setting:
+    // it carries no per-atom data and persists across uploads.  The LJ kernels are handed d_zero, as under disp_expansion.
+    int rdc_order = 0;              // 0 = off, 1 .. kRdcMaxOrder
+    DevBuf<double> d_rdcpart;       // [ntile*ntile] tile partials of the image sum
+    bool rdc_part_valid = false;    // ... of the configuration (and box) before the pending moves
+    DevBuf<double> d_rdclrcpart;    // [ntile*ntile] tile partials of the long-range correction at cutoff_c
+    bool rdc_static_valid = false;  // d_res[R_RDC_SELF] / [R_DISP_LRC] are those of the current parameters, box and rd_lrc
+    int rdc_static_lrc = -1;        // the rd_lrc they were made under
     bool lrc_valid = false;
     double lrc_cached = 0.0;
     DevBuf<KVec> d_kvec;
@@ -488,8 +499,8 @@ static DevAtoms dev_atoms(const mpmc_hip_ctx *c) {
     a.z = c->d_z;
     a.q = c->d_q;
     a.alpha = c->d_alpha;
-    a.eps = c->disp_on ? c->d_zero : c->d_eps;
-    a.sig = c->disp_on ? c->d_zero : c->d_sig;
+    a.eps = (c->disp_on || c->rdc_order) ? c->d_zero : c->d_eps;
+    a.sig = (c->disp_on || c->rdc_order) ? c->d_zero : c->d_sig;
     a.molmass = c->d_molmass;
     a.mol = c->d_mol;
     a.flags = c->d_flags;
@@ -885,7 +896,7 @@ extern "C" int mpmc_hip_set_params(mpmc_hip_ctx *c, const mpmc_hip_params *p) {
         if (p->polar_gamma < 0.0) return fail("MPMC_HIP: invalid Pre-cond/SOR/ESOR gamma set");
     }
     if (p->polar_damp != c->par.polar_damp) c->all_dirty = true;
-    c->pair_part_valid = c->field_part_valid = c->disp_part_valid = false;
+    c->pair_part_valid = c->field_part_valid = c->disp_part_valid = c->rdc_part_valid = false;
     ++c->config_rev;
     c->par = *p;
     c->have_params = true;
@@ -942,6 +953,7 @@ static int apply_box(mpmc_hip_ctx *c, const double basis[9], double pbc_cutoff) 
     c->kvec_valid = false;
     c->lrc_valid = false;
     c->disp_lrc_valid = false;
+    c->rdc_static_valid = false;
     c->all_dirty = true;
     return 0;
 }
@@ -1022,6 +1034,7 @@ extern "C" int mpmc_hip_upload(mpmc_hip_ctx *c, int n, const double *x, const do
     c->disp_part_valid = c->disp_lrc_valid = false;
     c->at_on = false;  // ... and no three-body term until set_axilrod_teller() says otherwise
     c->at_part_valid = false;
+    c->rdc_part_valid = c->rdc_static_valid = false;  // (the rd_crystal setting itself stays: it holds no per-atom data)
     c->rank_saved.clear();
     c->perm_ranked = false;
     c->pending.n = 0;
@@ -1056,6 +1069,14 @@ extern "C" int mpmc_hip_upload(mpmc_hip_ctx *c, int n, const double *x, const do
 }
 
 static int flush_moves(mpmc_hip_ctx *c);
+// the zero epsilon / sigma the Lennard-Jones kernels read under disp_expansion and rd_crystal
+static int alloc_zero_params(mpmc_hip_ctx *c) {
+    if (c->d_zero) return 0;
+    HIPCHK(c->d_zero.alloc(c->max_npad));
+    HIPCHK(hipMemsetAsync(c->d_zero, 0, (size_t)c->max_npad * sizeof(double), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
 // disp_expansion (PHAHST): the resident epsilon / sigma become the exponent b and the range rho of the exponential
 // repulsion, and c6 / c8 / c10 (atomic units, upload order) arrive here.  Until the next upload the LJ kernels see zero
 // parameters and the dense kernels of kernels_disp.h form rd_energy.
@@ -1083,11 +1104,10 @@ extern "C" int mpmc_hip_set_dispersion(mpmc_hip_ctx *c, const mpmc_hip_disp_para
         HIPCHK(c->d_c6.alloc(nall));
         HIPCHK(c->d_c8.alloc(nall));
         HIPCHK(c->d_c10.alloc(nall));
-        HIPCHK(c->d_zero.alloc(nall));
         HIPCHK(c->d_disppart.alloc(ntile * ntile));
         HIPCHK(c->d_displrcpart.alloc(ntile * ntile));
-        HIPCHK(hipMemsetAsync(c->d_zero, 0, nall * sizeof(double), c->stream));
     }
+    if (alloc_zero_params(c)) return -1;
     std::vector<double> h6(nall, 0.0), h8(nall, 0.0), h10(nall, 0.0);  // pad atoms: zeros
     std::copy(c6, c6 + n, h6.begin());
     std::copy(c8, c8 + n, h8.begin());
@@ -1145,6 +1165,33 @@ extern "C" int mpmc_hip_set_axilrod_teller(mpmc_hip_ctx *c, int enable, int n, c
     HIPCHK(hipStreamSynchronize(c->stream));
     c->at_part_valid = false;
     c->at_on = true;
+    ++c->config_rev;
+    return 0;
+}
+
+// rd_crystal: Lennard-Jones summed over the lattice images n in {-(order-1) .. order-1}^3 out to
+// 2 * pbc_cutoff * (order - 0.5) (kernels_crystal.h).  0 switches it off.  A setting of the context, like set_params().
+extern "C" int mpmc_hip_set_rd_crystal(mpmc_hip_ctx *c, int order) {
+    if (!c) return fail("MPMC_HIP: set_rd_crystal: null context");
+    if (c->in_flight) return fail("MPMC_HIP: set_rd_crystal between energy_begin() and energy_end()");
+    if (order < 0 || order > kRdcMaxOrder)
+        return fail("MPMC_HIP: set_rd_crystal: rd_crystal_order %d outside 1 .. %d (0 = off)", order, kRdcMaxOrder);
+    if (order == c->rdc_order) return 0;  // nothing to change: no partial sum is thrown away
+    HIPCHK(hipSetDevice(c->device));
+    if (c->have_atoms && flush_moves(c)) return -1;  // keep the order of the caller's operations
+    if (order > 0) {
+        const size_t ntile = c->max_npad / 64;
+        if (alloc_zero_params(c)) return -1;
+        if (!c->d_rdcpart) {
+            HIPCHK(c->d_rdcpart.alloc(ntile * ntile));
+            HIPCHK(c->d_rdclrcpart.alloc(ntile * ntile));
+        }
+    }
+    c->rdc_order = order;
+    c->rdc_part_valid = c->rdc_static_valid = false;
+    c->pair_part_valid = false;  // the Lennard-Jones kernels change between real and zero parameters
+    c->lrc_valid = false;
+    c->all_dirty = true;
     ++c->config_rev;
     return 0;
 }
@@ -1356,6 +1403,7 @@ static bool edits_supported(const mpmc_hip_ctx *c) {
     if (!c->have_atoms || c->all_dirty || !c->opt.incremental || !c->opt.incremental_pairs || !c->opt.pair_coef) return false;
     if (c->disp_on) return false;  // disp_expansion: no device-side insert / remove (the caller uploads again)
     if (c->at_on) return false;    // axilrod_teller: the same
+    if (c->rdc_order) return false;  // rd_crystal: the same
     // Gauss-Seidel: only with the chain kernel, whose view is rebuilt from the order the caller states afterwards
     if (!P.rd_only && P.polarization && (P.polar_gs || P.polar_gs_ranked) && !gs_order_mode(c)) return false;
     return true;
@@ -1478,7 +1526,7 @@ extern "C" int mpmc_hip_insert_molecule(mpmc_hip_ctx *c, int count, const double
         const int npad = round_up(c->n, 128);
         if (npad != c->npad) {  // the tile grids of the pair / field / LRC partials change shape
             c->npad = npad;
-            c->pair_part_valid = c->field_part_valid = c->disp_part_valid = false;
+            c->pair_part_valid = c->field_part_valid = c->disp_part_valid = c->rdc_part_valid = false;
             c->lrc_valid = false;
         }
     }
@@ -1914,7 +1962,8 @@ __global__ __launch_bounds__(64) void publish_side_kernel(double *__restrict__ d
     if (threadIdx.x == 0) h_res2[n] = seq;
 }
 constexpr unsigned kSideSlots = (1u << R_RD_PAIR) | (1u << R_ES_REAL) | (1u << R_ES_INTRA) | (1u << 3) | (1u << R_LRC) |
-                                (1u << R_RECIP) | (1u << R_SELF) | (1u << R_DISP) | (1u << R_DISP_LRC) | (1u << R_AT);
+                                (1u << R_RECIP) | (1u << R_SELF) | (1u << R_DISP) | (1u << R_DISP_LRC) | (1u << R_AT) |
+                                (1u << R_RDC_SELF);
 
 // LJ / real-space Ewald tile kernel (graph slot GS_PAIR).  Tile partials persist: after a single-molecule
 // move only the tiles of the moved atoms' blocks are recomputed.
@@ -2029,6 +2078,60 @@ static int launch_disp(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hip
     return 0;
 }
 
+// rd_crystal: cutoff_c and the squared-distance threshold that decides exactly as `sqrt(r2) > cutoff_c` does
+static RdcParams rdc_params(const mpmc_hip_ctx *c) {
+    RdcParams rp;
+    rp.order = c->rdc_order;
+    rp.fh_order = c->par.feynman_hibbs ? c->par.feynman_hibbs_order : 0;
+    rp.temperature = c->par.temperature;
+    rp.cutoff_c = 2.0 * c->cutoff * ((double)c->rdc_order - 0.5);  // lj.c:176
+    double x = rp.cutoff_c * rp.cutoff_c;
+    while (std::sqrt(x) > rp.cutoff_c) x = std::nextafter(x, 0.0);
+    while (std::sqrt(std::nextafter(x, INFINITY)) <= rp.cutoff_c) x = std::nextafter(x, INFINITY);
+    rp.r2max = x;
+    return rp;
+}
+
+// rd_crystal: the image-sum tile kernel behind the pair kernel (same stream, same dirty blocks, same move); the self part
+// and the long-range correction at cutoff_c when the parameters, the box or rd_lrc changed.  `a` carries zero epsilon /
+// sigma in this mode: these kernels get the real ones.
+static int launch_rdc(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipStream_t sb) {
+    const int ntile = c->npad / 64;
+    DevAtoms lj = a;
+    lj.eps = c->d_eps;
+    lj.sig = c->d_sig;
+    const RdcParams rp = rdc_params(c);
+    const int want_lrc = c->par.rd_lrc ? 1 : 0;
+    if (!c->rdc_static_valid || c->rdc_static_lrc != want_lrc) {
+        ScopedTimer t(c, T_OTHER, sb);
+        hipLaunchKernelGGL(rdc_self_kernel, dim3(1), dim3(kRdcSelfThreads), 0, sb, lj, bx, rp, c->d_res + R_RDC_SELF);
+        if (want_lrc) {
+            DevBox bc = bx;
+            bc.cutoff = rp.cutoff_c;  // lj_lrc_corr / lj_lrc_self at the crystal cutoff (lj.c:188, :273)
+            DirtyBlocks all;
+            memset(&all, 0, sizeof(all));
+            hipLaunchKernelGGL(lj_lrc_kernel, dim3(ntile, ntile), dim3(64 * kLrcWaves), 0, sb, lj, bc, all, c->d_rdclrcpart);
+            hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(kReduceThreads), 0, sb, c->d_rdclrcpart, ntile * ntile, 1,
+                               c->d_res + R_DISP_LRC);
+        }
+        HIPCHK(hipGetLastError());
+        c->rdc_static_valid = true;
+        c->rdc_static_lrc = want_lrc;
+    }
+    if (!want_lrc) c->call.res_zero_mask |= 1u << R_DISP_LRC;
+    DirtyBlocks sel = c->call.dirty_blocks;
+    if (!c->rdc_part_valid) sel.n = 0;
+    if (c->rdc_part_valid && c->dirty_atoms.empty()) return 0;  // nothing moved: d_res[R_DISP] is still that sum
+    ScopedTimer t(c, T_PAIR, sb);
+    hipLaunchKernelGGL(rdc_tile_kernel, dim3(ntile, sel.n > 0 ? sel.n : ntile), dim3(64 * kRdcWaves), 0, sb, lj, bx, rp, sel,
+                       c->d_rdcpart, c->call.disp_moves);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(kReduceThreads), 0, sb, c->d_rdcpart, ntile * ntile, 1,
+                       c->d_res + R_DISP);
+    HIPCHK(hipGetLastError());
+    c->rdc_part_valid = true;
+    return 0;
+}
+
 // axilrod_teller: the block-triple kernel behind the pair (and dispersion) launch -- same stream, same dirty blocks, same
 // move -- and the fixed-order sum of all its partials (an order that is a function of the block count only).
 static int launch_at(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipStream_t sb) {
@@ -2085,7 +2188,7 @@ static bool blocks_of(const std::vector<int> &atoms, DirtyBlocks &out) {
 static void collect_dirty_blocks(mpmc_hip_ctx *c) {
     DirtyBlocks &d = c->call.dirty_blocks;
     if (c->all_dirty || !c->opt.incremental_pairs || !blocks_of(c->dirty_atoms, d)) {
-        c->pair_part_valid = c->field_part_valid = c->disp_part_valid = c->at_part_valid = false;
+        c->pair_part_valid = c->field_part_valid = c->disp_part_valid = c->at_part_valid = c->rdc_part_valid = false;
         memset(&d, 0, sizeof(d));
     }
     c->call.pair_part_valid_before = c->pair_part_valid;  // false whenever the dirty-block list cannot be trusted
@@ -2214,8 +2317,12 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
         // ---- disp_expansion: exp repulsion + damped C6 / C8 / C10 over ALL pairs, and its long-range correction
         if (c->disp_on) {
             if (launch_disp(c, a, bx, sb)) return -1;
+            k.res_zero_mask |= 1u << R_RDC_SELF;
+        } else if (c->rdc_order) {
+            // ---- rd_crystal: Lennard-Jones over the lattice images, its self part and its long-range correction
+            if (launch_rdc(c, a, bx, sb)) return -1;
         } else {
-            k.res_zero_mask |= (1u << R_DISP) | (1u << R_DISP_LRC);
+            k.res_zero_mask |= (1u << R_DISP) | (1u << R_DISP_LRC) | (1u << R_RDC_SELF);
         }
         // ---- axilrod_teller: the triple-dipole sum over ALL triples that are not on one molecule
         if (c->at_on) {
@@ -2304,7 +2411,7 @@ static bool graph_eligible(mpmc_hip_ctx *c) {
     const mpmc_hip_params &P = c->par;
     const SweepView &v = c->view[0];
     if (!c->opt.graph || is_timed_call(c) || !c->opt.incremental || !c->opt.incremental_pairs ||
-        !c->opt.pair_coef || c->disp_on || c->at_on)
+        !c->opt.pair_coef || c->disp_on || c->at_on || c->rdc_order)
         return false;
     if (P.rd_only || !P.polarization || P.polar_zodid || P.polar_gs || P.polar_gs_ranked || P.polar_precision != 0.0 ||
         P.polar_max_iter <= 0)
@@ -2403,6 +2510,9 @@ extern "C" int mpmc_hip_energy_begin(mpmc_hip_ctx *c) {
     if (c->order_stale && gs_order_mode(c))
         return fail("MPMC_HIP: energy: Gauss-Seidel after insert_molecule / remove_molecule needs the sweep order of the "
                     "new configuration (mpmc_hip_set_sweep_order)");
+    if (c->disp_on && c->rdc_order)
+        return fail("MPMC_HIP: energy: rd_crystal with disp_expansion is not implemented (the reference's disp_expansion() "
+                    "ignores rd_crystal)");
     HIPCHK(hipSetDevice(c->device));
     if (c->resident_off && c->resident_backoff > 0 && (long)c->energy_calls >= c->resident_retry_at)
         c->resident_off = false;  // (one more attempt at the one-launch solve; a give-up doubles the interval)
@@ -2556,7 +2666,10 @@ extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
     double r[R_COUNT];
     for (int k = 0; k < R_COUNT; ++k) r[k] = (c->call.split && ((kSideSlots >> k) & 1u)) ? c->h_res2[k] : c->h_res[k];
     // (disp_expansion: the LJ kernels ran on zero parameters, both of their slots are exactly 0)
-    const double rd = c->disp_on ? (r[R_RD_PAIR] + r[R_LRC]) + (r[R_DISP] + r[R_DISP_LRC]) : r[R_RD_PAIR] + r[R_LRC];
+    // (rd_crystal: the same, with the image sum, its self part and the correction at cutoff_c behind them)
+    const double rd = c->disp_on     ? (r[R_RD_PAIR] + r[R_LRC]) + (r[R_DISP] + r[R_DISP_LRC])
+                      : c->rdc_order ? (r[R_RD_PAIR] + r[R_LRC]) + ((r[R_DISP] + r[R_RDC_SELF]) + r[R_DISP_LRC])
+                                     : r[R_RD_PAIR] + r[R_LRC];
     const double real = r[R_ES_REAL] - r[R_ES_INTRA];
     const bool ewald = !P.rd_only && !P.wolf;
     const double recip = ewald ? r[R_RECIP] * (4.0 * kPI / c->volume) : 0.0;  // coulombic.c:92

@@ -17,6 +17,7 @@ EXPORTS = [
     "mpmc_hip_destroy", "mpmc_hip_set_option", "mpmc_hip_default_params", "mpmc_hip_set_params", "mpmc_hip_set_box",
     "mpmc_hip_scale_box",
     "mpmc_hip_upload", "mpmc_hip_set_dispersion", "mpmc_hip_set_axilrod_teller", "mpmc_hip_get_three_body_energy",
+    "mpmc_hip_set_rd_crystal",
     "mpmc_hip_update_atoms", "mpmc_hip_insert_molecule", "mpmc_hip_remove_molecule",
     "mpmc_hip_slot_count", "mpmc_hip_set_sweep_order", "mpmc_hip_energy", "mpmc_hip_energy_begin", "mpmc_hip_energy_end",
     "mpmc_hip_download_dipoles",
@@ -113,6 +114,7 @@ class DispParams(C.Structure):
 PARAM_NAMES = [f[0] for f in Params._fields_]
 DISP_NAMES = [f[0] for f in DispParams._fields_]
 AT_NAMES = ["axilrod_teller", "midzuno_kihara_approx"]  # mpmc_hip_set_axilrod_teller (reference keywords)
+RDC_NAMES = ["rd_crystal", "rd_crystal_order"]  # mpmc_hip_set_rd_crystal (reference keywords)
 AT_ALPHA_AU = 6.7483345  # A^3 -> Bohr^3, as the reference writes it (axilrod_teller.cpp:115)
 
 _lib = None
@@ -146,6 +148,7 @@ def load():
     lib.mpmc_hip_set_dispersion.argtypes = [vp, C.POINTER(DispParams), C.c_int, vp, vp, vp]
     lib.mpmc_hip_set_axilrod_teller.argtypes = [vp, C.c_int, C.c_int, vp]
     lib.mpmc_hip_get_three_body_energy.argtypes = [vp, dp]
+    lib.mpmc_hip_set_rd_crystal.argtypes = [vp, C.c_int]
     lib.mpmc_hip_update_atoms.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     lib.mpmc_hip_insert_molecule.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
     lib.mpmc_hip_remove_molecule.argtypes = [vp, C.c_int, C.c_int]
@@ -191,6 +194,8 @@ def make_params(**kw):
             continue  # mpmc_hip_set_dispersion's record (Engine.load_system)
         if k in AT_NAMES:
             continue  # mpmc_hip_set_axilrod_teller's arguments (Engine.load_system)
+        if k in RDC_NAMES:
+            continue  # mpmc_hip_set_rd_crystal's argument (Engine.load_system)
         if k not in PARAM_NAMES:
             raise KeyError(k)
         setattr(p, k, v)
@@ -286,6 +291,11 @@ class Engine:
             raise ValueError("c9 (c6, alpha) must have one entry per uploaded atom")
         _chk(self.lib.mpmc_hip_set_axilrod_teller(self.ctx, 1, self.n, c9.ctypes.data))
 
+    def set_rd_crystal(self, order):
+        """Lennard-Jones over lattice images (mpmc_hip_set_rd_crystal): order = rd_crystal_order, 1 .. 4; 0 switches the
+        mode off.  A context setting: it persists across uploads."""
+        _chk(self.lib.mpmc_hip_set_rd_crystal(self.ctx, int(order)))
+
     def three_body_energy(self):
         """observables->three_body_energy of the last completed energy(); 0 while the term is off."""
         v = C.c_double(0.0)
@@ -294,8 +304,10 @@ class Engine:
 
     def load_system(self, system, params):
         """Convenience: params (incl. optional pbc_cutoff) + box + atoms (+ the dispersion record when the flags carry
-        disp_expansion, + the three-body coefficients when they carry axilrod_teller)."""
+        disp_expansion, + the three-body coefficients when they carry axilrod_teller).  rd_crystal / rd_crystal_order among
+        the flags switch the image sum on (order 1 when only rd_crystal is given); without them it is switched off."""
         self.set_params(**params)
+        self.set_rd_crystal(int(params.get("rd_crystal_order", 1)) if params.get("rd_crystal") else 0)
         self.set_box(system["basis"], params.get("pbc_cutoff", 0.0))
         self.upload(system)
         if params.get("disp_expansion"):

@@ -85,6 +85,9 @@ def load():
     lib.host_set_c9.restype = None
     lib.host_get_three_body_energy.argtypes = [vp]
     lib.host_get_three_body_energy.restype = C.c_double
+    lib.host_get_rdc_flags.argtypes = [vp, vp]
+    lib.host_get_rdc_flags.restype = None
+    lib.host_read_frame.argtypes = [vp, C.c_char_p, C.c_int]
     lib.host_unsupported.argtypes = [vp]
     lib.host_unsupported.restype = C.c_char_p
     lib.volume_change.argtypes = [vp]
@@ -100,7 +103,7 @@ def config_text(flags, extra=None):
     onoff = {"rd_only", "rd_lrc", "feynman_hibbs", "polarization", "polar_gs", "polar_gs_ranked", "polar_sor",
              "polar_esor", "polar_palmo", "polar_rrms", "polar_zodid", "polar_wolf", "polar_ewald", "wolf",
              "disp_expansion", "damp_dispersion", "extrapolate_disp_coeffs", "schmidt_mixing", "axilrod_teller",
-             "midzuno_kihara_approx"}
+             "midzuno_kihara_approx", "rd_crystal", "read_pqr_box", "calc_pressure"}
     lines = []
     for k, v in flags.items():
         if k in onoff:

@@ -27,6 +27,7 @@ int host_apply_config(system_t *system, const char *text) {
     if (system->ensemble == ENSEMBLE_UVT && !system->user_fugacities) system->fugacity = system->pressure;
     if (system->ensemble == ENSEMBLE_UVT && !(system->fugacity > 0.0)) return 1;
     if (system->ensemble == ENSEMBLE_NPT && !(system->pressure > 0.0)) return 1; /* check_input.c:673-678 */
+    if (system->rd_crystal && system->rd_crystal_order <= 0) return 1;            /* check_input.c:1258-1263 */
     return 0;
 }
 
@@ -245,6 +246,22 @@ void host_set_c9(system_t *system, const double *c9) {
         for (atom_t *a = m->atoms; a; a = a->next, i++) a->c9 = c9[i];
 }
 double host_get_three_body_energy(system_t *system) { return system->observables->three_body_energy; }
+/* ---- rd_crystal and ensemble replay ---------------------------------------------------------------------------- */
+void host_get_rdc_flags(system_t *system, int out[2]) {
+    out[0] = system->rd_crystal;
+    out[1] = system->rd_crystal_order;
+}
+/* frame `index` (from 0) of the PQR trajectory `path` becomes the system's configuration, read the way
+ * replay_trajectory() reads it: every frame in front of it is read (and freed) first, so the box and the cutoff are
+ * what a replay would hold at that frame.  Returns read_frame()'s answer for that frame (1: the trajectory is shorter). */
+int host_read_frame(system_t *system, const char *path, int index) {
+    FILE *fp = fopen(path, "r");
+    if (!fp) return -1;
+    int rc = 0;
+    for (int k = 0; k <= index && rc == 0; k++) rc = read_frame(fp, system);
+    fclose(fp);
+    return rc;
+}
 /* the reason energy() would refuse this system, or NULL */
 const char *host_unsupported(system_t *system) { return energy_hip_unsupported(system); }
 

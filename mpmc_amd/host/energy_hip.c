@@ -48,6 +48,7 @@ typedef struct shim_state {
     int device;   /* -1: choose (rank % device count) */
     int capacity; /* atoms the context was created for */
     int uploaded; /* a configuration is resident */
+    int rdc_order; /* rd_crystal_order as sent with that upload (0: rd_crystal off) */
     int failed;   /* device / ABI failure of the last call */
     mpmc_hip_params params; /* as last sent */
     /* host image of the device, by DEVICE SLOT (the engine keeps its own atom order once molecules are inserted
@@ -234,13 +235,15 @@ static const char *unsupported(const system_t *s) {
     if (s->disp_expansion && (s->waldmanhagler || s->halgren_mixing || s->cdvdw_9th_repulsion))
         return "disp_expansion with waldmanhagler / halgren_mixing / cdvdw_9th_repulsion is not on the device";
     if (s->polarvdw || s->cdvdw_sig_repulsion) return "coupled-dipole van der Waals is not on the device";
-    if (s->rd_crystal) return "rd_crystal is not on the device";
     if (s->cavity_autoreject_absolute) return "cavity_autoreject_absolute needs the pair list";
     if (s->polarization && !s->polar_iterative) return "iterative Thole solver only (polar_iterative on)";
     if (s->polarization && s->damp_type != DAMPING_EXPONENTIAL) return "exponential Thole damping only";
     if (s->polarization && (s->polar_ewald_full || s->polar_wolf_full)) return "polar_ewald_full / polar_wolf_full are not on the device";
     if (s->ensemble == ENSEMBLE_NVE) return "ensemble nve is not supported";
 #endif
+    /* rd_crystal (Lennard-Jones over lattice images) is on the device up to order 4; disp_expansion() ignores it */
+    if (s->rd_crystal && s->disp_expansion) return "rd_crystal with disp_expansion is not on the device";
+    if (s->rd_crystal && s->rd_crystal_order > 4) return "rd_crystal_order above 4 is not on the device";
     /* disp_expansion: the default and the Schmidt mixing of the exponent are on the device; the rest is refused by name */
     if (s->disp_expansion_mbvdw) return "disp_expansion_mbvdw (many-body van der Waals) is not on the device";
     if (s->disp_expansion && s->gilbert_smith_mixing) return "gilbert_smith_mixing is not on the device";
@@ -359,6 +362,8 @@ static int full_upload(shim_state *st, system_t *system) {
     if (!rc) rc = mpmc_hip_upload(st->ctx, n, st->x, st->y, st->z, st->q, st->alpha, st->eps, st->sig, st->mass, mol, fz);
     free(mol); free(fz);
     if (rc) return hip_fail("upload");
+    st->rdc_order = system->rd_crystal ? system->rd_crystal_order : 0;
+    if (mpmc_hip_set_rd_crystal(st->ctx, st->rdc_order)) return hip_fail("set_rd_crystal");
     fill_disp_params(system, &st->disp);
     /* (an upload leaves the context on Lennard-Jones: nothing to say unless the PHAHST potential is asked for) */
     if (st->disp.disp_expansion && mpmc_hip_set_dispersion(st->ctx, &st->disp, n, st->c6, st->c8, st->c10))
@@ -654,6 +659,7 @@ int energy_hip_begin(system_t *system) {
         mpmc_hip_disp_params dnow;
         fill_disp_params(system, &dnow);
         if (memcmp(&dnow, &st->disp, sizeof(dnow))) need_upload = 1;
+        if ((system->rd_crystal ? system->rd_crystal_order : 0) != st->rdc_order) need_upload = 1;
     }
     if (!need_upload && scale_box) {
         const int rc = apply_volume_notes(st, system);

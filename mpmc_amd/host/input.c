@@ -102,8 +102,11 @@ int do_command(system_t *system, char **token) {
             system->ensemble = ENSEMBLE_NPT;
         else if (!strcasecmp(v, "total_energy"))
             system->ensemble = ENSEMBLE_TE;
+        else if (!strcasecmp(v, "replay"))
+            system->ensemble = ENSEMBLE_REPLAY;
         else {
-            error("INPUT: only `ensemble nvt`, `uvt`, `npt` and `total_energy` are implemented by this host layer\n");
+            error("INPUT: only `ensemble nvt`, `uvt`, `npt`, `total_energy` and `replay` are implemented by this host "
+                  "layer\n");
             return 1;
         }
         return 0;
@@ -153,6 +156,10 @@ int do_command(system_t *system, char **token) {
     FLAG("schmidt_mixing", schmidt_mixing);
     FLAG("axilrod_teller", axilrod_teller); /* input.c:992-1013 */
     FLAG("midzuno_kihara_approx", midzuno_kihara_approx);
+    FLAG("rd_crystal", rd_crystal); /* input.c:814-826 */
+    INT("rd_crystal_order", rd_crystal_order);
+    FLAG("read_pqr_box", read_pqr_box_on); /* input.c:1448-1455 */
+    FLAG("calc_pressure", calc_pressure);  /* input.c:575-582; refused by name in replay (check_system) */
     FLAG("disp_expansion_mbvdw", disp_expansion_mbvdw); /* these four are refused by energy_hip.c, each by name */
     FLAG("gilbert_smith_mixing", gilbert_smith_mixing);
     FLAG("bohm_ahlrichs_mixing", bohm_ahlrichs_mixing);
@@ -198,6 +205,7 @@ int do_command(system_t *system, char **token) {
     FLAG("hip", hip);
     TEXT("job_name", job_name);
     TEXT("pqr_input", pqr_input);
+    TEXT("traj_input", traj_input);
     TEXT("pqr_output", pqr_output);
     TEXT("energy_output", energy_output);
     if (!strcasecmp(k, "basis1") || !strcasecmp(k, "basis2") || !strcasecmp(k, "basis3")) {
@@ -358,9 +366,25 @@ static int check_system(system_t *system) {
         return -1;
     }
     if (system->ensemble != ENSEMBLE_NVT && system->ensemble != ENSEMBLE_TE && system->ensemble != ENSEMBLE_UVT &&
-        system->ensemble != ENSEMBLE_NPT) {
-        error("INPUT: ensemble must be nvt, uvt, npt or total_energy\n");
+        system->ensemble != ENSEMBLE_NPT && system->ensemble != ENSEMBLE_REPLAY) {
+        error("INPUT: ensemble must be nvt, uvt, npt, total_energy or replay\n");
         return -1;
+    }
+    if (system->ensemble == ENSEMBLE_REPLAY && !system->traj_input[0]) {
+        error("INPUT: ensemble replay needs traj_input\n");
+        return -1;
+    }
+    if (system->ensemble == ENSEMBLE_REPLAY && system->calc_pressure) {
+        error("INPUT: calc_pressure in ensemble replay is not implemented by this host layer\n");
+        return -1;
+    }
+    if (system->rd_crystal) { /* check_input.c:1258-1267 */
+        if (system->rd_crystal_order <= 0) {
+            error("INPUT: rd_crystal_order must be a positive integer\n");
+            return -1;
+        }
+        snprintf(linebuf, MAXLINE, "INPUT: rd crystal order set to %d.\n", system->rd_crystal_order);
+        output(linebuf);
     }
     if (system->ensemble == ENSEMBLE_NPT && !(system->pressure > 0.0)) { /* check_input.c:673-678 */
         error("INPUT: invalid pressure set for NPT\n");
@@ -400,22 +424,35 @@ system_t *setup_system(char *input_file) {
     system_t *system = read_config(input_file);
     if (!system) return NULL;
     if (!system->pqr_input[0]) snprintf(system->pqr_input, MAXLINE, "%s.initial.pqr", system->job_name);
-    /* pqr_input is relative to the directory of the input file, like running the reference in that directory */
+    /* pqr_input / traj_input are relative to the directory of the input file, like running the reference in that directory;
+     * ensemble replay takes its first configuration from the trajectory (input.c:1762-1768) */
+    const int replay = (system->ensemble == ENSEMBLE_REPLAY);
+    char *name = replay ? system->traj_input : system->pqr_input;
     char path[2 * MAXLINE];
     const char *slash = strrchr(input_file, '/');
-    if (slash && system->pqr_input[0] != '/')
-        snprintf(path, sizeof(path), "%.*s/%s", (int)(slash - input_file), input_file, system->pqr_input);
+    if (slash && name[0] != '/')
+        snprintf(path, sizeof(path), "%.*s/%s", (int)(slash - input_file), input_file, name);
     else
-        snprintf(path, sizeof(path), "%s", system->pqr_input);
+        snprintf(path, sizeof(path), "%s", name);
     FILE *fp = fopen(path, "r");
     if (!fp) {
         char msg[3 * MAXLINE];
-        snprintf(msg, sizeof(msg), "INPUT: could not open pqr_input %s\n", path);
+        snprintf(msg, sizeof(msg), "INPUT: could not open %s %s\n", replay ? "traj_input" : "pqr_input", path);
         error(msg);
         free_system(system);
         return NULL;
     }
-    system->molecules = read_molecules(fp, system);
+    if (replay) {
+        if (strlen(path) >= MAXLINE) {
+            error("INPUT: traj_input path too long\n");
+            fclose(fp);
+            free_system(system);
+            return NULL;
+        }
+        memmove(system->traj_input, path, strlen(path) + 1); /* replay_trajectory() opens it again */
+        if (read_frame(fp, system) != 0) system->molecules = NULL;
+    } else
+        system->molecules = read_molecules(fp, system);
     fclose(fp);
     if (!system->molecules) {
         error("INPUT: error reading in input molecules\n");

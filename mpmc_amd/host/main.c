@@ -1,5 +1,6 @@
 /* main.c -- `mpmc_hip <config>`: the reference's entry point (src/main/main.c:34-304) reduced to the
- * two modes this layer supports: `ensemble nvt` (mc()) and `ensemble total_energy` (single point). */
+ * modes this layer supports: the Monte Carlo ensembles (mc()), `ensemble total_energy` (single point) and
+ * `ensemble replay` (replay_trajectory()). */
 #include <stdlib.h>
 #include <string.h>
 #include <sys/time.h>
@@ -31,6 +32,8 @@ int main(int argc, char **argv) {
                  "OUTPUT: repulsion/dispersion energy = %.5f K\nOUTPUT: polarization energy = %.5f K\n",
                  e, o->coulombic_energy, o->rd_energy, o->polarization_energy);
         output(linebuf);
+    } else if (system->ensemble == ENSEMBLE_REPLAY) {
+        rc = replay_trajectory(system);
     } else {
         struct timeval t0, t1;
         gettimeofday(&t0, NULL);

@@ -434,7 +434,7 @@ void boltzmann_factor(system_t *system, double initial_energy, double final_ener
 }
 
 /* reference write_observables(), src/io/output.c:988-1006 */
-static void write_observables(FILE *fp, system_t *system, observables_t *o, double core_temp) {
+void write_observables(FILE *fp, system_t *system, observables_t *o, double core_temp) {
     fprintf(fp, "%d %f %f %f %f %f %f %f %f %f %f %f\n", system->step, o->energy, o->coulombic_energy, o->rd_energy,
             o->polarization_energy, o->vdw_energy, o->kinetic_energy, o->temperature, o->N, o->spin_ratio, o->volume,
             core_temp);

@@ -115,6 +115,12 @@ typedef struct _system {
     int disp_expansion_mbvdw, gilbert_smith_mixing, bohm_ahlrichs_mixing, wilson_popelier_mixing;
     /* the triple-dipole three-body term (structs.h:422); midzuno_kihara_approx: c9 = 3/4 alpha c6 per atom */
     int axilrod_teller, midzuno_kihara_approx;
+    /* Lennard-Jones over lattice images (structs.h, lj.c:109-276): sent with mpmc_hip_set_rd_crystal() */
+    int rd_crystal, rd_crystal_order;
+    /* ensemble replay (replay.c): the trajectory, whether its REMARK BOX lines set the box, and calc_pressure, which is
+     * read so that replay can refuse it by name */
+    int read_pqr_box_on, calc_pressure;
+    char traj_input[MAXLINE];
     int iter_success; /* the reference's convergence-FAILURE flag */
     int natoms;
     char job_name[MAXLINE], pqr_input[MAXLINE], energy_output[MAXLINE], pqr_output[MAXLINE];
@@ -154,6 +160,12 @@ void update_com(molecule_t *molecules);
 
 /* Monte Carlo (reference src/mc/mc.c, mc_moves.c, checkpoint.c, src/mersenne/mersenne.cpp) */
 int mc(system_t *system);
+/* ensemble replay (reference src/mc/replay.c): energy() of every frame of system->traj_input, one observables line each.
+ * read_frame(): the next frame's molecules (and box, under read_pqr_box) into `system`, whose old molecules it frees;
+ * 0 = a frame was read, 1 = end of the trajectory, -1 = error. */
+int replay_trajectory(system_t *system);
+int read_frame(FILE *fp, system_t *system);
+void write_observables(FILE *fp, system_t *system, observables_t *o, double core_temp);
 void checkpoint(system_t *system);
 void restore(system_t *system);
 void make_move(system_t *system);
