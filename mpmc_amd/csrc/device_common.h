@@ -65,8 +65,6 @@ struct MoveTargets {  // where a kernel that carries the move writes it (what ap
     double *px, *py, *pz;
 };
 
-
-
 struct DevAtoms {
     const double *x, *y, *z;
     const double *q, *alpha, *eps, *sig, *molmass;

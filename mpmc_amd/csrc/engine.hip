@@ -305,7 +305,7 @@ struct CallState {
     bool moves_in_pair = false;   // ... or inside the pair kernel's launch (steps without polarization)
     bool side_carry = false;      // ... and the side stream's pair kernel carries the same move itself (side_moves):
     MoveList side_moves;          //     no fork event between the two streams in a steady-state polarizable step
-    MoveList disp_moves;          // the move the pair kernel's launch carried: the disp_expansion tile kernel behind it takes it too
+    MoveList pair_moves;          // the move the pair kernel's launch carried: the dense tile kernels behind it take it too
     MoveList side_apply;          // a move the main stream applied with apply_moves_kernel: the side stream applies it
     bool side_applied = false;    //     too (a launch of its own, in front of its first kernel) instead of waiting for an event
     bool coef_job_valid = false;  // setup_view() left the coefficient update of this step for launch_field()
@@ -326,6 +326,13 @@ struct CallState {
     bool spec_rank = false;       // enqueued speculatively (polar_gs_ranked)
     bool timed = false;           // events were recorded
     int iterations = 0, iter_success = 0;
+};
+
+// A sum kept as per-tile partials and, added up in a fixed order, in a slot of d_res (kernels_tile.h).  valid: both are those
+// of the current parameters, box and tile grid and of the configuration before the pending moves.
+struct TileSum {
+    DevBuf<double> part;
+    bool valid = false;
 };
 
 struct mpmc_hip_ctx {
@@ -386,31 +393,26 @@ struct mpmc_hip_ctx {
     DevBuf<double> d_fieldpart;     // [nchunk][3][npad]
     bool field_part_valid = false;  // same for d_fieldpart (real-space static field)
     int field_key = -1;             // mode / chunking the resident field partials were made with
-    DevBuf<double> d_lrcpart;       // tile partials of the (cached) long-range correction
+    TileSum lrc;                    // [ntile*ntile] the (cached) long-range correction, R_LRC
     // ---- disp_expansion (PHAHST, mpmc_hip_set_dispersion): d_eps / d_sig then hold the exponent b and the range rho, the
     // LJ kernels are handed d_zero in their place (every LJ pair and the LJ long-range correction give exactly 0)
     bool disp_on = false;
     DispParams disp_par = {0, 0, 0};
     DevBuf<double> d_c6, d_c8, d_c10, d_zero;
-    DevBuf<double> d_disppart;      // [ntile*ntile] tile partials of the dense pair sum
-    bool disp_part_valid = false;   // ... of the configuration before the pending moves
-    DevBuf<double> d_displrcpart;   // [ntile*ntile] tile partials of its long-range correction
-    bool disp_lrc_valid = false;    // d_res[R_DISP_LRC] is that of the current parameters, cutoff and volume
+    TileSum disp;                   // [ntile*ntile] the dense pair sum, R_DISP
+    TileSum disp_lrc;               // [ntile*ntile] its long-range correction, R_DISP_LRC: parameters, cutoff and volume only
     // ---- axilrod_teller (mpmc_hip_set_axilrod_teller): the triple-dipole term, kernels_at.h
     bool at_on = false;
     DevBuf<double> d_at_a, d_at_g;  // per atom: alpha * 6.7483345 and 1 / (c9 / a^3)
-    DevBuf<double> d_atpart;        // [at_unit_count(ntile)][kAtSplit] block-triple partials
-    bool at_part_valid = false;     // ... of the configuration (and box) before the pending moves
+    TileSum at;                     // [at_unit_count(ntile)][kAtSplit] block-triple partials, R_AT
     double three_body = 0.0;        // the term of the last completed energy_end() (0 outside the mode)
     // ---- rd_crystal (mpmc_hip_set_rd_crystal): Lennard-Jones over lattice images, kernels_crystal.h.  A context setting:
     // it carries no per-atom data and persists across uploads.  The LJ kernels are handed d_zero, as under disp_expansion.
     int rdc_order = 0;              // 0 = off, 1 .. kRdcMaxOrder
-    DevBuf<double> d_rdcpart;       // [ntile*ntile] tile partials of the image sum
-    bool rdc_part_valid = false;    // ... of the configuration (and box) before the pending moves
-    DevBuf<double> d_rdclrcpart;    // [ntile*ntile] tile partials of the long-range correction at cutoff_c
-    bool rdc_static_valid = false;  // d_res[R_RDC_SELF] / [R_DISP_LRC] are those of the current parameters, box and rd_lrc
+    TileSum rdc;                    // [ntile*ntile] the image sum, R_DISP
+    TileSum rdc_static;             // [ntile*ntile] the long-range correction at cutoff_c, R_DISP_LRC; valid covers the self
+                                    // part (R_RDC_SELF) too: both are those of the current parameters, box and rd_lrc
     int rdc_static_lrc = -1;        // the rd_lrc they were made under
-    bool lrc_valid = false;
     double lrc_cached = 0.0;
     DevBuf<KVec> d_kvec;
     int nk = 0;
@@ -826,7 +828,7 @@ extern "C" int mpmc_hip_create(mpmc_hip_ctx **out, int device, int max_atoms) {
     }
     const size_t ntile = np / 64;
     HIPCHK(c->d_pairpart.alloc(ntile * ntile * kPairChannels));
-    HIPCHK(c->d_lrcpart.alloc(ntile * ntile));
+    HIPCHK(c->lrc.part.alloc(ntile * ntile));
     HIPCHK(c->d_rankpart.alloc(ntile * ntile));
     const size_t nchunk_max = std::max<size_t>(1, np / 64) + 16;  // + k-chunk slots of the Ewald field
     HIPCHK(c->d_fieldpart.alloc(nchunk_max * 3 * np));
@@ -876,6 +878,24 @@ extern "C" void mpmc_hip_destroy(mpmc_hip_ctx *c) {
     delete c;
 }
 
+// ---- What an event makes stale; DESIGN.md ("Tile passes") has the table and the reasons.  The mode setters
+// (set_dispersion, set_axilrod_teller, set_rd_crystal) drop their own term's sums where they stand.
+// all_dirty, or the moved blocks cannot be listed: every sum over positions (the static ones read no coordinate)
+static void positions_unknown(mpmc_hip_ctx *c) {
+    c->pair_part_valid = c->field_part_valid = c->disp.valid = c->rdc.valid = c->at.valid = false;
+}
+// set_params(), or insert_molecule() grew the tile grid.  Not c->at: no parameter enters the three-body term, and the grid
+// cannot grow in its mode (edits_supported()); a full triple pass after every set_params() would be wasted.
+static void params_or_grid_changed(mpmc_hip_ctx *c) {
+    c->pair_part_valid = c->field_part_valid = c->disp.valid = c->rdc.valid = false;
+}
+// apply_box(): the sums of parameters, cutoff and volume (those over positions go with all_dirty)
+static void box_changed(mpmc_hip_ctx *c) { c->lrc.valid = c->disp_lrc.valid = c->rdc_static.valid = false; }
+// upload(): everything per-atom (the pair / field partials go with all_dirty; the rd_crystal SETTING stays)
+static void atoms_replaced(mpmc_hip_ctx *c) {
+    c->lrc.valid = c->disp.valid = c->disp_lrc.valid = c->at.valid = c->rdc.valid = c->rdc_static.valid = false;
+}
+
 // reference src/io/check_input.c:318-470 (the subset that concerns this path)
 extern "C" int mpmc_hip_set_params(mpmc_hip_ctx *c, const mpmc_hip_params *p) {
     if (!c || !p) return fail("MPMC_HIP: set_params: null argument");
@@ -896,7 +916,7 @@ extern "C" int mpmc_hip_set_params(mpmc_hip_ctx *c, const mpmc_hip_params *p) {
         if (p->polar_gamma < 0.0) return fail("MPMC_HIP: invalid Pre-cond/SOR/ESOR gamma set");
     }
     if (p->polar_damp != c->par.polar_damp) c->all_dirty = true;
-    c->pair_part_valid = c->field_part_valid = c->disp_part_valid = c->rdc_part_valid = false;
+    params_or_grid_changed(c);
     ++c->config_rev;
     c->par = *p;
     c->have_params = true;
@@ -951,9 +971,7 @@ static int apply_box(mpmc_hip_ctx *c, const double basis[9], double pbc_cutoff) 
                     b[2][1] == 0.0);
     c->kvecf_valid = false;
     c->kvec_valid = false;
-    c->lrc_valid = false;
-    c->disp_lrc_valid = false;
-    c->rdc_static_valid = false;
+    box_changed(c);
     c->all_dirty = true;
     return 0;
 }
@@ -1029,12 +1047,9 @@ extern "C" int mpmc_hip_upload(mpmc_hip_ctx *c, int n, const double *x, const do
     c->self_valid = false;
     c->have_atoms = true;
     c->have_polar_result = false;
-    c->lrc_valid = false;
     c->disp_on = false;  // an upload brings Lennard-Jones parameters until set_dispersion() says otherwise
-    c->disp_part_valid = c->disp_lrc_valid = false;
     c->at_on = false;  // ... and no three-body term until set_axilrod_teller() says otherwise
-    c->at_part_valid = false;
-    c->rdc_part_valid = c->rdc_static_valid = false;  // (the rd_crystal setting itself stays: it holds no per-atom data)
+    atoms_replaced(c);
     c->rank_saved.clear();
     c->perm_ranked = false;
     c->pending.n = 0;
@@ -1089,9 +1104,9 @@ extern "C" int mpmc_hip_set_dispersion(mpmc_hip_ctx *c, const mpmc_hip_disp_para
     if (n != c->n) return fail("MPMC_HIP: set_dispersion: %d coefficients for the %d atoms of the upload", n, c->n);
     HIPCHK(hipSetDevice(c->device));
     if (flush_moves(c)) return -1;  // keep the order of the caller's operations
-    c->disp_part_valid = c->disp_lrc_valid = false;
-    c->pair_part_valid = false;
-    c->lrc_valid = false;
+    c->disp.valid = c->disp_lrc.valid = false;
+    c->pair_part_valid = false;  // the Lennard-Jones kernels change between real and zero parameters
+    c->lrc.valid = false;
     c->all_dirty = true;
     ++c->config_rev;
     if (!p->disp_expansion) {
@@ -1104,8 +1119,8 @@ extern "C" int mpmc_hip_set_dispersion(mpmc_hip_ctx *c, const mpmc_hip_disp_para
         HIPCHK(c->d_c6.alloc(nall));
         HIPCHK(c->d_c8.alloc(nall));
         HIPCHK(c->d_c10.alloc(nall));
-        HIPCHK(c->d_disppart.alloc(ntile * ntile));
-        HIPCHK(c->d_displrcpart.alloc(ntile * ntile));
+        HIPCHK(c->disp.part.alloc(ntile * ntile));
+        HIPCHK(c->disp_lrc.part.alloc(ntile * ntile));
     }
     if (alloc_zero_params(c)) return -1;
     std::vector<double> h6(nall, 0.0), h8(nall, 0.0), h10(nall, 0.0);  // pad atoms: zeros
@@ -1135,7 +1150,7 @@ extern "C" int mpmc_hip_set_axilrod_teller(mpmc_hip_ctx *c, int enable, int n, c
     if (!enable) {
         if (flush_moves(c)) return -1;
         c->at_on = false;
-        c->at_part_valid = false;
+        c->at.valid = false;
         ++c->config_rev;
         return 0;
     }
@@ -1157,13 +1172,13 @@ extern "C" int mpmc_hip_set_axilrod_teller(mpmc_hip_ctx *c, int enable, int n, c
     if (!c->d_at_a) {
         HIPCHK(c->d_at_a.alloc(nall));
         HIPCHK(c->d_at_g.alloc(nall));
-        HIPCHK(c->d_atpart.alloc((size_t)at_unit_count((int)(nall / 64)) * kAtSplit));
+        HIPCHK(c->at.part.alloc((size_t)at_unit_count((int)(nall / 64)) * kAtSplit));
     }
     const size_t bd = nall * sizeof(double);
     HIPCHK(hipMemcpyAsync(c->d_at_a, ha.data(), bd, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_at_g, hg.data(), bd, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    c->at_part_valid = false;
+    c->at.valid = false;
     c->at_on = true;
     ++c->config_rev;
     return 0;
@@ -1182,15 +1197,15 @@ extern "C" int mpmc_hip_set_rd_crystal(mpmc_hip_ctx *c, int order) {
     if (order > 0) {
         const size_t ntile = c->max_npad / 64;
         if (alloc_zero_params(c)) return -1;
-        if (!c->d_rdcpart) {
-            HIPCHK(c->d_rdcpart.alloc(ntile * ntile));
-            HIPCHK(c->d_rdclrcpart.alloc(ntile * ntile));
+        if (!c->rdc.part) {
+            HIPCHK(c->rdc.part.alloc(ntile * ntile));
+            HIPCHK(c->rdc_static.part.alloc(ntile * ntile));
         }
     }
     c->rdc_order = order;
-    c->rdc_part_valid = c->rdc_static_valid = false;
+    c->rdc.valid = c->rdc_static.valid = false;
     c->pair_part_valid = false;  // the Lennard-Jones kernels change between real and zero parameters
-    c->lrc_valid = false;
+    c->lrc.valid = false;
     c->all_dirty = true;
     ++c->config_rev;
     return 0;
@@ -1526,8 +1541,8 @@ extern "C" int mpmc_hip_insert_molecule(mpmc_hip_ctx *c, int count, const double
         const int npad = round_up(c->n, 128);
         if (npad != c->npad) {  // the tile grids of the pair / field / LRC partials change shape
             c->npad = npad;
-            c->pair_part_valid = c->field_part_valid = c->disp_part_valid = c->rdc_part_valid = false;
-            c->lrc_valid = false;
+            params_or_grid_changed(c);
+            c->lrc.valid = false;
         }
     }
     double mm = 0.0;
@@ -2000,7 +2015,7 @@ static int launch_pair_kernel(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &
     }
     c->call.side_moves.n = 0;
     c->call.moves_in_pair = false;
-    c->call.disp_moves = mv;
+    c->call.pair_moves = mv;
     if (with_recip && c->opt.fuse_recip && c->call.plain_launches && c->nk > 0 &&
         (c->nk + 63) / 64 <= ntile) {
         // the reciprocal-space partials of the same blocks ride in a second z-slice of this launch (pair_recip_kernel) when
@@ -2046,36 +2061,57 @@ static int launch_recip_partial(mpmc_hip_ctx *c, const DevAtoms &a, hipStream_t 
     return 0;
 }
 
-// disp_expansion: the dense tile kernel behind the pair kernel (same stream, same dirty blocks, same move) and the fixed-order
-// sum of its tile partials; the long-range correction when the parameters, the cutoff or the volume changed.
+// ---- Dense tile sums (kernels_tile.h).  The fixed-order sum of a TileSum's partials into its slot of d_res:
+static void sum_tiles(mpmc_hip_ctx *c, const TileSum &ts, int nparts, ResSlot slot, hipStream_t sb) {
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(kReduceThreads), 0, sb, ts.part, nparts, 1, c->d_res + slot);
+}
+
+// The pass of a sum over positions, behind the pair kernel: same stream, same dirty blocks, same move.  enqueue(sel)
+// launches the term's kernel over the tiles of the blocks in sel (sel.n == 0: all of them).
+template <typename Enqueue>
+static int tile_pass(mpmc_hip_ctx *c, TileSum &ts, int nparts, ResSlot slot, hipStream_t sb, Enqueue &&enqueue) {
+    DirtyBlocks sel = c->call.dirty_blocks;
+    if (!ts.valid) sel.n = 0;
+    if (ts.valid && c->dirty_atoms.empty()) return 0;  // nothing moved: d_res[slot] is still that sum
+    ScopedTimer t(c, T_PAIR, sb);
+    enqueue(sel);
+    sum_tiles(c, ts, nparts, slot, sb);
+    HIPCHK(hipGetLastError());
+    ts.valid = true;
+    return 0;
+}
+
+// A static sum (parameters, cutoff, volume and which atoms exist: no coordinate), made again when it is stale.  enqueue()
+// launches its kernels; nparts == 0: they left no tile partials to add up.
+template <typename Enqueue>
+static int static_pass(mpmc_hip_ctx *c, TileSum &ts, bool stale, int nparts, ResSlot slot, hipStream_t sb, Enqueue &&enqueue) {
+    if (!stale) return 0;
+    ScopedTimer t(c, T_OTHER, sb);
+    enqueue();
+    if (nparts > 0) sum_tiles(c, ts, nparts, slot, sb);
+    HIPCHK(hipGetLastError());
+    ts.valid = true;
+    return 0;
+}
+
+// disp_expansion: the dense pair sum, and its long-range correction when the parameters, the cutoff or the volume changed.
 static int launch_disp(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipStream_t sb) {
     const int ntile = c->npad / 64;
     const DispAtoms da = {c->d_eps, c->d_sig, c->d_c6, c->d_c8, c->d_c10};
     if (c->par.rd_lrc) {
-        if (!c->disp_lrc_valid) {
-            ScopedTimer t(c, T_OTHER, sb);
-            hipLaunchKernelGGL(disp_lrc_kernel, dim3(ntile, ntile), dim3(64 * kDispLrcWaves), 0, sb, a, da, bx, c->disp_par,
-                               c->d_displrcpart);
-            hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(kReduceThreads), 0, sb, c->d_displrcpart, ntile * ntile, 1,
-                               c->d_res + R_DISP_LRC);
-            HIPCHK(hipGetLastError());
-            c->disp_lrc_valid = true;
-        }
+        if (static_pass(c, c->disp_lrc, !c->disp_lrc.valid, ntile * ntile, R_DISP_LRC, sb, [&] {
+                hipLaunchKernelGGL(disp_lrc_kernel, dim3(ntile, ntile), dim3(64 * kDispLrcWaves), 0, sb, a, da, bx, c->disp_par,
+                                   c->disp_lrc.part);
+            }))
+            return -1;
     } else {
         c->call.res_zero_mask |= 1u << R_DISP_LRC;
-        c->disp_lrc_valid = false;
+        c->disp_lrc.valid = false;
     }
-    DirtyBlocks sel = c->call.dirty_blocks;
-    if (!c->disp_part_valid) sel.n = 0;
-    if (c->disp_part_valid && c->dirty_atoms.empty()) return 0;  // nothing moved: d_res[R_DISP] is still that sum
-    ScopedTimer t(c, T_PAIR, sb);
-    hipLaunchKernelGGL(disp_tile_kernel, dim3(ntile, sel.n > 0 ? sel.n : ntile), dim3(64 * kDispWaves), 0, sb, a, da, bx,
-                       c->disp_par, sel, c->d_disppart, c->call.disp_moves);
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(kReduceThreads), 0, sb, c->d_disppart, ntile * ntile, 1,
-                       c->d_res + R_DISP);
-    HIPCHK(hipGetLastError());
-    c->disp_part_valid = true;
-    return 0;
+    return tile_pass(c, c->disp, ntile * ntile, R_DISP, sb, [&](const DirtyBlocks &sel) {
+        hipLaunchKernelGGL(disp_tile_kernel, dim3(ntile, sel.n > 0 ? sel.n : ntile), dim3(64 * kDispWaves), 0, sb, a, da, bx,
+                           c->disp_par, sel, c->disp.part, c->call.pair_moves);
+    });
 }
 
 // rd_crystal: cutoff_c and the squared-distance threshold that decides exactly as `sqrt(r2) > cutoff_c` does
@@ -2092,9 +2128,8 @@ static RdcParams rdc_params(const mpmc_hip_ctx *c) {
     return rp;
 }
 
-// rd_crystal: the image-sum tile kernel behind the pair kernel (same stream, same dirty blocks, same move); the self part
-// and the long-range correction at cutoff_c when the parameters, the box or rd_lrc changed.  `a` carries zero epsilon /
-// sigma in this mode: these kernels get the real ones.
+// rd_crystal: the image sum; the self part and the long-range correction at cutoff_c when the parameters, the box or rd_lrc
+// changed.  `a` carries zero epsilon / sigma in this mode: these kernels get the real ones.
 static int launch_rdc(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipStream_t sb) {
     const int ntile = c->npad / 64;
     DevAtoms lj = a;
@@ -2102,55 +2137,36 @@ static int launch_rdc(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipS
     lj.sig = c->d_sig;
     const RdcParams rp = rdc_params(c);
     const int want_lrc = c->par.rd_lrc ? 1 : 0;
-    if (!c->rdc_static_valid || c->rdc_static_lrc != want_lrc) {
-        ScopedTimer t(c, T_OTHER, sb);
-        hipLaunchKernelGGL(rdc_self_kernel, dim3(1), dim3(kRdcSelfThreads), 0, sb, lj, bx, rp, c->d_res + R_RDC_SELF);
-        if (want_lrc) {
+    const bool stale = !c->rdc_static.valid || c->rdc_static_lrc != want_lrc;
+    if (static_pass(c, c->rdc_static, stale, want_lrc ? ntile * ntile : 0, R_DISP_LRC, sb, [&] {
+            hipLaunchKernelGGL(rdc_self_kernel, dim3(1), dim3(kRdcSelfThreads), 0, sb, lj, bx, rp, c->d_res + R_RDC_SELF);
+            if (!want_lrc) return;
             DevBox bc = bx;
             bc.cutoff = rp.cutoff_c;  // lj_lrc_corr / lj_lrc_self at the crystal cutoff (lj.c:188, :273)
-            DirtyBlocks all;
-            memset(&all, 0, sizeof(all));
-            hipLaunchKernelGGL(lj_lrc_kernel, dim3(ntile, ntile), dim3(64 * kLrcWaves), 0, sb, lj, bc, all, c->d_rdclrcpart);
-            hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(kReduceThreads), 0, sb, c->d_rdclrcpart, ntile * ntile, 1,
-                               c->d_res + R_DISP_LRC);
-        }
-        HIPCHK(hipGetLastError());
-        c->rdc_static_valid = true;
-        c->rdc_static_lrc = want_lrc;
-    }
+            const DirtyBlocks all = {};
+            hipLaunchKernelGGL(lj_lrc_kernel, dim3(ntile, ntile), dim3(64 * kLrcWaves), 0, sb, lj, bc, all, c->rdc_static.part);
+        }))
+        return -1;
+    c->rdc_static_lrc = want_lrc;
     if (!want_lrc) c->call.res_zero_mask |= 1u << R_DISP_LRC;
-    DirtyBlocks sel = c->call.dirty_blocks;
-    if (!c->rdc_part_valid) sel.n = 0;
-    if (c->rdc_part_valid && c->dirty_atoms.empty()) return 0;  // nothing moved: d_res[R_DISP] is still that sum
-    ScopedTimer t(c, T_PAIR, sb);
-    hipLaunchKernelGGL(rdc_tile_kernel, dim3(ntile, sel.n > 0 ? sel.n : ntile), dim3(64 * kRdcWaves), 0, sb, lj, bx, rp, sel,
-                       c->d_rdcpart, c->call.disp_moves);
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(kReduceThreads), 0, sb, c->d_rdcpart, ntile * ntile, 1,
-                       c->d_res + R_DISP);
-    HIPCHK(hipGetLastError());
-    c->rdc_part_valid = true;
-    return 0;
+    return tile_pass(c, c->rdc, ntile * ntile, R_DISP, sb, [&](const DirtyBlocks &sel) {
+        hipLaunchKernelGGL(rdc_tile_kernel, dim3(ntile, sel.n > 0 ? sel.n : ntile), dim3(64 * kRdcWaves), 0, sb, lj, bx, rp, sel,
+                           c->rdc.part, c->call.pair_moves);
+    });
 }
 
-// axilrod_teller: the block-triple kernel behind the pair (and dispersion) launch -- same stream, same dirty blocks, same
-// move -- and the fixed-order sum of all its partials (an order that is a function of the block count only).
+// axilrod_teller: the block-triple sum (behind the pair and the dispersion launch); the order of the sum over all its
+// partials is a function of the block count only.
 static int launch_at(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipStream_t sb) {
     const int ntile = c->npad / 64;
     const AtAtoms ta = {c->d_at_a, c->d_at_g};
-    DirtyBlocks sel = c->call.dirty_blocks;
-    if (!c->at_part_valid) sel.n = 0;
-    if (c->at_part_valid && c->dirty_atoms.empty()) return 0;  // nothing moved: d_res[R_AT] is still that sum
     const long units = at_unit_count(ntile);
-    const dim3 grid = sel.n > 0 ? dim3((unsigned)(ntile * (ntile + 1) / 2 * kAtSplit), (unsigned)sel.n)
-                                : dim3((unsigned)(units * kAtSplit));
-    ScopedTimer t(c, T_PAIR, sb);
-    hipLaunchKernelGGL(at_triple_kernel, grid, dim3(64 * kAtWaves), 0, sb, a, ta, bx, sel, ntile, c->d_atpart,
-                       c->call.disp_moves);
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(kReduceThreads), 0, sb, c->d_atpart, (int)(units * kAtSplit), 1,
-                       c->d_res + R_AT);
-    HIPCHK(hipGetLastError());
-    c->at_part_valid = true;
-    return 0;
+    return tile_pass(c, c->at, (int)(units * kAtSplit), R_AT, sb, [&](const DirtyBlocks &sel) {
+        const dim3 grid = sel.n > 0 ? dim3((unsigned)(ntile * (ntile + 1) / 2 * kAtSplit), (unsigned)sel.n)
+                                    : dim3((unsigned)(units * kAtSplit));
+        hipLaunchKernelGGL(at_triple_kernel, grid, dim3(64 * kAtWaves), 0, sb, a, ta, bx, sel, ntile, c->at.part,
+                           c->call.pair_moves);
+    });
 }
 
 static int launch_publish(mpmc_hip_ctx *c) {
@@ -2188,7 +2204,7 @@ static bool blocks_of(const std::vector<int> &atoms, DirtyBlocks &out) {
 static void collect_dirty_blocks(mpmc_hip_ctx *c) {
     DirtyBlocks &d = c->call.dirty_blocks;
     if (c->all_dirty || !c->opt.incremental_pairs || !blocks_of(c->dirty_atoms, d)) {
-        c->pair_part_valid = c->field_part_valid = c->disp_part_valid = c->at_part_valid = c->rdc_part_valid = false;
+        positions_unknown(c);
         memset(&d, 0, sizeof(d));
     }
     c->call.pair_part_valid_before = c->pair_part_valid;  // false whenever the dirty-block list cannot be trusted
@@ -2275,19 +2291,16 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
             // tile partials kept, and only the tiles of inserted / removed atoms' blocks redone afterwards
             DirtyBlocks lsel;
             const bool overflow = !blocks_of(c->lrc_dirty_atoms, lsel);
-            if (!c->lrc_valid) lsel.n = 0;
-            if (!c->lrc_valid || overflow || lsel.n > 0) {
-                ScopedTimer t(c, T_OTHER, sb);
-                hipLaunchKernelGGL(lj_lrc_kernel, dim3(ntile, lsel.n > 0 ? lsel.n : ntile), dim3(64 * kLrcWaves), 0, sb, a, bx, lsel,
-                                   c->d_lrcpart);
-                hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(kReduceThreads), 0, sb, c->d_lrcpart, ntile * ntile, 1,
-                                   c->d_res + R_LRC);
-                c->lrc_valid = true;
-            }
+            if (!c->lrc.valid) lsel.n = 0;
+            if (static_pass(c, c->lrc, !c->lrc.valid || overflow || lsel.n > 0, ntile * ntile, R_LRC, sb, [&] {
+                    hipLaunchKernelGGL(lj_lrc_kernel, dim3(ntile, lsel.n > 0 ? lsel.n : ntile), dim3(64 * kLrcWaves), 0, sb, a, bx,
+                                       lsel, c->lrc.part);
+                }))
+                return -1;
             c->lrc_dirty_atoms.clear();
         } else {
             k.res_zero_mask |= 1u << R_LRC;  // (zeroed by the publish kernel: a memset is a launch of its own)
-            c->lrc_valid = false;
+            c->lrc.valid = false;
         }
 
         // ---- fused pair kernel: LJ(+FH) and real-space Ewald(+FH, + intra-molecular screening)
@@ -2418,7 +2431,7 @@ static bool graph_eligible(mpmc_hip_ctx *c) {
         return false;
     if (c->all_dirty || c->staged_copies || c->pending.n <= 0 || c->call.dirty_blocks.n < 1) return false;
     if (!v.C_valid || !v.pos_valid || !c->pair_part_valid || !c->field_part_valid) return false;
-    if (P.rd_lrc && !c->lrc_valid) return false;
+    if (P.rd_lrc && !c->lrc.valid) return false;
     if (P.polar_ewald && !c->kvecf_valid) return false;
     bool polarizable_moved = false;
     for (int atom : c->dirty_atoms) polarizable_moved |= (v.slot_of_atom[atom] >= 0);

@@ -32,7 +32,7 @@
 // (i, j) pair data stay in registers), and the k atoms arrive in slices of 8: the (j, k) table of the slice (broadcast
 // reads) and the (i, k) table (one column per lane) are formed once per workgroup in LDS.
 #pragma once
-#include "device_common.h"
+#include "kernels_tile.h"
 
 namespace mpmc {
 
@@ -214,15 +214,7 @@ __global__ __launch_bounds__(64 * kAtWaves) void at_triple_kernel(DevAtoms a, At
             }
         }
     }
-    acc = wave_sum(acc);
-    if (lane == 0) red[wv] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {  // waves in order: deterministic
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < kAtWaves; ++w) t += red[w];
-        out[0] = t;
-    }
+    block_sum_store<kAtWaves>(acc, red, out);
 }
 
 }  // namespace mpmc

@@ -28,12 +28,11 @@
 // square-rooted r; this file forms q = sigma^2 * (1 / r^2), q^3 and (q^3)^2 from one reciprocal of r^2.  The terms differ
 // by ~1e-16 relative, four orders inside the tests' tolerance; no decision depends on them.
 //
-// Tile ownership is the pair kernel's: one workgroup of 8 waves per 64 x 64 tile, J >= I, lane = row atom, each wave takes
-// 8 of the 64 column atoms, the innermost loop runs over the images (translations staged once per workgroup in LDS).  A
-// tile's partial is a function of its two blocks' atoms and the box only and is summed in a fixed order, so an incremental
-// pass over the moved atoms' blocks leaves the bits of a from-scratch pass.
+// One workgroup of 8 waves per 64 x 64 tile, J >= I, lane = row atom, each wave takes 8 of the 64 column atoms, the innermost
+// loop runs over the images (translations staged once per workgroup in LDS); tile ownership and the fixed-order sum are
+// kernels_tile.h's.
 #pragma once
-#include "device_common.h"
+#include "kernels_tile.h"
 
 namespace mpmc {
 
@@ -92,23 +91,16 @@ __device__ __forceinline__ void load_rdc_tile(RdcTile &t, const DevAtoms &a, con
     t.flags[lane] = a.flags[j];
 }
 
-// Full pass: grid = (npad/64 [J], npad/64 [I]); tiles with J < I only clear their slot.  Incremental pass (sel.n > 0):
-// grid = (npad/64, sel.n), block (x, y) redoes the tile of blocks {sel.blk[y], x} -- disp_tile_kernel's scheme, and like it
-// this kernel takes a moved atom's position from the list, never from memory.  a: the REAL epsilon / sigma (the
+// Grids of the full and the incremental pass: owned_tile().  Like disp_tile_kernel this kernel takes a moved atom's
+// position from the list, never from memory.  a: the REAL epsilon / sigma (the
 // Lennard-Jones kernels of the same call are handed zeros).
 constexpr int kRdcWaves = 8;
 constexpr int kRdcJPerWave = kWave / kRdcWaves;
 __global__ __launch_bounds__(64 * kRdcWaves) void rdc_tile_kernel(DevAtoms a, DevBox bx, RdcParams rp, DirtyBlocks sel,
                                                                    double *__restrict__ partials, MoveList m) {
-    int I = blockIdx.y, J = blockIdx.x;
+    int I, J;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (sel.n > 0) {
-        const int db = sel.blk[blockIdx.y], o = blockIdx.x;
-        for (int k = 0; k < (int)blockIdx.y; ++k)
-            if (sel.blk[k] == o) return;  // the tile of two dirty blocks belongs to the earlier one
-        I = min(db, o);
-        J = max(db, o);
-    }
+    if (!owned_tile(sel, I, J)) return;
     double *out = partials + (size_t)I * gridDim.x + J;
     if (J < I) {
         if (threadIdx.x == 0) out[0] = 0.0;
@@ -138,8 +130,7 @@ __global__ __launch_bounds__(64 * kRdcWaves) void rdc_tile_kernel(DevAtoms a, De
     for (int jj = wv * kRdcJPerWave; jj < (wv + 1) * kRdcJPerWave; ++jj) {
         const int j = J * kWave + jj;
         const int flj = tj.flags[jj];
-        // pair (i < j) of two real atoms, not frozen-frozen; same-molecule pairs take part (lj.c:191-193)
-        if (!((j > i) && (fli & kValid) && (flj & kValid) && !((fli & kFrozen) && (flj & kFrozen)))) continue;
+        if (!pair_in_sum(i, j, fli, flj)) continue;  // same-molecule pairs take part (lj.c:191-193)
         const double epsj = tj.eps[jj], sigj = tj.sig[jj];
         // Lorentz-Berthelot as the Lennard-Jones path mixes it (pairs.c:200-211): what is left out here is exactly 0
         if (!(sigi > 0.0 && sigj > 0.0) || epsi == 0.0 || epsj == 0.0) continue;
@@ -180,15 +171,7 @@ __global__ __launch_bounds__(64 * kRdcWaves) void rdc_tile_kernel(DevAtoms a, De
         }
         acc += e;
     }
-    acc = wave_sum(acc);
-    if (lane == 0) red[wv] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {  // waves in order: deterministic
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < kRdcWaves; ++k) t += red[k];
-        out[0] = t;
-    }
+    block_sum_store<kRdcWaves>(acc, red, out);
 }
 
 // Self part (rd_crystal_self, lj.c:109-162): the two lattice sums are the same for every atom, so they are formed once

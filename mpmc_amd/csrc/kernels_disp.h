@@ -8,11 +8,10 @@
 //   * per-atom epsilon is the exponent b (1/A), per-atom sigma the range rho (A);
 //   * the pair part of the long-range correction runs over every pair that is not frozen-frozen (same-molecule and
 //     rd-excluded pairs included), the self part over every non-frozen atom with its coefficients as read, in atomic units.
-// Tile ownership is the pair kernel's (kernels_pair.h): one workgroup of 8 waves per 64 x 64 tile, J >= I, lane = row atom,
-// each wave takes 8 of the 64 column atoms; a tile's partial is a function of its two blocks' atoms only and is summed in a
-// fixed order, so an incremental pass over the moved atoms' blocks leaves the bits of a from-scratch pass.
+// One workgroup of 8 waves per 64 x 64 tile, J >= I, lane = row atom, each wave takes 8 of the 64 column atoms; tile
+// ownership and the fixed-order sum are kernels_tile.h's.
 #pragma once
-#include "device_common.h"
+#include "kernels_tile.h"
 
 namespace mpmc {
 
@@ -68,25 +67,17 @@ __device__ __forceinline__ void load_disp_tile(DispTile &t, const DevAtoms &a, c
     t.flags[lane] = a.flags[j];
 }
 
-// Full pass: grid = (npad/64 [J], npad/64 [I]); tiles with J < I only clear their slot.  Incremental pass (sel.n > 0):
-// grid = (npad/64, sel.n), block (x, y) redoes the tile of blocks {sel.blk[y], x} -- exactly pair_rd_es_body's scheme.
-// m: the step's move, as the pair kernel in front of this launch carried it (that launch also wrote the coordinate arrays;
-// a moved atom's position is taken from the list all the same, so this kernel never reads a coordinate the other stream's
-// writer may be storing at the same time).
+// Grids of the full and the incremental pass: owned_tile().  m: the step's move, as the pair kernel in front of this launch
+// carried it (that launch also wrote the coordinate arrays; a moved atom's position is taken from the list all the same, so
+// this kernel never reads a coordinate the other stream's writer may be storing at the same time).
 constexpr int kDispWaves = 8;
 constexpr int kDispJPerWave = kWave / kDispWaves;
 __global__ __launch_bounds__(64 * kDispWaves) void disp_tile_kernel(DevAtoms a, DispAtoms d, DevBox bx, DispParams dp,
                                                                     DirtyBlocks sel, double *__restrict__ partials,
                                                                     MoveList m) {
-    int I = blockIdx.y, J = blockIdx.x;
+    int I, J;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (sel.n > 0) {
-        const int db = sel.blk[blockIdx.y], o = blockIdx.x;
-        for (int k = 0; k < (int)blockIdx.y; ++k)
-            if (sel.blk[k] == o) return;  // the tile of two dirty blocks belongs to the earlier one
-        I = min(db, o);
-        J = max(db, o);
-    }
+    if (!owned_tile(sel, I, J)) return;
     double *out = partials + (size_t)I * gridDim.x + J;
     if (J < I) {
         if (threadIdx.x == 0) out[0] = 0.0;
@@ -109,9 +100,8 @@ __global__ __launch_bounds__(64 * kDispWaves) void disp_tile_kernel(DevAtoms a, 
     for (int jj = wv * kDispJPerWave; jj < (wv + 1) * kDispJPerWave; ++jj) {
         const int j = J * kWave + jj;
         const int flj = tj.flags[jj];
-        // pair (i < j) of two real atoms, not frozen-frozen, not on one molecule (pairs.c:61-81)
-        if (!((j > i) && (fli & kValid) && (flj & kValid) && !((fli & kFrozen) && (flj & kFrozen)))) continue;
-        if (moli == tj.mol[jj]) continue;
+        if (!pair_in_sum(i, j, fli, flj)) continue;
+        if (moli == tj.mol[jj]) continue;  // ... and not on one molecule (pairs.c:61-81)
         const double bj = tj.b[jj], rhoj = tj.rho[jj];
         const double c6j = tj.c6[jj], c8j = tj.c8[jj], c10j = tj.c10[jj];
         // null repulsion AND null dispersion (pairs.c:68)
@@ -159,15 +149,7 @@ __global__ __launch_bounds__(64 * kDispWaves) void disp_tile_kernel(DevAtoms a, 
         }
         acc += -f6 * c6 * ir6 - f8 * c8 * ir8 - f10 * c10 * ir10 + repulsion;
     }
-    acc = wave_sum(acc);
-    if (lane == 0) red[wv] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {  // waves in order: deterministic
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < kDispWaves; ++k) t += red[k];
-        out[0] = t;
-    }
+    block_sum_store<kDispWaves>(acc, red, out);
 }
 
 // Long-range correction (disp_expansion.c:5-38, :50-53, :92-100): parameters, the cutoff and the volume only, so it is
@@ -206,7 +188,7 @@ __global__ __launch_bounds__(64 * kDispLrcWaves) void disp_lrc_kernel(DevAtoms a
         const int j = J * kWave + jj;
         const int flj = sfl[jj];
         // every pair that is not frozen-frozen: same-molecule and rd-excluded pairs included (disp_expansion.c:7, :50-53)
-        if (!((j > i) && (fli & kValid) && (flj & kValid) && !((fli & kFrozen) && (flj & kFrozen)))) continue;
+        if (!pair_in_sum(i, j, fli, flj)) continue;
         double c6, c8, c10;
         disp_mix_coeffs(dp, c6i, c8i, c10i, s6[jj], s8[jj], s10[jj], c6, c8, c10);
         acc += disp_lrc_term(c6, c8, c10, rc, bx.volume);
@@ -218,15 +200,7 @@ __global__ __launch_bounds__(64 * kDispLrcWaves) void disp_lrc_kernel(DevAtoms a
             acc += disp_lrc_term(c6i, c8i, c10, rc, bx.volume);
         }
     }
-    acc = wave_sum(acc);
-    if (lane == 0) red[wv] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < kDispLrcWaves; ++k) t += red[k];
-        out[0] = t;
-    }
+    block_sum_store<kDispLrcWaves>(acc, red, out);
 }
 
 }  // namespace mpmc

@@ -12,7 +12,7 @@
 // redone); they are reduced with 64-lane shuffles and summed in a fixed order by a finalisation
 // kernel, so results are bitwise reproducible run to run and independent of the update history.
 #pragma once
-#include "device_common.h"
+#include "kernels_tile.h"
 
 namespace mpmc {
 
@@ -81,7 +81,7 @@ __device__ __forceinline__ void pair_rd_es_body(const DevAtoms &a, const DevBox 
     if (sel.n > 0) {
         const int d = sel.blk[blockIdx.y], o = blockIdx.x;
         for (int k = 0; k < (int)blockIdx.y; ++k)
-            if (sel.blk[k] == o) return;  // the tile of two dirty blocks belongs to the earlier one
+            if (sel.blk[k] == o) return;  // the tile of two dirty blocks belongs to the earlier one (owned_tile())
         I = min(d, o);
         J = max(d, o);
     }
@@ -277,22 +277,16 @@ __global__ __launch_bounds__(64 * kPairWaves) void pair_rd_es_kernel(DevAtoms a,
 // (same-molecule pairs INCLUDED, lj.c:56-83) + per-atom self part (lj.c:85-107).  Depends only
 // on parameters and the volume, so it is evaluated at upload / box change, like the
 // reference's cached pair_ptr->lrc.
-// Tile partials persist like the pair kernel's; an incremental pass (sel.n > 0, grid = (npad/64, sel.n))
-// redoes the tiles of the blocks whose atoms were inserted or removed.
+// Tile partials persist like the pair kernel's; an incremental pass (owned_tile()) redoes the tiles of the blocks whose
+// atoms were inserted or removed.
 // (workgroup = 8 waves on one tile, each taking 8 of the 64 column atoms: a lone wave needs ~20 us for the 64 square
 //  roots and divides of a tile, and every grand-canonical edit redoes the tiles of the edited block)
 constexpr int kLrcWaves = 8;
 __global__ __launch_bounds__(64 * kLrcWaves) void lj_lrc_kernel(DevAtoms a, DevBox bx, DirtyBlocks sel,
                                                                  double *__restrict__ partials) {
-    int I = blockIdx.y, J = blockIdx.x;
+    int I, J;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (sel.n > 0) {
-        const int d = sel.blk[blockIdx.y], o = blockIdx.x;
-        for (int k = 0; k < (int)blockIdx.y; ++k)
-            if (sel.blk[k] == o) return;
-        I = min(d, o);
-        J = max(d, o);
-    }
+    if (!owned_tile(sel, I, J)) return;
     double *out = partials + (size_t)(I * gridDim.x + J);
     if (J < I) {
         if (threadIdx.x == 0) out[0] = 0.0;
@@ -315,7 +309,7 @@ __global__ __launch_bounds__(64 * kLrcWaves) void lj_lrc_kernel(DevAtoms a, DevB
     for (int jj = wv * (kWave / kLrcWaves); jj < (wv + 1) * (kWave / kLrcWaves); ++jj) {
         const int j = J * kWave + jj;
         const int flj = sfl[jj];
-        if (!((j > i) && (fli & kValid) && (flj & kValid) && !((fli & kFrozen) && (flj & kFrozen)))) continue;
+        if (!pair_in_sum(i, j, fli, flj)) continue;
         const double sigj = ssig[jj], epsj = seps[jj];
         double sig, eps;
         if (sigi < 0.0 || sigj < 0.0) {
@@ -345,15 +339,7 @@ __global__ __launch_bounds__(64 * kLrcWaves) void lj_lrc_kernel(DevAtoms a, DevB
             acc += ((16.0 / 3.0) * kPI * epsi * s3) * ((1.0 / 3.0) * sc9 - sc3) / bx.volume;
         }
     }
-    acc = wave_sum(acc);
-    if (lane == 0) red[wv] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {  // waves in order: deterministic
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < kLrcWaves; ++k) t += red[k];
-        out[0] = t;
-    }
+    block_sum_store<kLrcWaves>(acc, red, out);
 }
 
 // Reciprocal-space Ewald (coulombic.c:42-95): one 256-thread block per k-vector computes the

@@ -115,6 +115,9 @@ PARAM_NAMES = [f[0] for f in Params._fields_]
 DISP_NAMES = [f[0] for f in DispParams._fields_]
 AT_NAMES = ["axilrod_teller", "midzuno_kihara_approx"]  # mpmc_hip_set_axilrod_teller (reference keywords)
 RDC_NAMES = ["rd_crystal", "rd_crystal_order"]  # mpmc_hip_set_rd_crystal (reference keywords)
+# flags that make_params() leaves to others: pbc_cutoff is a box property at this boundary (set_box), the rest are the
+# arguments of the three calls above (Engine.load_system)
+NOT_PARAMS = frozenset(["pbc_cutoff"] + DISP_NAMES + AT_NAMES + RDC_NAMES)
 AT_ALPHA_AU = 6.7483345  # A^3 -> Bohr^3, as the reference writes it (axilrod_teller.cpp:115)
 
 _lib = None
@@ -188,14 +191,8 @@ def make_params(**kw):
     p = Params()
     load().mpmc_hip_default_params(C.byref(p))
     for k, v in kw.items():
-        if k == "pbc_cutoff":
-            continue  # a box property at this boundary (set_box)
-        if k in DISP_NAMES:
-            continue  # mpmc_hip_set_dispersion's record (Engine.load_system)
-        if k in AT_NAMES:
-            continue  # mpmc_hip_set_axilrod_teller's arguments (Engine.load_system)
-        if k in RDC_NAMES:
-            continue  # mpmc_hip_set_rd_crystal's argument (Engine.load_system)
+        if k in NOT_PARAMS:
+            continue
         if k not in PARAM_NAMES:
             raise KeyError(k)
         setattr(p, k, v)
@@ -372,11 +369,6 @@ class Engine:
         A = np.zeros((3 * self.n, 3 * self.n))
         _chk(self.lib.mpmc_hip_download_amatrix(self.ctx, A.ctypes.data))
         return A
-
-    def timings(self):
-        t = Timings()
-        _chk(self.lib.mpmc_hip_get_timings(self.ctx, C.byref(t)))
-        return {f: getattr(t, f) for f, _ in Timings._fields_}
 
     def ranking(self):
         rank = np.zeros(self.n)
