@@ -201,6 +201,7 @@ struct SweepView {
     std::vector<int> slot_of_atom;  // atom index -> view slot, -1 if not in the view
     DevBuf<double> mupub;  // Gauss-Seidel chain: the published dipoles of a sweep, planar per block (hand-off buffer)
     DevBuf<double> es, mu0, mu1, munew, y, efind, efchg, rrms;
+    DevBuf<double> tmu0;  // the first Jacobi sweep's sums T mu_0, kept for the energy of a solve whose last sweep is deferred
     DevBuf<unsigned> gsflags;  // [8] gs_chain_kernel: ticket counter, sticky error word, breadcrumbs
     // Gauss-Seidel chain (kernels_gs_chain.h): cached inverses of the diagonal blocks and expanded sub-diagonal tiles
     DevBuf<double> Minv;         // [cap/64][kMinvDoubles]
@@ -224,6 +225,20 @@ struct SweepView {
     std::vector<int> h_idx;
 };
 
+// The last sweep of a fixed-count plain Jacobi solve, not launched yet (run_polarization(), defer_last_sweep()): U_pol does
+// not need it, whoever asks for mu / E_ind does (complete_pending_sweep()).  Everything the launch takes that is not device
+// state travels here; the device state it reads (view coordinates, coefficients, E_static, mu_{n-1}) stays as the call
+// left it until something listed in DESIGN.md section 3 changes it -- which completes the sweep first -- or the next
+// energy_begin() drops it.
+struct PendingSweep {
+    bool on = false;
+    struct SweepView *view = nullptr;
+    const double *mu_in = nullptr;
+    double *mu_out = nullptr;
+    DevBox bx;
+    SweepParams sp;
+};
+
 // The kernels of one steady-state MC step whose arguments change from step to step; every other node of
 // the captured graph is replayed as it was.
 enum GraphSlotId { GS_MOVES = 0, GS_COEF, GS_FIELD, GS_PAIR, GS_RECIP, GS_PUBLISH, GS_NSLOT };
@@ -239,6 +254,7 @@ struct StepGraph {
     int iterations = 0;
     struct SweepView *result_view = nullptr;
     const double *result_mu = nullptr;
+    PendingSweep psweep;  // (never part of the capture: a replay leaves the same sweep pending)
     const double *energy_part = nullptr;
     int energy_nt = 0;
     int recip_chunks = 0, pair_rows_to_sum = 0;
@@ -380,6 +396,7 @@ struct mpmc_hip_ctx {
     SweepView *result_view = nullptr;
     const double *result_mu = nullptr;
     bool results_scattered = true;
+    PendingSweep psweep;            // the solve's last sweep, when the last call left it to the first reader of its output
     const double *energy_part = nullptr;  // per-block energy sums to fold in publish_result_kernel (or null)
     int energy_nt = 0;
     bool es_stale = false;  // d_es (atom order) not yet reduced from the field partials
@@ -541,6 +558,12 @@ static DevBox dev_box(const mpmc_hip_ctx *c) {
 }
 
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
+static int complete_pending_sweep(mpmc_hip_ctx *c);  // engine_polar.inc
+// the polarization result is gone (the configuration it belongs to is being replaced): nobody can ask for the pending sweep
+static void drop_polar_result(mpmc_hip_ctx *c) {
+    c->psweep.on = false;
+    c->have_polar_result = false;
+}
 static void (*chain_kernel_of(int ortho))(GsChain);  // engine_polar.inc
 
 // running maximum of |coordinate| (device_common.h: above kScreen32MaxCoord the pair / field screens switch
@@ -710,6 +733,7 @@ static const OptionRow kOptions[] = {
 
 extern "C" int mpmc_hip_set_option(mpmc_hip_ctx *c, const char *name, int value) {
     if (!c || !name) return fail("MPMC_HIP: set_option: null argument");
+    if (complete_pending_sweep(c)) return -1;  // (launched under the options of the call it belongs to)
     ++c->config_rev;
     for (const OptionRow &o : kOptions) {
         if (strcmp(name, o.name)) continue;
@@ -816,6 +840,7 @@ extern "C" int mpmc_hip_create(mpmc_hip_ctx **out, int device, int max_atoms) {
         c->gs_qoff = (int)(3 * np + 192);
         HIPCHK(v.y.alloc(3 * np));
         HIPCHK(v.efind.alloc(3 * np));
+        HIPCHK(v.tmu0.alloc(3 * np));
         HIPCHK(v.efchg.alloc(3 * np));
         HIPCHK(v.rrms.alloc(np));
         HIPCHK(v.gsflags.alloc(16));
@@ -915,6 +940,7 @@ extern "C" int mpmc_hip_set_params(mpmc_hip_ctx *c, const mpmc_hip_params *p) {
         if (p->polar_sor && p->polar_esor) return fail("MPMC_HIP: cannot specify both SOR and ESOR SCF methods");
         if (p->polar_gamma < 0.0) return fail("MPMC_HIP: invalid Pre-cond/SOR/ESOR gamma set");
     }
+    if (complete_pending_sweep(c)) return -1;
     if (p->polar_damp != c->par.polar_damp) c->all_dirty = true;
     params_or_grid_changed(c);
     ++c->config_rev;
@@ -979,6 +1005,7 @@ static int apply_box(mpmc_hip_ctx *c, const double basis[9], double pbc_cutoff) 
 extern "C" int mpmc_hip_set_box(mpmc_hip_ctx *c, const double basis[9], double pbc_cutoff) {
     if (!c || !basis) return fail("MPMC_HIP: set_box: null argument");
     if (c->in_flight) return fail("MPMC_HIP: set_box between energy_begin() and energy_end()");
+    if (complete_pending_sweep(c)) return -1;
     return apply_box(c, basis, pbc_cutoff);
 }
 
@@ -992,6 +1019,7 @@ extern "C" int mpmc_hip_upload(mpmc_hip_ctx *c, int n, const double *x, const do
     if (!x || !y || !z || !charge || !polarizability || !epsilon || !sigma || !mass || !molecule || !frozen)
         return fail("MPMC_HIP: upload: null array");
     HIPCHK(hipSetDevice(c->device));
+    drop_polar_result(c);
     const int npad = round_up(n, 128);
     const int nall = c->max_npad;  // every allocated slot is (re)initialised: later inserts may grow into them
     std::vector<double> hx(nall, 0.0), hy(nall, 0.0), hz(nall, 0.0), hq(nall, 0.0), ha(nall, 0.0), he(nall, 0.0),
@@ -1226,6 +1254,8 @@ extern "C" int mpmc_hip_get_three_body_energy(mpmc_hip_ctx *c, double *out) {
 static void side_wait_for_moves(mpmc_hip_ctx *c, hipStream_t s);
 static int flush_moves(mpmc_hip_ctx *c) {
     if (c->pending.n > 0) {
+        // (outside an evaluation: a pending sweep reads the view's coordinates; energy_begin() has dropped it by now)
+        if (complete_pending_sweep(c)) return -1;
         SweepView &v0 = c->view[0];
         HIPCHK(launch_slot(c, GS_MOVES, apply_moves_kernel, dim3(1), dim3(64), c->stream, c->pending, c->d_x, c->d_y,
                            c->d_z, v0.d_slot, v0.px, v0.py, v0.pz));
@@ -1284,6 +1314,7 @@ extern "C" int mpmc_hip_update_atoms(mpmc_hip_ctx *c, int first, int count, cons
     if (queued) {
         // nothing to launch yet
     } else if ((size_t)(3 * count) <= c->h_stage.size()) {
+        if (complete_pending_sweep(c)) return -1;
         if (flush_moves(c)) return -1;
         c->staged_copies = true;
         c->main_writes = true;
@@ -1303,6 +1334,7 @@ extern "C" int mpmc_hip_update_atoms(mpmc_hip_ctx *c, int first, int count, cons
         HIPCHK(hipMemcpyAsync(c->d_y + first, s + count, b, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->d_z + first, s + 2 * count, b, hipMemcpyHostToDevice, c->stream));
     } else {
+        if (complete_pending_sweep(c)) return -1;
         if (flush_moves(c)) return -1;
         c->staged_copies = true;
         c->main_writes = true;
@@ -1343,6 +1375,7 @@ extern "C" int mpmc_hip_scale_box(mpmc_hip_ctx *c, const double basis[9], double
         const double v = std::fabs(delta[k]);
         if (!(v <= dmax)) dmax = (v == v) ? v : INFINITY;
     }
+    if (complete_pending_sweep(c)) return -1;  // (a refused box below leaves the last result readable)
     if (flush_moves(c)) return -1;  // keep the order of the caller's operations
     if (c->d_delta.size() < need) {
         HIPCHK(hipStreamSynchronize(c->stream));  // (growth only: an earlier launch may still read the old buffer)
@@ -1444,6 +1477,7 @@ static int launch_edits(mpmc_hip_ctx *c, const EditList &ed) {
     t.pz = v0.pz;
     t.palpha = v0.palpha;
     t.pflags = v0.pflags;
+    drop_polar_result(c);  // (mark_edited(): the result of the configuration before the edit cannot be asked for any more)
     if (flush_moves(c)) return -1;  // keep the order of the caller's operations
     c->main_writes = true;
     hipLaunchKernelGGL(apply_edits_kernel, dim3(1), dim3(64), 0, c->stream, ed, t);
@@ -1616,6 +1650,7 @@ extern "C" int mpmc_hip_set_sweep_order(mpmc_hip_ctx *c, int count, const int *s
             return fail("MPMC_HIP: set_sweep_order: %d slots stated, the configuration has %d polarizable sites", count, npolar);
     }
     HIPCHK(hipSetDevice(c->device));
+    drop_polar_result(c);
     if (flush_moves(c)) return -1;  // queued moves were addressed through the old view
     c->main_writes = true;          // (the slot map below; and a flushed move is a main-stream write the side stream has not seen)
     // how far the new order agrees with the old one: the blocks in front of the first difference keep their data
@@ -2216,6 +2251,7 @@ static void begin_call(mpmc_hip_ctx *c) {
     c->ev_next = 0;
     c->recs.clear();
     c->call = CallState();
+    c->psweep.on = false;  // nobody asked for the previous call's dipoles: its last sweep is never launched
     collect_dirty_blocks(c);
 }
 
@@ -2501,6 +2537,7 @@ static int graph_step(mpmc_hip_ctx *c) {
     c->graph_launch_s += (g2.tv_sec - g1.tv_sec) + 1e-9 * (g2.tv_nsec - g1.tv_nsec);
     c->result_view = c->sg.result_view;
     c->result_mu = c->sg.result_mu;
+    c->psweep = c->sg.psweep;
     c->results_scattered = false;
     c->have_polar_result = true;
     c->call.iterations = c->sg.iterations;
@@ -2564,6 +2601,7 @@ extern "C" int mpmc_hip_energy_begin(mpmc_hip_ctx *c) {
                 c->sg.iterations = c->call.iterations;
                 c->sg.result_view = c->result_view;
                 c->sg.result_mu = c->result_mu;
+                c->sg.psweep = c->psweep;
                 c->sg.energy_part = c->energy_part;
                 c->sg.energy_nt = c->energy_nt;
                 c->sg.recip_chunks = c->call.recip_chunks;
@@ -2716,6 +2754,7 @@ extern "C" int mpmc_hip_download_dipoles(mpmc_hip_ctx *c, double *mu, double *ef
     if (!c->have_polar_result) return fail("MPMC_HIP: download_dipoles: no polarization energy evaluated yet");
     HIPCHK(hipSetDevice(c->device));
     if (ensure_static_field(c)) return -1;
+    if (complete_pending_sweep(c)) return -1;  // mu_n and E_ind(mu_{n-1}), if the call left its last sweep to this moment
     if (!c->results_scattered) {
         // the solver works on the compacted polarizable atoms; atom order is produced when somebody asks
         SweepView *V = c->result_view;

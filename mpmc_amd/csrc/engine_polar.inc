@@ -454,6 +454,7 @@ static int launch_sweep(mpmc_hip_ctx *c, SweepView &v, const DevBox &bx, const d
         fin.errmax = c->d_errmax;
         fin.mu_final = mu_final;
         fin.energy_part = v.energy_part;
+        fin.tmu0 = v.tmu0;
         fin.sp = sp;
         size_t half_plane = 0;
         {
@@ -514,6 +515,33 @@ static int launch_sweep(mpmc_hip_ctx *c, SweepView &v, const DevBox &bx, const d
                            v.pflags, mu_in, v.es, v.efind, out, v.rrms, c->d_errmax, sp);
     }
     return 0;
+}
+
+// Does this call leave its LAST Jacobi sweep to whoever asks for the dipoles?  U_pol = -1/2 sum mu_n.E needs mu_{n-1} and
+// the first sweep's sums only (kernels_coef.h, pair_finish_kernel; DESIGN.md section 3), and sweep n produces nothing else a
+// Monte Carlo step reads.  A function of the flags, the view's size and the device alone -- not of options other than the
+// storage the sweeps run on, of the resident solver's fallback state or of earlier calls -- so that U_pol's last bits
+// are a function of the configuration: plain fixed-count Jacobi (gamma = 1, at least two sweeps, no RRMS) on pair
+// coefficients, on a view too large for the one-launch solvers (resident_plan()'s size test), whose results the
+// launch-per-sweep path is held to bit for bit.
+static bool defer_last_sweep(const mpmc_hip_ctx *c, const SweepView &v) {
+    const mpmc_hip_params &P = c->par;
+    if (!c->opt.pair_coef || !v.C_valid) return false;
+    if (P.polar_zodid || P.polar_gs || P.polar_gs_ranked || P.polar_palmo || P.polar_sor || P.polar_esor || P.polar_rrms)
+        return false;
+    if (P.polar_precision != 0.0 || P.polar_gamma != 1.0 || P.polar_max_iter < 2) return false;
+    const int nt = std::max(1, (v.nv + kCoefTile - 1) / kCoefTile);
+    return nt * (nt + 1) / 2 + nt > c->num_cus;
+}
+
+// The sweep the last call left out, now: mu_n into the buffer result_mu already names, E_ind(mu_{n-1}) into the view.
+// Same launches with the same arguments as when the call itself ran it, hence the same bits.
+static int complete_pending_sweep(mpmc_hip_ctx *c) {
+    if (!c->psweep.on) return 0;
+    const PendingSweep p = c->psweep;
+    c->psweep.on = false;
+    HIPCHK(hipSetDevice(c->device));
+    return launch_sweep<kSweepJacobi>(c, *p.view, p.bx, p.mu_in, p.mu_out, p.sp, T_SWEEP);
 }
 
 static void (*chain_kernel_of(int ortho))(GsChain) { return ortho ? gs_chain_kernel<1> : gs_chain_kernel<0>; }
@@ -898,6 +926,7 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
 
     int iteration_counter = 0;
     bool ranked_active = false;  // becomes true after the first update_ranking()
+    const bool defer = !rp.ok && defer_last_sweep(c, *V);
     if (rp.ok) {
         if (launch_resident(c, *V, bx, rp, want_rrms)) return -1;
         iteration_counter = P.polar_max_iter;
@@ -931,8 +960,25 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
                 sp.want_rrms = want_rrms;
                 sp.want_err = P.polar_precision > 0.0;
                 sp.err_slot = iteration_counter;
-                sp.skip_sums = (P.polar_precision == 0.0 && iteration_counter < P.polar_max_iter) ? 1 : 0;
-                if (launch_sweep<kSweepJacobi>(c, *V, bx, mu_in, mu_out, sp, T_SWEEP)) return -1;
+                sp.skip_sums = (P.polar_precision == 0.0 && iteration_counter < P.polar_max_iter - (defer ? 1 : 0)) ? 1 : 0;
+                if (defer) {
+                    sp.mu0_scale = P.polar_gamma;  // (init_view_kernel's `scale` in this mode)
+                    if (iteration_counter == 1) sp.energy_mode |= kEnergyStoreTmu0;
+                    if (iteration_counter == P.polar_max_iter - 1) sp.energy_mode |= kEnergyFromTmu0;
+                }
+                if (defer && iteration_counter == P.polar_max_iter) {
+                    // sweep n: recorded, not launched (complete_pending_sweep())
+                    sp.skip_sums = 1;
+                    PendingSweep &ps = c->psweep;
+                    ps.on = true;
+                    ps.view = V;
+                    ps.mu_in = mu_in;
+                    ps.mu_out = mu_out;
+                    ps.bx = bx;
+                    ps.sp = sp;
+                } else if (launch_sweep<kSweepJacobi>(c, *V, bx, mu_in, mu_out, sp, T_SWEEP)) {
+                    return -1;
+                }
                 // the device is busy now: feed the LJ/Ewald stream (its ~55 us of kernels only have to be done by the
                 // time the last sweep is)
                 if (c->call.enqueue_side && (iteration_counter == c->opt.side_after || P.polar_max_iter < c->opt.side_after)) c->call.enqueue_side();

@@ -541,7 +541,13 @@ struct SweepParams {
     int want_err;    // polar_precision > 0: the host reads max (new-old)^2 after every sweep
     int err_slot;    // index into errmax[] for this iteration
     int skip_sums;   // 1: the block's energy / RRMS sums are not wanted (an iteration that is known not to be the last)
+    // Fixed-count plain Jacobi with the last sweep deferred (pair_finish_kernel): which of the two
+    // extra jobs this sweep's finish does.  0 everywhere else.
+    int energy_mode = 0;      // kEnergyStoreTmu0 | kEnergyFromTmu0
+    double mu0_scale = 1.0;   // init_view_kernel's `scale`: mu_0 = alpha * E_static * scale
 };
+constexpr int kEnergyStoreTmu0 = 1;  // sweep 1: keep the sums s = T mu_0 per site
+constexpr int kEnergyFromTmu0 = 2;   // sweep n - 1: the block's energy share is sum_i (mu_0.E - (T mu_0).mu_{n-1})
 
 template <int MODE>
 __global__ __launch_bounds__(64) void sweep_kernel(const double *__restrict__ A, int lda, int npad,
