@@ -201,7 +201,7 @@ struct SweepView {
     std::vector<int> slot_of_atom;  // atom index -> view slot, -1 if not in the view
     DevBuf<double> mupub;  // Gauss-Seidel chain: the published dipoles of a sweep, planar per block (hand-off buffer)
     DevBuf<double> es, mu0, mu1, munew, y, efind, efchg, rrms;
-    DevBuf<double> tmu0;  // the first Jacobi sweep's sums T mu_0, kept for the energy of a solve whose last sweep is deferred
+    DevBuf<double> tmu0;  // a Jacobi sweep's sums T mu, kept for the energy of a solve whose last sweep is deferred (odd counts)
     DevBuf<unsigned> gsflags;  // [8] gs_chain_kernel: ticket counter, sticky error word, breadcrumbs
     // Gauss-Seidel chain (kernels_gs_chain.h): cached inverses of the diagonal blocks and expanded sub-diagonal tiles
     DevBuf<double> Minv;         // [cap/64][kMinvDoubles]
@@ -332,6 +332,8 @@ struct CallState {
     int gs_sweeps = 0;                // Gauss-Seidel sweeps enqueued so far
     bool gs_used[2] = {false, false};  // the persistent kernel ran on view 0 / 1: its error word travels with the record
     std::function<void()> enqueue_side;  // set while run_polarization() may feed the side stream (see enqueue_direct)
+    std::function<void()> publish_early;  // set while run_polarization() may launch the publish kernel itself, behind the
+    bool published = false;               //   finish that completes U_pol (see enqueue_direct); published: it did
     bool recip_fused = false;     // the reciprocal-space partials rode in the pair kernel's launch
     int recip_chunks = 0;         // chunk sums the publish kernel folds (0: R_RECIP was written directly)
     int pair_rows_to_sum = 0;     // tile partials of the pair kernel the publish kernel has to add up
@@ -2412,10 +2414,26 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
     };
     k.enqueue_side = polar_first ? std::function<void()>(enqueue_side) : std::function<void()>();
     if (!polar_first) enqueue_side();
+    // Early publication.  A fixed-count Jacobi solve whose last sweep is deferred knows U_pol after the finish of sweep
+    // ceil(n / 2) (engine_polar.inc, defer_last_sweep()); sweeps up to n - 1 serve only a later reader of the dipoles.  With
+    // the side stream publishing its own slots nothing else of the record is the main stream's, so run_polarization()
+    // launches the publish kernel right behind that finish: the host decides the step and enqueues the next one while
+    // the remaining sweeps run, and the next call's launches queue behind them in stream order.  Not when the call is
+    // timed with events (ev_last marks the end of the chain) nor in a captured step: both keep the placement at the end,
+    // and the same bits (tests/test_gpu_early_publish.py holds a timed context against an untimed one).
+    int publish_rc = 0;
+    if (k.split && polar_first && !is_timed_call(c))
+        k.publish_early = [&]() {
+            if (k.published || k.build_join_pending) return;
+            k.published = true;
+            publish_rc = launch_publish(c);
+        };
     {
         // ---- polarization (main stream)
         if (do_polar) {
-            if (run_polarization(c, a, bx, &polar_iterations, &iter_success)) {
+            const int rc = run_polarization(c, a, bx, &polar_iterations, &iter_success);
+            k.publish_early = nullptr;
+            if (rc || publish_rc) {
                 k.enqueue_side = nullptr;
                 return -1;
             }
@@ -2427,6 +2445,7 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
         if (!do_polar || P.polar_zodid) c->view[0].A_valid = c->view[0].C_valid = false;
     }
     k.enqueue_side = nullptr;
+    k.publish_early = nullptr;
     enqueue_side();
     if (side_rc) return -1;
     if (c->pending.n > 0 && flush_moves(c)) return -1;  // (a move no launch of this call carried: cannot happen, but cheap)
@@ -2438,7 +2457,7 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
     if (two_streams && !k.split) hipStreamWaitEvent(c->stream, c->ev_join, 0);
     const bool timed_call = is_timed_call(c);
     if (timed_call) hipEventRecord(c->ev_last, c->stream);
-    if (launch_publish(c)) return -1;
+    if (!k.published && launch_publish(c)) return -1;  // (published: run_polarization() has launched it already)
     k.iterations = polar_iterations;
     k.iter_success = iter_success;
     k.timed = timed_call;

@@ -517,9 +517,9 @@ static int launch_sweep(mpmc_hip_ctx *c, SweepView &v, const DevBox &bx, const d
     return 0;
 }
 
-// Does this call leave its LAST Jacobi sweep to whoever asks for the dipoles?  U_pol = -1/2 sum mu_n.E needs mu_{n-1} and
-// the first sweep's sums only (kernels_coef.h, pair_finish_kernel; DESIGN.md section 3), and sweep n produces nothing else a
-// Monte Carlo step reads.  A function of the flags, the view's size and the device alone -- not of options other than the
+// Does this call leave its LAST Jacobi sweep to whoever asks for the dipoles?  U_pol = -1/2 sum mu_n.E needs the dipoles and
+// sums of sweeps up to ceil(n / 2) only (kernels_coef.h, pair_finish_kernel; DESIGN.md section 3), and sweep n produces
+// nothing else a Monte Carlo step reads.  A function of the flags, the view's size and the device alone -- not of options other than the
 // storage the sweeps run on, of the resident solver's fallback state or of earlier calls -- so that U_pol's last bits
 // are a function of the configuration: plain fixed-count Jacobi (gamma = 1, at least two sweeps, no RRMS) on pair
 // coefficients, on a view too large for the one-launch solvers (resident_plan()'s size test), whose results the
@@ -960,11 +960,15 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
                 sp.want_rrms = want_rrms;
                 sp.want_err = P.polar_precision > 0.0;
                 sp.err_slot = iteration_counter;
-                sp.skip_sums = (P.polar_precision == 0.0 && iteration_counter < P.polar_max_iter - (defer ? 1 : 0)) ? 1 : 0;
+                sp.skip_sums = (P.polar_precision == 0.0 && iteration_counter < P.polar_max_iter) ? 1 : 0;
+                // the deferral: U_pol comes from the finish of sweep m = ceil(n / 2) (pair_finish_kernel); no other finish
+                // of the call writes the block sums
+                const int mid = (P.polar_max_iter + 1) / 2;
                 if (defer) {
-                    sp.mu0_scale = P.polar_gamma;  // (init_view_kernel's `scale` in this mode)
-                    if (iteration_counter == 1) sp.energy_mode |= kEnergyStoreTmu0;
-                    if (iteration_counter == P.polar_max_iter - 1) sp.energy_mode |= kEnergyFromTmu0;
+                    const bool odd = P.polar_max_iter & 1;
+                    sp.skip_sums = 1;
+                    if (odd && iteration_counter == P.polar_max_iter - mid) sp.energy_mode |= kEnergyStoreSums;
+                    if (iteration_counter == mid) sp.energy_mode |= kEnergyMid | (odd ? kEnergyPrevSums : 0);
                 }
                 if (defer && iteration_counter == P.polar_max_iter) {
                     // sweep n: recorded, not launched (complete_pending_sweep())
@@ -982,6 +986,13 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
                 // the device is busy now: feed the LJ/Ewald stream (its ~55 us of kernels only have to be done by the
                 // time the last sweep is)
                 if (c->call.enqueue_side && (iteration_counter == c->opt.side_after || P.polar_max_iter < c->opt.side_after)) c->call.enqueue_side();
+                // U_pol is complete behind this finish: the record goes out here, in front of sweeps m + 1 .. n - 1, which
+                // only a later reader of the dipoles needs (enqueue_direct; the side stream is fed first, so that the host
+                // is not left waiting for a record whose other half has not been enqueued)
+                if (defer && iteration_counter == mid && c->call.publish_early) {
+                    if (c->call.enqueue_side) c->call.enqueue_side();
+                    c->call.publish_early();
+                }
             } else {
                 GsFinishArgs gfa;
                 gfa.w_new = w_new;

@@ -291,7 +291,7 @@ struct CoefFinish {
     unsigned long long *errmax;
     const double *mu_final;    // Palmo: the dipoles the energy is taken with
     double *energy_part;       // [nt][2]: sum_i mu.E, sum_i rrms_i of the block
-    double *tmu0;              // [3 nvpad] the first sweep's sums T mu_0 (sp.energy_mode; unused otherwise)
+    double *tmu0;              // [3 nvpad] the sums an earlier sweep keeps for the energy (sp.energy_mode; unused otherwise)
     SweepParams sp;
 };
 
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(64 * kCoefFinishGroups) void pair_finish_kernel(int
     const size_t ncol = 3 * (size_t)kCoefTile * nt;
     // the epilogue's operands are requested up front, so their latency overlaps the partial-sum loads
     double al = 0.0, old[3] = {0.0, 0.0, 0.0}, es[3] = {0.0, 0.0, 0.0}, aux[3] = {0.0, 0.0, 0.0};
-    double tm0[3] = {0.0, 0.0, 0.0};  // T mu_0 of an earlier launch (sp.energy_mode == kEnergyFromTmu0)
+    double sk[3] = {0.0, 0.0, 0.0};  // the sums an earlier sweep stored (f.sp.energy_mode & kEnergyPrevSums)
     int fl = 0;
     if (g == 0) {
         al = f.alpha[i];
@@ -409,7 +409,7 @@ __global__ __launch_bounds__(64 * kCoefFinishGroups) void pair_finish_kernel(int
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
             es[p] = f.es[3 * i + p];
-            if (MODE == kSweepJacobi && f.sp.energy_mode == kEnergyFromTmu0) tm0[p] = f.tmu0[3 * i + p];
+            if (MODE == kSweepJacobi && (f.sp.energy_mode & kEnergyPrevSums)) sk[p] = f.tmu0[3 * i + p];
             if (MODE == kSweepJacobi) {
                 old[p] = f.mu_in[3 * i + p];
             } else {
@@ -458,28 +458,28 @@ __global__ __launch_bounds__(64 * kCoefFinishGroups) void pair_finish_kernel(int
     }
     double m_new[3], e_new[3];
     const int emode = (MODE == kSweepJacobi) ? f.sp.energy_mode : 0;
-    coef_epilogue<MODE>(f, t, i, lane, s, al, fl, old, es, aux, m_new, e_new, !f.sp.skip_sums && !(emode & kEnergyFromTmu0));
+    coef_epilogue<MODE>(f, t, i, lane, s, al, fl, old, es, aux, m_new, e_new, !f.sp.skip_sums && !(emode & kEnergyMid));
     // Plain fixed-count Jacobi (gamma = 1) with the last sweep left to whoever asks for the dipoles: with T symmetric,
-    //     sum_i mu_n.E = sum_i mu_0.E - (T mu_0).mu_{n-1},      mu_0 = alpha E,  mu_n = alpha (E - T mu_{n-1}),
-    // so the finish of sweep 1 keeps its sums s = T mu_0 and the finish of sweep n - 1, which has mu_{n-1} in registers,
-    // leaves the block's share of that sum where the last sweep's finish would have left sum_i mu_n.E.
+    // mu_0 = alpha E, s_k = T mu_{k-1}, mu_k = alpha (E - s_k) and m = ceil(n / 2),
+    //     sum_i mu_n.E = sum_i mu_m.E - (mu_m - mu_{m-1}).s_{n-m}
+    // (DESIGN.md section 3).  The finish of sweep m has mu_m, mu_{m-1} (old) and E in registers and leaves the block's
+    // share of that sum where the last sweep's finish would have left sum_i mu_n.E.  Even n: s_{n-m} are this sweep's
+    // own sums; odd n: those of sweep m - 1, which its finish stored per site.
     if (emode) {
 #pragma clang fp contract(off)
-        if (emode & kEnergyStoreTmu0) {
+        if (emode & kEnergyStoreSums) {
 #pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                f.tmu0[3 * i + p] = s[p];
-                tm0[p] = s[p];  // (n = 2: this launch is sweep n - 1 as well)
-            }
+            for (int p = 0; p < 3; ++p) f.tmu0[3 * i + p] = s[p];
         }
-        if (emode & kEnergyFromTmu0) {
+        if (emode & kEnergyMid) {
             double e_i = 0.0;
             if ((fl & kValid) && al != 0.0) {  // (the lanes coef_epilogue zeroes contribute nothing)
-                double m0[3];
+                if (!(emode & kEnergyPrevSums)) {
 #pragma unroll
-                for (int p = 0; p < 3; ++p) m0[p] = al * es[p] * f.sp.mu0_scale;  // init_view_kernel's expression
-                e_i = m0[0] * es[0] + m0[1] * es[1] + m0[2] * es[2];
-                e_i -= tm0[0] * m_new[0] + tm0[1] * m_new[1] + tm0[2] * m_new[2];
+                    for (int p = 0; p < 3; ++p) sk[p] = s[p];
+                }
+                e_i = m_new[0] * es[0] + m_new[1] * es[1] + m_new[2] * es[2];
+                e_i -= (m_new[0] - old[0]) * sk[0] + (m_new[1] - old[1]) * sk[1] + (m_new[2] - old[2]) * sk[2];
             }
             e_i = wave_sum(e_i);
             if (lane == 0) {

@@ -541,13 +541,14 @@ struct SweepParams {
     int want_err;    // polar_precision > 0: the host reads max (new-old)^2 after every sweep
     int err_slot;    // index into errmax[] for this iteration
     int skip_sums;   // 1: the block's energy / RRMS sums are not wanted (an iteration that is known not to be the last)
-    // Fixed-count plain Jacobi with the last sweep deferred (pair_finish_kernel): which of the two
+    // Fixed-count plain Jacobi with the last sweep deferred (pair_finish_kernel): which of the
     // extra jobs this sweep's finish does.  0 everywhere else.
-    int energy_mode = 0;      // kEnergyStoreTmu0 | kEnergyFromTmu0
-    double mu0_scale = 1.0;   // init_view_kernel's `scale`: mu_0 = alpha * E_static * scale
+    int energy_mode = 0;      // kEnergyStoreSums | kEnergyMid [| kEnergyPrevSums]
 };
-constexpr int kEnergyStoreTmu0 = 1;  // sweep 1: keep the sums s = T mu_0 per site
-constexpr int kEnergyFromTmu0 = 2;   // sweep n - 1: the block's energy share is sum_i (mu_0.E - (T mu_0).mu_{n-1})
+// n sweeps, m = ceil(n / 2); s_k = T mu_{k-1} are the sums of sweep k
+constexpr int kEnergyStoreSums = 1;  // sweep n - m of an odd n: keep the sums s_{n-m} per site (SweepView::tmu0)
+constexpr int kEnergyMid = 2;        // sweep m: the block's energy share is sum_i (mu_m.E - (mu_m - mu_{m-1}).s_{n-m})
+constexpr int kEnergyPrevSums = 4;   // with kEnergyMid, odd n: s_{n-m} are the stored sums, not this sweep's own
 
 template <int MODE>
 __global__ __launch_bounds__(64) void sweep_kernel(const double *__restrict__ A, int lda, int npad,
