@@ -106,6 +106,8 @@ typedef struct mpmc_hip_timings {
                            * cumulative)                                                                       */
     int resident_fallbacks; /* such calls that were repeated on the multi-launch path because a hand-off of the
                            * resident kernel timed out (the device was shared); the context then stays there    */
+    int pending_sweeps;   /* sweeps of the last evaluation's fixed-count Jacobi solve that are not launched yet: U_pol
+                           * does not need them, mpmc_hip_download_dipoles() launches them (state, not a measurement) */
 } mpmc_hip_timings;
 
 const char *mpmc_hip_last_error(void);
@@ -331,11 +333,12 @@ int mpmc_hip_slot_count(mpmc_hip_ctx *ctx);
  * needs.  A fixed-count plain Jacobi solve -- polar_max_iter = n >= 2, polar_precision = 0, polar_gamma = 1, none of
  * polar_sor / polar_esor / polar_palmo / polar_rrms / polar_zodid / polar_gs / polar_gs_ranked -- on pair coefficients
  * and on a view too large for the one-launch solvers (nt (nt + 1) / 2 + nt > compute units for nt 64-site blocks: 22
- * blocks or more on MI355X) launches n - 1 sweeps: with T symmetric, U_pol = -1/2 sum mu_n.E equals
- * -1/2 sum mu_0.E + 1/2 (T mu_0).mu_{n-1}, which the finish of sweep n - 1 forms.  polar_iterations is n all the same.
- * The n-th sweep (mu_n, E_ind of mu_{n-1}) stays pending; it is launched by the first call that reads its output or
- * that changes what it reads (below), and dropped by the next energy() if nobody did.  Every other solve runs all its
- * sweeps inside the call, as before. */
+ * blocks or more on MI355X) launches at most n - 1 sweeps: with T symmetric, U_pol = -1/2 sum mu_n.E is known behind
+ * the finish of sweep m = ceil(n / 2).  polar_iterations is n all the same.  The n-th sweep (mu_n,
+ * E_ind of mu_{n-1}) stays pending, and so do sweeps m + 1 .. n - 1 when the call published its result behind sweep m
+ * (every untimed launch-by-launch call with the side stream's own record; mpmc_hip_timings.pending_sweeps says how
+ * many): they are launched, in order, by the first call that reads their output or that changes what they read (below),
+ * and dropped by the next energy() if nobody did.  Every other solve runs all its sweeps inside the call, as before. */
 int mpmc_hip_energy(mpmc_hip_ctx *ctx, mpmc_hip_result *out);
 
 /* The same in two halves: _begin enqueues the evaluation and returns, _end waits for it and fills the
@@ -348,11 +351,11 @@ int mpmc_hip_energy_end(mpmc_hip_ctx *ctx, mpmc_hip_result *out);
 /* Per-atom vectors of the last energy(): atom->mu, ef_static, ef_induced,
  * ef_induced_change, each [n][3] (needed by write_dipole/write_field at corrtime,
  * output.c:1029-1088).  Any pointer may be NULL.
- * May launch device work beyond the copies: the last call's pending n-th Jacobi sweep (see mpmc_hip_energy; one sweep +
- * one finish launch, the first time only), then the scatter to atom order.  The vectors are, bit for bit, those the
- * call would have left had it run the sweep itself.  The pending sweep is also completed by whatever changes the
- * device state it reads while the result stays readable -- moves that are applied at once (more than 32 atoms, or a
- * full move list), mpmc_hip_set_box, mpmc_hip_scale_box, mpmc_hip_set_params, mpmc_hip_set_option,
+ * May launch device work beyond the copies: the last call's pending Jacobi sweeps (see mpmc_hip_energy; one sweep +
+ * one finish launch each, up to n - ceil(n / 2) of them, the first time only), then the scatter to atom order.  The
+ * vectors are, bit for bit, those the call would have left had it run the sweeps itself.  The pending sweeps are also
+ * completed by whatever changes the device state they read while the result stays readable -- moves that are applied
+ * at once (more than 32 atoms, or a full move list), mpmc_hip_set_box, mpmc_hip_scale_box, mpmc_hip_set_params, mpmc_hip_set_option,
  * mpmc_hip_download_amatrix with moves queued -- and dropped where the result itself is discarded (upload,
  * insert_molecule, remove_molecule, set_sweep_order).  Moves that are only queued (mpmc_hip_update_atoms of a
  * molecule) touch nothing: a Monte Carlo step pays nothing for it. */

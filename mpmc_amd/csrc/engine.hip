@@ -225,18 +225,24 @@ struct SweepView {
     std::vector<int> h_idx;
 };
 
-// The last sweep of a fixed-count plain Jacobi solve, not launched yet (run_polarization(), defer_last_sweep()): U_pol does
-// not need it, whoever asks for mu / E_ind does (complete_pending_sweep()).  Everything the launch takes that is not device
-// state travels here; the device state it reads (view coordinates, coefficients, E_static, mu_{n-1}) stays as the call
-// left it until something listed in DESIGN.md section 3 changes it -- which completes the sweep first -- or the next
-// energy_begin() drops it.
+// The sweeps of a fixed-count plain Jacobi solve that are not launched yet (run_polarization(), defer_last_sweep()): U_pol
+// does not need them, whoever asks for mu / E_ind does (complete_pending_sweep()).  Sweep n always; sweeps m + 1 .. n - 1
+// (m = ceil(n / 2)) as well when the call's record went out behind the finish of sweep m, in launch order.  Every entry
+// carries the buffers of the mu0 / mu1 ping-pong the call would have given it and its own parameters; view and box are the
+// call's.  Everything the launches take that is not device state travels here; the device state they read (view
+// coordinates, coefficients, E_static, mu_m) and the buffers they write (the other mu buffer, E_ind, the sweep scratch) stay
+// as the call left them until something listed in DESIGN.md section 3 changes them -- which completes the sweeps first --
+// or the next energy_begin() drops them.  Copyable: the step graph saves and restores it.
 struct PendingSweep {
-    bool on = false;
+    struct One {
+        const double *mu_in = nullptr;
+        double *mu_out = nullptr;
+        SweepParams sp;
+    };
+    std::vector<One> sweeps;  // in launch order; empty: nothing pending
     struct SweepView *view = nullptr;
-    const double *mu_in = nullptr;
-    double *mu_out = nullptr;
     DevBox bx;
-    SweepParams sp;
+    void drop() { sweeps.clear(); }
 };
 
 // The kernels of one steady-state MC step whose arguments change from step to step; every other node of
@@ -254,7 +260,7 @@ struct StepGraph {
     int iterations = 0;
     struct SweepView *result_view = nullptr;
     const double *result_mu = nullptr;
-    PendingSweep psweep;  // (never part of the capture: a replay leaves the same sweep pending)
+    PendingSweep psweep;  // (never part of the capture: a replay leaves the same sweeps pending)
     const double *energy_part = nullptr;
     int energy_nt = 0;
     int recip_chunks = 0, pair_rows_to_sum = 0;
@@ -398,7 +404,7 @@ struct mpmc_hip_ctx {
     SweepView *result_view = nullptr;
     const double *result_mu = nullptr;
     bool results_scattered = true;
-    PendingSweep psweep;            // the solve's last sweep, when the last call left it to the first reader of its output
+    PendingSweep psweep;            // the solve's sweeps that the last call left to the first reader of their output
     const double *energy_part = nullptr;  // per-block energy sums to fold in publish_result_kernel (or null)
     int energy_nt = 0;
     bool es_stale = false;  // d_es (atom order) not yet reduced from the field partials
@@ -563,7 +569,7 @@ static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static int complete_pending_sweep(mpmc_hip_ctx *c);  // engine_polar.inc
 // the polarization result is gone (the configuration it belongs to is being replaced): nobody can ask for the pending sweep
 static void drop_polar_result(mpmc_hip_ctx *c) {
-    c->psweep.on = false;
+    c->psweep.drop();
     c->have_polar_result = false;
 }
 static void (*chain_kernel_of(int ortho))(GsChain);  // engine_polar.inc
@@ -2253,7 +2259,7 @@ static void begin_call(mpmc_hip_ctx *c) {
     c->ev_next = 0;
     c->recs.clear();
     c->call = CallState();
-    c->psweep.on = false;  // nobody asked for the previous call's dipoles: its last sweep is never launched
+    c->psweep.drop();  // nobody asked for the previous call's dipoles: its pending sweeps are never launched
     collect_dirty_blocks(c);
 }
 
@@ -2417,8 +2423,8 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
     // Early publication.  A fixed-count Jacobi solve whose last sweep is deferred knows U_pol after the finish of sweep
     // ceil(n / 2) (engine_polar.inc, defer_last_sweep()); sweeps up to n - 1 serve only a later reader of the dipoles.  With
     // the side stream publishing its own slots nothing else of the record is the main stream's, so run_polarization()
-    // launches the publish kernel right behind that finish: the host decides the step and enqueues the next one while
-    // the remaining sweeps run, and the next call's launches queue behind them in stream order.  Not when the call is
+    // launches the publish kernel right behind that finish and leaves the remaining sweeps to whoever asks for the
+    // dipoles (PendingSweep): the next call's launches queue right behind the record.  Not when the call is
     // timed with events (ev_last marks the end of the chain) nor in a captured step: both keep the placement at the end,
     // and the same bits (tests/test_gpu_early_publish.py holds a timed context against an untimed one).
     int publish_rc = 0;
@@ -2773,7 +2779,7 @@ extern "C" int mpmc_hip_download_dipoles(mpmc_hip_ctx *c, double *mu, double *ef
     if (!c->have_polar_result) return fail("MPMC_HIP: download_dipoles: no polarization energy evaluated yet");
     HIPCHK(hipSetDevice(c->device));
     if (ensure_static_field(c)) return -1;
-    if (complete_pending_sweep(c)) return -1;  // mu_n and E_ind(mu_{n-1}), if the call left its last sweep to this moment
+    if (complete_pending_sweep(c)) return -1;  // mu_n and E_ind(mu_{n-1}), if the call left its last sweeps to this moment
     if (!c->results_scattered) {
         // the solver works on the compacted polarizable atoms; atom order is produced when somebody asks
         SweepView *V = c->result_view;
@@ -2833,6 +2839,7 @@ extern "C" int mpmc_hip_get_timings(mpmc_hip_ctx *c, mpmc_hip_timings *t) {
     t->spec_rank_redos = (int)c->spec_redos;
     t->resident_calls = (int)c->resident_calls;
     t->resident_fallbacks = (int)c->resident_fallbacks;
+    t->pending_sweeps = (int)c->psweep.sweeps.size();  // (state, not an event measurement)
     if (!c->timed) return 0;
     HIPCHK(hipSetDevice(c->device));
     float acc[T_NCLASS] = {0};

@@ -534,14 +534,16 @@ static bool defer_last_sweep(const mpmc_hip_ctx *c, const SweepView &v) {
     return nt * (nt + 1) / 2 + nt > c->num_cus;
 }
 
-// The sweep the last call left out, now: mu_n into the buffer result_mu already names, E_ind(mu_{n-1}) into the view.
-// Same launches with the same arguments as when the call itself ran it, hence the same bits.
+// The sweeps the last call left out, now and in order: mu_n into the buffer result_mu already names, E_ind(mu_{n-1}) into
+// the view.  Same launches with the same arguments as when the call itself ran them, hence the same bits.
 static int complete_pending_sweep(mpmc_hip_ctx *c) {
-    if (!c->psweep.on) return 0;
-    const PendingSweep p = c->psweep;
-    c->psweep.on = false;
+    if (c->psweep.sweeps.empty()) return 0;
+    PendingSweep p;
+    std::swap(p, c->psweep);  // (nothing is pending any more, whatever a launch below returns)
     HIPCHK(hipSetDevice(c->device));
-    return launch_sweep<kSweepJacobi>(c, *p.view, p.bx, p.mu_in, p.mu_out, p.sp, T_SWEEP);
+    for (const PendingSweep::One &s : p.sweeps)
+        if (launch_sweep<kSweepJacobi>(c, *p.view, p.bx, s.mu_in, s.mu_out, s.sp, T_SWEEP)) return -1;
+    return 0;
 }
 
 static void (*chain_kernel_of(int ortho))(GsChain) { return ortho ? gs_chain_kernel<1> : gs_chain_kernel<0>; }
@@ -927,6 +929,7 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
     int iteration_counter = 0;
     bool ranked_active = false;  // becomes true after the first update_ranking()
     const bool defer = !rp.ok && defer_last_sweep(c, *V);
+    c->psweep.drop();  // (begin_call() has; an abandoned graph capture runs this function twice in one call)
     if (rp.ok) {
         if (launch_resident(c, *V, bx, rp, want_rrms)) return -1;
         iteration_counter = P.polar_max_iter;
@@ -970,25 +973,27 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
                     if (odd && iteration_counter == P.polar_max_iter - mid) sp.energy_mode |= kEnergyStoreSums;
                     if (iteration_counter == mid) sp.energy_mode |= kEnergyMid | (odd ? kEnergyPrevSums : 0);
                 }
-                if (defer && iteration_counter == P.polar_max_iter) {
-                    // sweep n: recorded, not launched (complete_pending_sweep())
-                    sp.skip_sums = 1;
+                // sweep n, and sweeps m + 1 .. n - 1 once the record HAS gone out behind the finish of sweep m (published: not
+                // on a timed or captured call, nor while a builder join is pending): recorded in order, not launched
+                // (complete_pending_sweep()).  The ping-pong below goes on as if they had been.
+                if (defer && (iteration_counter == P.polar_max_iter || (iteration_counter > mid && c->call.published))) {
                     PendingSweep &ps = c->psweep;
-                    ps.on = true;
                     ps.view = V;
-                    ps.mu_in = mu_in;
-                    ps.mu_out = mu_out;
                     ps.bx = bx;
-                    ps.sp = sp;
+                    PendingSweep::One one;
+                    one.mu_in = mu_in;
+                    one.mu_out = mu_out;
+                    one.sp = sp;
+                    ps.sweeps.push_back(one);
                 } else if (launch_sweep<kSweepJacobi>(c, *V, bx, mu_in, mu_out, sp, T_SWEEP)) {
                     return -1;
                 }
                 // the device is busy now: feed the LJ/Ewald stream (its ~55 us of kernels only have to be done by the
                 // time the last sweep is)
                 if (c->call.enqueue_side && (iteration_counter == c->opt.side_after || P.polar_max_iter < c->opt.side_after)) c->call.enqueue_side();
-                // U_pol is complete behind this finish: the record goes out here, in front of sweeps m + 1 .. n - 1, which
-                // only a later reader of the dipoles needs (enqueue_direct; the side stream is fed first, so that the host
-                // is not left waiting for a record whose other half has not been enqueued)
+                // U_pol is complete behind this finish: the record goes out here, and sweeps m + 1 .. n - 1, which only a
+                // later reader of the dipoles needs, are then left to that reader (above) (enqueue_direct; the side stream
+                // is fed first, so that the host is not left waiting for a record whose other half has not been enqueued)
                 if (defer && iteration_counter == mid && c->call.publish_early) {
                     if (c->call.enqueue_side) c->call.enqueue_side();
                     c->call.publish_early();

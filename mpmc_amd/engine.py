@@ -98,6 +98,7 @@ class Timings(C.Structure):
         ("spec_rank_redos", C.c_int),
         ("resident_calls", C.c_int),
         ("resident_fallbacks", C.c_int),
+        ("pending_sweeps", C.c_int),
     ]
 
 

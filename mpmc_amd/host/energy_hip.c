@@ -757,6 +757,7 @@ double energy_hip_end(system_t *system) {
             s->spec_rank_redos = t.spec_rank_redos; /* cumulative in the engine */
             s->resident_calls = t.resident_calls;
             s->resident_fallbacks = t.resident_fallbacks;
+            s->pending_sweeps = t.pending_sweeps; /* state of the last evaluation */
         }
     }
     observables_t *o = system->observables;

@@ -55,7 +55,9 @@ void energy_hip_set_volume_notes(system_t *system, int on);
  * reads them (write_dipole() / write_field() at corrtime, src/mc/mc.c:398-414) instead of on every step */
 int energy_hip_download_dipoles(system_t *system);
 /* everything the reference's per-step pairs() / polar() leave behind for the writers of a corrtime block
- * (mc.c:366-414): wrapped coordinates (pairs.c:334) and, with polarization, the per-atom vectors above */
+ * (mc.c:366-414): wrapped coordinates (pairs.c:334) and, with polarization, the per-atom vectors above.
+ * A fixed-count Jacobi solve of n sweeps leaves up to n - ceil(n / 2) of them to this call (the engine launches them
+ * when the dipoles are asked for: mpmc_hip_timings.pending_sweeps), so a driver pays them once per corrtime block */
 int energy_hip_corrtime(system_t *system);
 
 /* cleanup() (src/main/cleanup.c): destroys the device context and the side table entry */
