@@ -300,6 +300,50 @@ int mpmc_hip_get_three_body_energy(mpmc_hip_ctx *ctx, double *out);
  * tiles of the moved atoms' blocks are summed again, with the bits of a from-scratch evaluation. */
 int mpmc_hip_set_rd_crystal(mpmc_hip_ctx *ctx, int order);
 
+/* polarvdw (alias cdvdw), the coupled-dipole many-body van der Waals term (reference src/energy/vdw.c:579-632; added to
+ * potential_energy at energy.c:194 and reported as observables->vdw_energy; not computed under rd_only):
+ *     vdw_energy = e_total - e_iso + lr_corr.
+ * With k_i = sqrt(polarizability_i) * omega_i, the atoms with k_i != 0 and K = diag(k), C = K A K is formed from the FULL
+ * Thole matrix A -- diagonal blocks 1 / alpha_i, off-diagonal blocks the exponentially damped (polar_damp) dipole tensor at
+ * the minimum-image distance; no cutoff; same-molecule and frozen-frozen pairs included -- and
+ *     e_total = 4.13412763705e16 * 3.81911146e-12 * sum_i sqrt(max(lambda_i(C), 0))       (negative eigenvalues clipped);
+ *     e_iso   = sum over the molecules, in upload order, of the same expression for the molecule's own diagonal sub-block
+ *               of C, evaluated ONCE per type id, on the first molecule of the type the context sees, and kept while the
+ *               mode stays on (kept as the reference has it: a later molecule of the type with another geometry still
+ *               takes the first one's value);
+ *     lr_corr = under rd_lrc, over every unordered pair that is not frozen-frozen, same-molecule pairs included, whose
+ *               alpha_i, alpha_j, omega_i, omega_j are all non-zero: -4/3 pi cC / cutoff^3 / volume with
+ *               cC = 1.5 * 7.63822291e-12 * w_i w_j / (w_i + w_j) * 4.13412763705e16 * a_i a_j.
+ * In this mode Lennard-Jones is repulsion only (lj.c:230-231): rd_energy = sum over the Lennard-Jones pairs of
+ * 4 eps_ij (sigma_ij / r)^12, plus under rd_lrc (16/9) pi eps sigma^3 (sigma / cutoff)^9 / volume per pair and per atom
+ * (lj.c:77-78, :100-101).  The eigenvalues come from a Householder tridiagonalisation and Sturm-count bisection on the
+ * device; the matrix is rebuilt from the resident positions in every call.
+ * omega: per atom, in upload order, in atomic units (PQR column 15).  mol_type[i]: an id that is equal for all atoms of all
+ * molecules of one type.  The polarizabilities (a negative one is an error) and the molecules are the upload's.  Called
+ * after mpmc_hip_upload(); enable = 0 (arrays ignored), or a later upload without this call, switches the mode off and
+ * returns the context to Lennard-Jones; the e_iso values survive a new upload as long as set_vdw(enable = 1) follows it
+ * before the next energy().  While the mode is on, mpmc_hip_result.energy includes the term (a non-finite term sets status
+ * bit 0), insert_molecule / remove_molecule answer 1 (upload the whole configuration again), and update_atoms, scale_box,
+ * energy_begin / _end, several contexts, Ewald / Wolf and every solver mode work as before.  energy() refuses the
+ * combinations with mpmc_hip_set_dispersion, mpmc_hip_set_rd_crystal, mpmc_hip_set_axilrod_teller and feynman_hibbs. */
+int mpmc_hip_set_vdw(mpmc_hip_ctx *ctx, int enable, int n, const double *omega, const int *mol_type);
+/* observables->vdw_energy of the last completed energy() / energy_end(); 0 while the mode is off. */
+int mpmc_hip_get_vdw_energy(mpmc_hip_ctx *ctx, double *out);
+/* Its parts, and the mode's rd_energy parts: e_total, e_iso, lr_corr, the repulsion pair sum, the repulsion long-range
+ * correction (pair + self); zeros while the mode is off. */
+int mpmc_hip_get_vdw_terms(mpmc_hip_ctx *ctx, double terms[5]);
+
+/* cavity_autoreject_absolute (reference energy.c:48-64): with scale = cavity_autoreject_scale > 0 every energy() also
+ * counts the pairs of atoms on DIFFERENT molecules -- frozen-frozen pairs included -- whose minimum-image distance is
+ * < scale, the distance and the comparison in the reference's fp64 operation order.  0 = off.  A setting of the context
+ * like mpmc_hip_set_rd_crystal(): it persists across uploads and is usable in every mode.  The engine only counts: what
+ * the reference does on a non-zero count (return MAXVALUE, leave the observables, count the rejection) is the caller's.
+ * The count of the last completed energy() / energy_end() is valid whatever the other terms came out as -- a close contact
+ * routinely makes the repulsion, and can make the coupled-dipole term, non-finite (status bit 0): energy_end() still
+ * returns 0 and the count is that of the configuration. */
+int mpmc_hip_set_autoreject(mpmc_hip_ctx *ctx, double scale);
+int mpmc_hip_get_close_contacts(mpmc_hip_ctx *ctx, long long *count);
+
 /* New coordinates for atoms [first, first+count): the delta after one MC move
  * (make_move perturbs one molecule, mc_moves.c:567). */
 int mpmc_hip_update_atoms(mpmc_hip_ctx *ctx, int first, int count, const double *x, const double *y,

@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <memory>
 #include <tuple>
 #include <utility>
@@ -39,6 +40,7 @@
 #include "kernels_disp.h"
 #include "kernels_at.h"
 #include "kernels_crystal.h"
+#include "kernels_vdw.h"
 #include "kernels_polar.h"
 #include "kernels_gs.h"
 #include "kernels_gs_chain.h"
@@ -176,7 +178,13 @@ enum ResSlot {
     R_AT = 14,        // axilrod_teller: the triple-dipole sum (kernels_at.h); reads as zero outside that mode
     R_RDC_SELF = 15,  // rd_crystal: the self part (kernels_crystal.h); its pair part and long-range correction take R_DISP and
                       // R_DISP_LRC, which the two modes cannot both want (energy() refuses the combination)
-    R_COUNT = 16
+    R_COUNT = 16,
+    // polarvdw (kernels_vdw.h) adds no slot: the repulsion-only sum and its long-range correction take R_DISP and R_DISP_LRC,
+    // the eigenvalue sum e_total takes R_AT and lr_corr takes R_RDC_SELF -- energy() refuses the mode together with each of
+    // the three modes that own them.  The close-contact count rides in the spare fourth pair channel.
+    R_VDW = R_AT,
+    R_VDW_LRC = R_RDC_SELF,
+    R_CONTACTS = 3
 };
 
 // A "sweep view" = the polarizable atoms, compacted, in the order the SCF sweep visits them.
@@ -438,6 +446,32 @@ struct mpmc_hip_ctx {
     TileSum rdc_static;             // [ntile*ntile] the long-range correction at cutoff_c, R_DISP_LRC; valid covers the self
                                     // part (R_RDC_SELF) too: both are those of the current parameters, box and rd_lrc
     int rdc_static_lrc = -1;        // the rd_lrc they were made under
+    // ---- polarvdw (mpmc_hip_set_vdw): coupled-dipole many-body van der Waals + repulsion-only Lennard-Jones, kernels_vdw.h.
+    // The LJ kernels are handed d_zero, as under disp_expansion.
+    bool vdw_on = false;
+    DevBuf<double> d_vdw_w;         // per atom: omega (atomic units), zero for pad atoms
+    DevBuf<int> d_vdw_idx;          // the sites of the matrix (k != 0), in atom order: atom slot ...
+    DevBuf<double> d_vdw_k;         // ... and k = sqrt(alpha) * omega
+    int vdw_na = 0;
+    DevBuf<double> d_vdw_C;         // [3 na][3 na], destroyed by every solve
+    DevBuf<double> d_vdw_vec;       // v, p, d, e, lambda: 3 na doubles each; then tau and the e_iso scratch slot
+    TileSum vdw;                    // (no partials) valid: d_res[R_VDW] is e_total of the configuration before the pending moves
+    TileSum vdw_lrc;                // [ntile*ntile] lr_corr, R_VDW_LRC
+    TileSum rep;                    // [ntile*ntile] the repulsion-only pair sum, R_DISP
+    TileSum rep_lrc;                // [ntile*ntile] its long-range correction, R_DISP_LRC
+    struct VdwMolecule {
+        int type, first_site, sites;  // type id; its run of sites in d_vdw_idx
+    };
+    std::vector<VdwMolecule> vdw_mols;   // the molecules of the upload, in upload order
+    std::map<int, double> vdw_iso;       // e_iso per type id, from the first molecule of the type seen (vdw.c:262-320); kept
+                                         // across uploads while the mode stays on
+    double vdw_e_iso = 0.0;              // its sum over the molecules, in upload order
+    bool vdw_iso_summed = false;
+    double vdw_energy = 0.0;             // the term of the last completed energy_end() (0 outside the mode)
+    double vdw_terms[5] = {0, 0, 0, 0, 0};  // ... and e_total, e_iso, lr_corr, the repulsion sum, its long-range correction
+    // ---- cavity_autoreject_absolute (mpmc_hip_set_autoreject): a context setting, persists across uploads
+    double autoreject_scale = 0.0;       // 0 = off
+    long long close_contacts = 0;        // of the last completed energy_end()
     double lrc_cached = 0.0;
     DevBuf<KVec> d_kvec;
     int nk = 0;
@@ -526,8 +560,8 @@ static DevAtoms dev_atoms(const mpmc_hip_ctx *c) {
     a.z = c->d_z;
     a.q = c->d_q;
     a.alpha = c->d_alpha;
-    a.eps = (c->disp_on || c->rdc_order) ? c->d_zero : c->d_eps;
-    a.sig = (c->disp_on || c->rdc_order) ? c->d_zero : c->d_sig;
+    a.eps = (c->disp_on || c->rdc_order || c->vdw_on) ? c->d_zero : c->d_eps;
+    a.sig = (c->disp_on || c->rdc_order || c->vdw_on) ? c->d_zero : c->d_sig;
     a.molmass = c->d_molmass;
     a.mol = c->d_mol;
     a.flags = c->d_flags;
@@ -916,17 +950,22 @@ extern "C" void mpmc_hip_destroy(mpmc_hip_ctx *c) {
 // all_dirty, or the moved blocks cannot be listed: every sum over positions (the static ones read no coordinate)
 static void positions_unknown(mpmc_hip_ctx *c) {
     c->pair_part_valid = c->field_part_valid = c->disp.valid = c->rdc.valid = c->at.valid = false;
+    c->rep.valid = c->vdw.valid = false;
 }
 // set_params(), or insert_molecule() grew the tile grid.  Not c->at: no parameter enters the three-body term, and the grid
 // cannot grow in its mode (edits_supported()); a full triple pass after every set_params() would be wasted.
 static void params_or_grid_changed(mpmc_hip_ctx *c) {
     c->pair_part_valid = c->field_part_valid = c->disp.valid = c->rdc.valid = false;
+    c->rep.valid = c->vdw.valid = false;  // (polar_damp enters the matrix)
 }
 // apply_box(): the sums of parameters, cutoff and volume (those over positions go with all_dirty)
-static void box_changed(mpmc_hip_ctx *c) { c->lrc.valid = c->disp_lrc.valid = c->rdc_static.valid = false; }
+static void box_changed(mpmc_hip_ctx *c) {
+    c->lrc.valid = c->disp_lrc.valid = c->rdc_static.valid = c->rep_lrc.valid = c->vdw_lrc.valid = false;
+}
 // upload(): everything per-atom (the pair / field partials go with all_dirty; the rd_crystal SETTING stays)
 static void atoms_replaced(mpmc_hip_ctx *c) {
     c->lrc.valid = c->disp.valid = c->disp_lrc.valid = c->at.valid = c->rdc.valid = c->rdc_static.valid = false;
+    c->rep.valid = c->rep_lrc.valid = c->vdw.valid = c->vdw_lrc.valid = false;
 }
 
 // reference src/io/check_input.c:318-470 (the subset that concerns this path)
@@ -1085,6 +1124,7 @@ extern "C" int mpmc_hip_upload(mpmc_hip_ctx *c, int n, const double *x, const do
     c->have_polar_result = false;
     c->disp_on = false;  // an upload brings Lennard-Jones parameters until set_dispersion() says otherwise
     c->at_on = false;  // ... and no three-body term until set_axilrod_teller() says otherwise
+    c->vdw_on = false;  // ... and no coupled-dipole term until set_vdw() says otherwise (its e_iso cache stays for that call)
     atoms_replaced(c);
     c->rank_saved.clear();
     c->perm_ranked = false;
@@ -1251,6 +1291,124 @@ extern "C" int mpmc_hip_get_three_body_energy(mpmc_hip_ctx *c, double *out) {
     if (!c || !out) return fail("MPMC_HIP: get_three_body_energy: null argument");
     if (c->in_flight) return fail("MPMC_HIP: get_three_body_energy between energy_begin() and energy_end()");
     *out = c->at_on ? c->three_body : 0.0;
+    return 0;
+}
+
+// polarvdw: the coupled-dipole many-body van der Waals term and repulsion-only Lennard-Jones (kernels_vdw.h).  omega
+// (atomic units, upload order) and the type id of every atom's molecule arrive here; the polarizabilities and the
+// molecules are the upload's.  Until the next upload the LJ kernels see zero parameters.
+extern "C" int mpmc_hip_set_vdw(mpmc_hip_ctx *c, int enable, int n, const double *omega, const int *mol_type) {
+    if (!c) return fail("MPMC_HIP: set_vdw: null context");
+    if (c->in_flight) return fail("MPMC_HIP: set_vdw between energy_begin() and energy_end()");
+    if (!c->have_atoms) return fail("MPMC_HIP: set_vdw: no configuration uploaded");
+    if (c->edited) return fail("MPMC_HIP: set_vdw: molecules were inserted or removed since the upload");
+    HIPCHK(hipSetDevice(c->device));
+    if (!enable) {
+        c->vdw_iso.clear();
+        if (!c->vdw_on) return 0;
+        if (flush_moves(c)) return -1;
+        c->vdw_on = false;
+        c->rep.valid = c->rep_lrc.valid = c->vdw.valid = c->vdw_lrc.valid = false;
+        c->pair_part_valid = false;  // the Lennard-Jones kernels change between real and zero parameters
+        c->lrc.valid = false;
+        c->all_dirty = true;
+        ++c->config_rev;
+        return 0;
+    }
+    if (n != c->n) return fail("MPMC_HIP: set_vdw: %d frequencies for the %d atoms of the upload", n, c->n);
+    if (!omega || !mol_type) return fail("MPMC_HIP: set_vdw: null array");
+    if (flush_moves(c)) return -1;  // keep the order of the caller's operations
+    const size_t nall = c->max_npad, ntile = nall / 64;
+    std::vector<double> ha(nall, 0.0), hw(nall, 0.0), hk;
+    std::vector<int> hmol(nall, 0), hidx;
+    HIPCHK(hipMemcpyAsync(ha.data(), c->d_alpha, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hmol.data(), c->d_mol, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::vector<mpmc_hip_ctx::VdwMolecule> mols;
+    for (int i = 0; i < n; ++i) {
+        if (ha[i] < 0.0) return fail("MPMC_HIP: set_vdw: negative polarizability %g of atom %d", ha[i], i);
+        if (i == 0 || hmol[i] != hmol[i - 1]) {
+            mols.push_back({mol_type[i], (int)hidx.size(), 0});
+        } else if (mol_type[i] != mols.back().type) {
+            return fail("MPMC_HIP: set_vdw: atom %d has type id %d, its molecule %d", i, mol_type[i], mols.back().type);
+        }
+        hw[i] = omega[i];
+        const double k = std::sqrt(ha[i]) * omega[i];  // getsqrtKinv, vdw.c:337
+        if (k != 0.0) {  // build_M leaves the others out (vdw.c:119)
+            hidx.push_back(i);
+            hk.push_back(k);
+            ++mols.back().sites;
+        }
+    }
+    const int na = (int)hidx.size();
+    if (!c->d_vdw_w) {
+        HIPCHK(c->d_vdw_w.alloc(nall));
+        HIPCHK(c->d_vdw_idx.alloc(nall));
+        HIPCHK(c->d_vdw_k.alloc(nall));
+        HIPCHK(c->vdw_lrc.part.alloc(ntile * ntile));
+        HIPCHK(c->rep.part.alloc(ntile * ntile));
+        HIPCHK(c->rep_lrc.part.alloc(ntile * ntile));
+    }
+    if (alloc_zero_params(c)) return -1;
+    const size_t nc = 3 * (size_t)std::max(na, 1);
+    if (c->d_vdw_C.size() < nc * nc) {
+        HIPCHK(c->d_vdw_C.alloc(nc * nc));
+        HIPCHK(c->d_vdw_vec.alloc(5 * nc + 2));
+    }
+    HIPCHK(hipMemcpyAsync(c->d_vdw_w, hw.data(), nall * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (na > 0) {
+        HIPCHK(hipMemcpyAsync(c->d_vdw_idx, hidx.data(), (size_t)na * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->d_vdw_k, hk.data(), (size_t)na * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->vdw_na = na;
+    c->vdw_mols = std::move(mols);
+    c->vdw_iso_summed = false;
+    c->rep.valid = c->rep_lrc.valid = c->vdw.valid = c->vdw_lrc.valid = false;
+    if (!c->vdw_on) {
+        c->pair_part_valid = false;  // the Lennard-Jones kernels change between real and zero parameters
+        c->lrc.valid = false;
+        c->all_dirty = true;
+    }
+    c->vdw_on = true;
+    ++c->config_rev;
+    return 0;
+}
+
+extern "C" int mpmc_hip_get_vdw_energy(mpmc_hip_ctx *c, double *out) {
+    if (!c || !out) return fail("MPMC_HIP: get_vdw_energy: null argument");
+    if (c->in_flight) return fail("MPMC_HIP: get_vdw_energy between energy_begin() and energy_end()");
+    *out = c->vdw_on ? c->vdw_energy : 0.0;
+    return 0;
+}
+
+extern "C" int mpmc_hip_get_vdw_terms(mpmc_hip_ctx *c, double terms[5]) {
+    if (!c || !terms) return fail("MPMC_HIP: get_vdw_terms: null argument");
+    if (c->in_flight) return fail("MPMC_HIP: get_vdw_terms between energy_begin() and energy_end()");
+    for (int k = 0; k < 5; ++k) terms[k] = c->vdw_on ? c->vdw_terms[k] : 0.0;
+    return 0;
+}
+
+// cavity_autoreject_absolute: count the pairs on different molecules closer than `scale` (kernels_vdw.h).  0 switches it
+// off.  A setting of the context, like set_rd_crystal().
+extern "C" int mpmc_hip_set_autoreject(mpmc_hip_ctx *c, double scale) {
+    if (!c) return fail("MPMC_HIP: set_autoreject: null context");
+    if (c->in_flight) return fail("MPMC_HIP: set_autoreject between energy_begin() and energy_end()");
+    if (!(scale >= 0.0) || !std::isfinite(scale)) return fail("MPMC_HIP: set_autoreject: scale %g (0 = off)", scale);
+    if (scale == c->autoreject_scale) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    if (c->have_atoms && flush_moves(c)) return -1;  // keep the order of the caller's operations
+    c->autoreject_scale = scale;
+    c->pair_part_valid = false;  // the count travels in the pair kernel's tile partials
+    c->all_dirty = true;
+    ++c->config_rev;
+    return 0;
+}
+
+extern "C" int mpmc_hip_get_close_contacts(mpmc_hip_ctx *c, long long *count) {
+    if (!c || !count) return fail("MPMC_HIP: get_close_contacts: null argument");
+    if (c->in_flight) return fail("MPMC_HIP: get_close_contacts between energy_begin() and energy_end()");
+    *count = c->autoreject_scale != 0.0 ? c->close_contacts : 0;
     return 0;
 }
 
@@ -1460,6 +1618,7 @@ static bool edits_supported(const mpmc_hip_ctx *c) {
     if (c->disp_on) return false;  // disp_expansion: no device-side insert / remove (the caller uploads again)
     if (c->at_on) return false;    // axilrod_teller: the same
     if (c->rdc_order) return false;  // rd_crystal: the same
+    if (c->vdw_on) return false;     // polarvdw: the same
     // Gauss-Seidel: only with the chain kernel, whose view is rebuilt from the order the caller states afterwards
     if (!P.rd_only && P.polarization && (P.polar_gs || P.polar_gs_ranked) && !gs_order_mode(c)) return false;
     return true;
@@ -2059,6 +2218,12 @@ static int launch_pair_kernel(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &
     c->call.side_moves.n = 0;
     c->call.moves_in_pair = false;
     c->call.pair_moves = mv;
+    // cavity_autoreject_absolute: the close-contact count of the same tiles, into the channel the pair kernel has cleared
+    auto contacts = [&] {
+        if (c->autoreject_scale == 0.0) return;
+        hipLaunchKernelGGL(contact_tile_kernel, grid, dim3(64 * kContactWaves), 0, sb, a, bx, c->autoreject_scale, sel,
+                           c->d_pairpart, kPairChannels, (int)R_CONTACTS, mv);
+    };
     if (with_recip && c->opt.fuse_recip && c->call.plain_launches && c->nk > 0 &&
         (c->nk + 63) / 64 <= ntile) {
         // the reciprocal-space partials of the same blocks ride in a second z-slice of this launch (pair_recip_kernel) when
@@ -2076,6 +2241,7 @@ static int launch_pair_kernel(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &
             else
                 hipLaunchKernelGGL(pair_recip_kernel<4>, g2, block, 0, sb, a, bx, pp, sel, c->d_pairpart, mv, mt, rj);
             HIPCHK(hipGetLastError());
+            contacts();
             c->pair_part_valid = true;
             c->recip_part_valid = true;
             c->call.recip_fused = true;
@@ -2088,6 +2254,7 @@ static int launch_pair_kernel(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &
         HIPCHK(launch_slot(c, GS_PAIR, pair_rd_es_kernel<2>, grid, block, sb, a, bx, pp, sel, c->d_pairpart, mv, mt));
     else
         HIPCHK(launch_slot(c, GS_PAIR, pair_rd_es_kernel<4>, grid, block, sb, a, bx, pp, sel, c->d_pairpart, mv, mt));
+    contacts();
     c->pair_part_valid = true;
     return 0;
 }
@@ -2210,6 +2377,104 @@ static int launch_at(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipSt
         hipLaunchKernelGGL(at_triple_kernel, grid, dim3(64 * kAtWaves), 0, sb, a, ta, bx, sel, ntile, c->at.part,
                            c->call.pair_moves);
     });
+}
+
+// polarvdw: au2invsec * halfHBAR * sum sqrt(max(lambda, 0)) of the matrix C of `na` sites (the run [first, first + na) of
+// the site list) -> out[0].  Build, 3 (n - 2) + 1 launches of the Householder reduction, bisection, sum: plain launches on
+// one stream, every trip count known here (kernels_vdw.h).
+static int vdw_eigen_sum(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, int first, int na, const MoveList &mv,
+                         double *out, hipStream_t sb) {
+    if (na <= 0) {  // a matrix of dimension 0: no eigenvalue (lapack_diag returns NULL, vdw.c:169)
+        HIPCHK(hipMemsetAsync(out, 0, sizeof(double), sb));
+        return 0;
+    }
+    const int n = 3 * na, ld = n;
+    const size_t nc = 3 * (size_t)std::max(c->vdw_na, 1);
+    double *C = c->d_vdw_C, *v = c->d_vdw_vec, *p = v + nc, *d = p + nc, *e = d + nc, *lam = e + nc, *scal = lam + nc;
+    const VdwSites s = {c->d_vdw_idx + first, c->d_vdw_k + first, na};
+    hipLaunchKernelGGL(vdw_build_kernel, dim3((na + 63) / 64, na), dim3(64), 0, sb, a, bx, c->par.polar_damp, s, C, ld, mv);
+    for (int j = 0; j < n - 2; ++j) {
+        const int mm = n - j - 1;
+        hipLaunchKernelGGL(vdw_reflect_kernel, dim3(1), dim3(kVdwReflectThreads), 0, sb, C, ld, n, j, v, scal, d, e);
+        hipLaunchKernelGGL(vdw_symv_kernel, dim3((mm + kVdwSymvWaves - 1) / kVdwSymvWaves), dim3(64 * kVdwSymvWaves), 0, sb, C, ld,
+                           n, j, v, scal, p);
+        hipLaunchKernelGGL(vdw_rank2_kernel, dim3((mm + kVdwUpdRows - 1) / kVdwUpdRows), dim3(64 * kVdwUpdWaves), 0, sb, C, ld, n,
+                           j, v, p, scal);
+    }
+    hipLaunchKernelGGL(vdw_reflect_kernel, dim3(1), dim3(kVdwReflectThreads), 0, sb, C, ld, n, n - 2, v, scal, d, e);
+    hipLaunchKernelGGL(vdw_bisect_kernel, dim3((n + 63) / 64), dim3(64), 0, sb, d, e, n, lam);
+    hipLaunchKernelGGL(vdw_sum_kernel, dim3(1), dim3(kVdwSumThreads), 0, sb, lam, d, e, n, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// polarvdw: e_iso of every molecule type that has none yet, from the first molecule of the type in this upload
+// (calc_e_iso, vdw.c:225-259), then the sum over the molecules in upload order (sum_eiso_vdw).  Runs on the main stream in
+// front of the evaluation and waits for it: once per type for as long as the mode stays on.
+static int vdw_ensure_iso(mpmc_hip_ctx *c) {
+    if (c->vdw_iso_summed) return 0;
+    const DevAtoms a = dev_atoms(c);
+    const DevBox bx = dev_box(c);
+    const size_t nc = 3 * (size_t)std::max(c->vdw_na, 1);
+    double *slot = c->d_vdw_vec + 5 * nc + 1;
+    for (const auto &m : c->vdw_mols) {
+        if (c->vdw_iso.count(m.type)) continue;
+        double v = 0.0;
+        if (vdw_eigen_sum(c, a, bx, m.first_site, m.sites, c->pending, slot, c->stream)) return -1;
+        HIPCHK(hipMemcpyAsync(&v, slot, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->vdw_iso[m.type] = v;
+    }
+    double s = 0.0;
+    for (const auto &m : c->vdw_mols) s += c->vdw_iso[m.type];
+    c->vdw_e_iso = s;
+    c->vdw_iso_summed = true;
+    return 0;
+}
+
+// polarvdw: the repulsion-only pair sum and its long-range correction (R_DISP, R_DISP_LRC), then lr_corr and the
+// eigenvalue sum of the whole configuration behind them on the same stream.  `a` carries zero epsilon / sigma in this
+// mode: the repulsion kernels get the real ones.
+static int launch_vdw(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipStream_t sb) {
+    const int ntile = c->npad / 64;
+    DevAtoms lj = a;
+    lj.eps = c->d_eps;
+    lj.sig = c->d_sig;
+    const DirtyBlocks all = {};
+    if (c->par.rd_lrc) {
+        if (static_pass(c, c->rep_lrc, !c->rep_lrc.valid, ntile * ntile, R_DISP_LRC, sb, [&] {
+                hipLaunchKernelGGL(rep_lrc_kernel, dim3(ntile, ntile), dim3(64 * kVdwLrcWaves), 0, sb, lj, bx, all, c->rep_lrc.part);
+            }))
+            return -1;
+    } else {
+        c->call.res_zero_mask |= 1u << R_DISP_LRC;
+        c->rep_lrc.valid = false;
+    }
+    if (tile_pass(c, c->rep, ntile * ntile, R_DISP, sb, [&](const DirtyBlocks &sel) {
+            hipLaunchKernelGGL(rep_tile_kernel, dim3(ntile, sel.n > 0 ? sel.n : ntile), dim3(64 * kRepWaves), 0, sb, lj, bx, sel,
+                               c->rep.part, c->call.pair_moves);
+        }))
+        return -1;
+    if (c->par.rd_only) {  // vdw() is not called under rd_only (energy.c:149-177)
+        c->call.res_zero_mask |= (1u << R_VDW) | (1u << R_VDW_LRC);
+        c->vdw.valid = c->vdw_lrc.valid = false;
+        return 0;
+    }
+    if (c->par.rd_lrc) {
+        if (static_pass(c, c->vdw_lrc, !c->vdw_lrc.valid, ntile * ntile, R_VDW_LRC, sb, [&] {
+                hipLaunchKernelGGL(vdw_lrc_kernel, dim3(ntile, ntile), dim3(64 * kVdwLrcWaves), 0, sb, a,
+                                   (const double *)c->d_vdw_w, bx, all, c->vdw_lrc.part);
+            }))
+            return -1;
+    } else {
+        c->call.res_zero_mask |= 1u << R_VDW_LRC;
+        c->vdw_lrc.valid = false;
+    }
+    if (c->vdw.valid && c->dirty_atoms.empty()) return 0;  // nothing moved: d_res[R_VDW] is still that sum
+    ScopedTimer t(c, T_OTHER, sb);
+    if (vdw_eigen_sum(c, a, bx, 0, c->vdw_na, c->call.pair_moves, c->d_res + R_VDW, sb)) return -1;
+    c->vdw.valid = true;
+    return 0;
 }
 
 static int launch_publish(mpmc_hip_ctx *c) {
@@ -2378,13 +2643,16 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
         } else if (c->rdc_order) {
             // ---- rd_crystal: Lennard-Jones over the lattice images, its self part and its long-range correction
             if (launch_rdc(c, a, bx, sb)) return -1;
+        } else if (c->vdw_on) {
+            // ---- polarvdw: repulsion-only Lennard-Jones, then the coupled-dipole term (it owns R_AT and R_RDC_SELF here)
+            if (launch_vdw(c, a, bx, sb)) return -1;
         } else {
             k.res_zero_mask |= (1u << R_DISP) | (1u << R_DISP_LRC) | (1u << R_RDC_SELF);
         }
         // ---- axilrod_teller: the triple-dipole sum over ALL triples that are not on one molecule
         if (c->at_on) {
             if (launch_at(c, a, bx, sb)) return -1;
-        } else {
+        } else if (!c->vdw_on) {
             k.res_zero_mask |= 1u << R_AT;
         }
 
@@ -2485,7 +2753,7 @@ static bool graph_eligible(mpmc_hip_ctx *c) {
     const mpmc_hip_params &P = c->par;
     const SweepView &v = c->view[0];
     if (!c->opt.graph || is_timed_call(c) || !c->opt.incremental || !c->opt.incremental_pairs ||
-        !c->opt.pair_coef || c->disp_on || c->at_on || c->rdc_order)
+        !c->opt.pair_coef || c->disp_on || c->at_on || c->rdc_order || c->vdw_on || c->autoreject_scale != 0.0)
         return false;
     if (P.rd_only || !P.polarization || P.polar_zodid || P.polar_gs || P.polar_gs_ranked || P.polar_precision != 0.0 ||
         P.polar_max_iter <= 0)
@@ -2588,7 +2856,21 @@ extern "C" int mpmc_hip_energy_begin(mpmc_hip_ctx *c) {
     if (c->disp_on && c->rdc_order)
         return fail("MPMC_HIP: energy: rd_crystal with disp_expansion is not implemented (the reference's disp_expansion() "
                     "ignores rd_crystal)");
+    if (c->vdw_on) {
+        if (c->disp_on)
+            return fail("MPMC_HIP: energy: polarvdw with disp_expansion (mpmc_hip_set_dispersion) is not implemented");
+        if (c->rdc_order)
+            return fail("MPMC_HIP: energy: polarvdw with rd_crystal (mpmc_hip_set_rd_crystal) is not implemented");
+        if (c->at_on)
+            return fail("MPMC_HIP: energy: polarvdw with axilrod_teller (mpmc_hip_set_axilrod_teller) is not implemented");
+        if (c->par.feynman_hibbs)
+            return fail("MPMC_HIP: energy: polarvdw with feynman_hibbs is not implemented (the reference's finite-difference "
+                        "correction cannot be matched)");
+    } else {
+        c->vdw_iso.clear();  // the mode is off: its e_iso cache goes
+    }
     HIPCHK(hipSetDevice(c->device));
+    if (c->vdw_on && !c->par.rd_only && vdw_ensure_iso(c)) return -1;
     if (c->resident_off && c->resident_backoff > 0 && (long)c->energy_calls >= c->resident_retry_at)
         c->resident_off = false;  // (one more attempt at the one-launch solve; a give-up doubles the interval)
     const mpmc_hip_params &P = c->par;
@@ -2745,6 +3027,7 @@ extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
     // (rd_crystal: the same, with the image sum, its self part and the correction at cutoff_c behind them)
     const double rd = c->disp_on     ? (r[R_RD_PAIR] + r[R_LRC]) + (r[R_DISP] + r[R_DISP_LRC])
                       : c->rdc_order ? (r[R_RD_PAIR] + r[R_LRC]) + ((r[R_DISP] + r[R_RDC_SELF]) + r[R_DISP_LRC])
+                      : c->vdw_on    ? (r[R_RD_PAIR] + r[R_LRC]) + (r[R_DISP] + r[R_DISP_LRC])  // polarvdw: repulsion only
                                      : r[R_RD_PAIR] + r[R_LRC];
     const double real = r[R_ES_REAL] - r[R_ES_INTRA];
     const bool ewald = !P.rd_only && !P.wolf;
@@ -2761,6 +3044,15 @@ extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
     out->energy = rd + coul + upol;  // energy.c:196
     c->three_body = c->at_on ? r[R_AT] : 0.0;
     if (c->at_on) out->energy += c->three_body;  // energy.c:194: behind the other terms (vdw_energy is 0 on this path)
+    // polarvdw: vdw_energy = e_total - e_iso + lr_corr (vdw.c:631; not under rd_only), added at energy.c:194-196
+    c->vdw_energy = (c->vdw_on && !P.rd_only) ? ((r[R_VDW] - c->vdw_e_iso) + 0.0) + r[R_VDW_LRC] : 0.0;
+    if (c->vdw_on) out->energy += c->vdw_energy;
+    c->vdw_terms[0] = (c->vdw_on && !P.rd_only) ? r[R_VDW] : 0.0;
+    c->vdw_terms[1] = (c->vdw_on && !P.rd_only) ? c->vdw_e_iso : 0.0;
+    c->vdw_terms[2] = (c->vdw_on && !P.rd_only) ? r[R_VDW_LRC] : 0.0;
+    c->vdw_terms[3] = c->vdw_on ? r[R_DISP] : 0.0;
+    c->vdw_terms[4] = c->vdw_on ? r[R_DISP_LRC] : 0.0;
+    c->close_contacts = c->autoreject_scale != 0.0 ? (long long)r[R_CONTACTS] : 0;
     out->dipole_rrms = do_polar ? r[R_RRMS] : 0.0;
     out->volume = c->volume;
     out->cutoff = c->cutoff;

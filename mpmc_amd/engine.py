@@ -17,7 +17,8 @@ EXPORTS = [
     "mpmc_hip_destroy", "mpmc_hip_set_option", "mpmc_hip_default_params", "mpmc_hip_set_params", "mpmc_hip_set_box",
     "mpmc_hip_scale_box",
     "mpmc_hip_upload", "mpmc_hip_set_dispersion", "mpmc_hip_set_axilrod_teller", "mpmc_hip_get_three_body_energy",
-    "mpmc_hip_set_rd_crystal",
+    "mpmc_hip_set_rd_crystal", "mpmc_hip_set_vdw", "mpmc_hip_get_vdw_energy", "mpmc_hip_get_vdw_terms",
+    "mpmc_hip_set_autoreject", "mpmc_hip_get_close_contacts",
     "mpmc_hip_update_atoms", "mpmc_hip_insert_molecule", "mpmc_hip_remove_molecule",
     "mpmc_hip_slot_count", "mpmc_hip_set_sweep_order", "mpmc_hip_energy", "mpmc_hip_energy_begin", "mpmc_hip_energy_end",
     "mpmc_hip_download_dipoles",
@@ -116,9 +117,12 @@ PARAM_NAMES = [f[0] for f in Params._fields_]
 DISP_NAMES = [f[0] for f in DispParams._fields_]
 AT_NAMES = ["axilrod_teller", "midzuno_kihara_approx"]  # mpmc_hip_set_axilrod_teller (reference keywords)
 RDC_NAMES = ["rd_crystal", "rd_crystal_order"]  # mpmc_hip_set_rd_crystal (reference keywords)
+VDW_NAMES = ["polarvdw", "cdvdw"]  # mpmc_hip_set_vdw (reference keywords)
+AUTOREJECT_NAMES = ["cavity_autoreject_absolute", "cavity_autoreject_scale"]  # mpmc_hip_set_autoreject (reference keywords)
+VDW_TERMS = ["e_total", "e_iso", "lr_corr", "repulsion", "repulsion_lrc"]  # mpmc_hip_get_vdw_terms, in its order
 # flags that make_params() leaves to others: pbc_cutoff is a box property at this boundary (set_box), the rest are the
-# arguments of the three calls above (Engine.load_system)
-NOT_PARAMS = frozenset(["pbc_cutoff"] + DISP_NAMES + AT_NAMES + RDC_NAMES)
+# arguments of the calls above (Engine.load_system)
+NOT_PARAMS = frozenset(["pbc_cutoff"] + DISP_NAMES + AT_NAMES + RDC_NAMES + VDW_NAMES + AUTOREJECT_NAMES)
 AT_ALPHA_AU = 6.7483345  # A^3 -> Bohr^3, as the reference writes it (axilrod_teller.cpp:115)
 
 _lib = None
@@ -153,6 +157,11 @@ def load():
     lib.mpmc_hip_set_axilrod_teller.argtypes = [vp, C.c_int, C.c_int, vp]
     lib.mpmc_hip_get_three_body_energy.argtypes = [vp, dp]
     lib.mpmc_hip_set_rd_crystal.argtypes = [vp, C.c_int]
+    lib.mpmc_hip_set_vdw.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+    lib.mpmc_hip_get_vdw_energy.argtypes = [vp, dp]
+    lib.mpmc_hip_get_vdw_terms.argtypes = [vp, dp]
+    lib.mpmc_hip_set_autoreject.argtypes = [vp, C.c_double]
+    lib.mpmc_hip_get_close_contacts.argtypes = [vp, C.POINTER(C.c_longlong)]
     lib.mpmc_hip_update_atoms.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     lib.mpmc_hip_insert_molecule.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
     lib.mpmc_hip_remove_molecule.argtypes = [vp, C.c_int, C.c_int]
@@ -294,6 +303,41 @@ class Engine:
         mode off.  A context setting: it persists across uploads."""
         _chk(self.lib.mpmc_hip_set_rd_crystal(self.ctx, int(order)))
 
+    def set_vdw(self, system, enable=True):
+        """Coupled-dipole van der Waals + repulsion-only Lennard-Jones (mpmc_hip_set_vdw), after upload(): the per-atom
+        omega of `system` (atomic units) and its per-atom mol_type ids.  enable=False switches the mode off."""
+        if not enable:
+            _chk(self.lib.mpmc_hip_set_vdw(self.ctx, 0, 0, None, None))
+            return
+        omega = np.ascontiguousarray(system["omega"], dtype=np.float64)
+        mtype = np.ascontiguousarray(system["mol_type"], dtype=np.int32)
+        if omega.shape != (self.n,) or mtype.shape != (self.n,):
+            raise ValueError("omega and mol_type must have one entry per uploaded atom")
+        _chk(self.lib.mpmc_hip_set_vdw(self.ctx, 1, self.n, omega.ctypes.data, mtype.ctypes.data))
+
+    def vdw_energy(self):
+        """observables->vdw_energy of the last completed energy(); 0 while the mode is off."""
+        v = C.c_double(0.0)
+        _chk(self.lib.mpmc_hip_get_vdw_energy(self.ctx, C.byref(v)))
+        return v.value
+
+    def vdw_terms(self):
+        """e_total, e_iso, lr_corr, repulsion, repulsion_lrc of the last completed energy() (mpmc_hip_get_vdw_terms)."""
+        t = (C.c_double * 5)()
+        _chk(self.lib.mpmc_hip_get_vdw_terms(self.ctx, t))
+        return dict(zip(VDW_TERMS, [float(x) for x in t]))
+
+    def set_autoreject(self, scale):
+        """cavity_autoreject_absolute (mpmc_hip_set_autoreject): scale = cavity_autoreject_scale; 0 switches it off.  A
+        context setting: it persists across uploads."""
+        _chk(self.lib.mpmc_hip_set_autoreject(self.ctx, float(scale)))
+
+    def close_contacts(self):
+        """Different-molecule pairs closer than the scale in the last completed energy(); 0 while the setting is off."""
+        v = C.c_longlong(0)
+        _chk(self.lib.mpmc_hip_get_close_contacts(self.ctx, C.byref(v)))
+        return v.value
+
     def three_body_energy(self):
         """observables->three_body_energy of the last completed energy(); 0 while the term is off."""
         v = C.c_double(0.0)
@@ -302,16 +346,22 @@ class Engine:
 
     def load_system(self, system, params):
         """Convenience: params (incl. optional pbc_cutoff) + box + atoms (+ the dispersion record when the flags carry
-        disp_expansion, + the three-body coefficients when they carry axilrod_teller).  rd_crystal / rd_crystal_order among
+        disp_expansion, + the three-body coefficients when they carry axilrod_teller, + omega and the type ids when they
+        carry polarvdw).  cavity_autoreject_absolute + cavity_autoreject_scale switch the close-contact count on; without
+        them it is switched off.  rd_crystal / rd_crystal_order among
         the flags switch the image sum on (order 1 when only rd_crystal is given); without them it is switched off."""
         self.set_params(**params)
         self.set_rd_crystal(int(params.get("rd_crystal_order", 1)) if params.get("rd_crystal") else 0)
+        self.set_autoreject(float(params.get("cavity_autoreject_scale", 0.0))
+                            if params.get("cavity_autoreject_absolute") else 0.0)
         self.set_box(system["basis"], params.get("pbc_cutoff", 0.0))
         self.upload(system)
         if params.get("disp_expansion"):
             self.set_dispersion(system, **{k: params[k] for k in DISP_NAMES if k in params})
         if params.get("axilrod_teller"):
             self.set_axilrod_teller(system, midzuno_kihara_approx=bool(params.get("midzuno_kihara_approx")))
+        if params.get("polarvdw") or params.get("cdvdw"):
+            self.set_vdw(system)
 
     def update_atoms(self, first, pos):
         pos = np.ascontiguousarray(pos, dtype=np.float64)

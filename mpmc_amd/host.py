@@ -85,6 +85,13 @@ def load():
     lib.host_set_c9.restype = None
     lib.host_get_three_body_energy.argtypes = [vp]
     lib.host_get_three_body_energy.restype = C.c_double
+    lib.host_get_vdw.argtypes = [vp, vp]
+    lib.host_get_vdw.restype = None
+    lib.host_get_omega.argtypes = [vp, vp]
+    lib.host_get_omega.restype = None
+    lib.host_set_omega.argtypes = [vp, vp, vp]
+    lib.host_set_omega.restype = None
+    lib.host_displace_molecule.argtypes = [vp, C.c_int, vp]
     lib.host_get_rdc_flags.argtypes = [vp, vp]
     lib.host_get_rdc_flags.restype = None
     lib.host_read_frame.argtypes = [vp, C.c_char_p, C.c_int]
@@ -103,10 +110,13 @@ def config_text(flags, extra=None):
     onoff = {"rd_only", "rd_lrc", "feynman_hibbs", "polarization", "polar_gs", "polar_gs_ranked", "polar_sor",
              "polar_esor", "polar_palmo", "polar_rrms", "polar_zodid", "polar_wolf", "polar_ewald", "wolf",
              "disp_expansion", "damp_dispersion", "extrapolate_disp_coeffs", "schmidt_mixing", "axilrod_teller",
-             "midzuno_kihara_approx", "rd_crystal", "read_pqr_box", "calc_pressure"}
+             "midzuno_kihara_approx", "rd_crystal", "read_pqr_box", "calc_pressure", "polarvdw", "cdvdw",
+             "cavity_autoreject_absolute", "cdvdw_exp_repulsion", "cdvdw_sig_repulsion", "cdvdw_9th_repulsion"}
     lines = []
     for k, v in flags.items():
-        if k in onoff:
+        if k in ("polarvdw", "cdvdw") and isinstance(v, str):
+            lines.append("%s %s" % (k, v))  # evects / comp
+        elif k in onoff:
             lines.append("%s %s" % (k, "on" if v else "off"))
         elif k in ("ewald_alpha_set", "polar_ewald_alpha_set"):
             continue
@@ -158,6 +168,10 @@ class HostSystem:
         if "c9" in system:  # axilrod_teller: per-atom three-body coefficient (atomic units)
             c9 = np.ascontiguousarray(system["c9"], dtype=np.float64)
             self.lib.host_set_c9(self.ptr, c9.ctypes.data)
+        if "omega" in system:  # polarvdw: per-atom frequency (atomic units) and the molecules' type ids
+            w = np.ascontiguousarray(system["omega"], dtype=np.float64)
+            t = np.ascontiguousarray(system.get("mol_type", np.zeros(n)), dtype=np.int32)
+            self.lib.host_set_omega(self.ptr, w.ctypes.data, t.ctypes.data)
         extra = dict({"move_factor": move_factor, "rot_factor": rot_factor}, **(extra or {}))
         if self.lib.host_apply_config(self.ptr, config_text(flags, extra).encode()) != 0:
             raise ValueError("host layer rejected the configuration")
@@ -181,6 +195,19 @@ class HostSystem:
     def three_body_energy(self):
         """observables->three_body_energy of the last energy() (0 unless axilrod_teller is on)."""
         return self.lib.host_get_three_body_energy(self.ptr)
+
+    def displace_molecule(self, index, d):
+        """The index-th molecule of the list steps by d, outside Metropolis (a test entry)."""
+        v = np.ascontiguousarray(d, dtype=np.float64)
+        if self.lib.host_displace_molecule(self.ptr, int(index), v.ctypes.data) != 0:
+            raise IndexError(index)
+
+    def vdw(self):
+        """polarvdw / cavity_autoreject_absolute state: the keywords as read, count_autorejects, observables->vdw_energy."""
+        out = np.zeros(5)
+        self.lib.host_get_vdw(self.ptr, out.ctypes.data)
+        return dict(polarvdw=int(out[0]), cavity_autoreject_absolute=int(out[1]), cavity_autoreject_scale=out[2],
+                    count_autorejects=int(out[3]), vdw_energy=out[4])
 
     def observables(self):
         out = np.zeros(8)

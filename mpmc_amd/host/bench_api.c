@@ -28,6 +28,9 @@ int host_apply_config(system_t *system, const char *text) {
     if (system->ensemble == ENSEMBLE_UVT && !(system->fugacity > 0.0)) return 1;
     if (system->ensemble == ENSEMBLE_NPT && !(system->pressure > 0.0)) return 1; /* check_input.c:673-678 */
     if (system->rd_crystal && system->rd_crystal_order <= 0) return 1;            /* check_input.c:1258-1263 */
+    if (system->cavity_autoreject_absolute &&                                     /* check_input.c:872-878 */
+        ((system->cavity_autoreject_scale <= 0.0) || (system->cavity_autoreject_scale > 1.78)))
+        return 1;
     return 0;
 }
 
@@ -246,6 +249,39 @@ void host_set_c9(system_t *system, const double *c9) {
         for (atom_t *a = m->atoms; a; a = a->next, i++) a->c9 = c9[i];
 }
 double host_get_three_body_energy(system_t *system) { return system->observables->three_body_energy; }
+/* ---- polarvdw and cavity_autoreject_absolute ------------------------------------------------------------------ */
+/* polarvdw, cavity_autoreject_absolute, cavity_autoreject_scale, count_autorejects, observables->vdw_energy */
+void host_get_vdw(system_t *system, double out[5]) {
+    out[0] = (double)system->polarvdw;
+    out[1] = (double)system->cavity_autoreject_absolute;
+    out[2] = system->cavity_autoreject_scale;
+    out[3] = (double)system->count_autorejects;
+    out[4] = system->observables->vdw_energy;
+}
+void host_get_omega(system_t *system, double *omega) {
+    int i = 0;
+    for (molecule_t *m = system->molecules; m; m = m->next)
+        for (atom_t *a = m->atoms; a; a = a->next, i++) omega[i] = a->omega;
+}
+/* per-atom omega (atomic units) and type id of a system built from arrays: the molecule type becomes "T<id>" */
+void host_set_omega(system_t *system, const double *omega, const int *mol_type) {
+    int i = 0;
+    for (molecule_t *m = system->molecules; m; m = m->next) {
+        if (m->atoms) snprintf(m->moleculetype, MAXLINE, "T%d", mol_type[i]);
+        for (atom_t *a = m->atoms; a; a = a->next, i++) a->omega = omega[i];
+    }
+}
+/* test entry: the index-th molecule of the list steps by d, outside Metropolis; the next energy() finds it by walking
+ * the lists.  Returns non-zero when there is no such molecule. */
+int host_displace_molecule(system_t *system, int index, const double d[3]) {
+    molecule_t *m = system->molecules;
+    for (int k = 0; m && k < index; k++) m = m->next;
+    if (!m || index < 0) return 1;
+    for (atom_t *a = m->atoms; a; a = a->next)
+        for (int p = 0; p < 3; p++) a->pos[p] += d[p];
+    energy_hip_note_list_changed(system);
+    return 0;
+}
 /* ---- rd_crystal and ensemble replay ---------------------------------------------------------------------------- */
 void host_get_rdc_flags(system_t *system, int out[2]) {
     out[0] = system->rd_crystal;

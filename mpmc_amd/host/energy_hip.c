@@ -49,6 +49,8 @@ typedef struct shim_state {
     int capacity; /* atoms the context was created for */
     int uploaded; /* a configuration is resident */
     int rdc_order; /* rd_crystal_order as sent with that upload (0: rd_crystal off) */
+    int vdw_on;    /* polarvdw as sent with that upload */
+    double ar_scale; /* cavity_autoreject_scale as sent with that upload (0: cavity_autoreject_absolute off) */
     int failed;   /* device / ABI failure of the last call */
     mpmc_hip_params params; /* as last sent */
     /* host image of the device, by DEVICE SLOT (the engine keeps its own atom order once molecules are inserted
@@ -57,6 +59,7 @@ typedef struct shim_state {
     double *x, *y, *z, *q, *alpha, *eps, *sig, *mass;
     double *c6, *c8, *c10; /* disp_expansion: sent with every full upload (mpmc_hip_set_dispersion) */
     double *c9;            /* axilrod_teller: per atom as read; its effective value goes with every full upload */
+    double *omega;         /* polarvdw: sent with every full upload (mpmc_hip_set_vdw) */
     mpmc_hip_disp_params disp; /* as last sent */
     /* the resident molecules in LIST order */
     resident_t *res, *res2;
@@ -95,9 +98,9 @@ static shim_state *state_of(system_t *system, int create) {
 
 static void free_image(shim_state *st) {
     free(st->x); free(st->y); free(st->z); free(st->q); free(st->alpha); free(st->eps); free(st->sig); free(st->mass);
-    free(st->c6); free(st->c8); free(st->c10); free(st->c9);
+    free(st->c6); free(st->c8); free(st->c10); free(st->c9); free(st->omega);
     st->x = st->y = st->z = st->q = st->alpha = st->eps = st->sig = st->mass = NULL;
-    st->c6 = st->c8 = st->c10 = st->c9 = NULL;
+    st->c6 = st->c8 = st->c10 = st->c9 = st->omega = NULL;
     st->cap = 0;
 }
 
@@ -226,21 +229,36 @@ static void fill_disp_params(const system_t *s, mpmc_hip_disp_params *d) {
  * src/io/check_input.c:325-341, extended to the whole of energy()). */
 static const char *unsupported(const system_t *s) {
 #ifndef MPMC_SHIM_HOST_MIRROR
-    if (s->sg || s->dreiding || s->lj_buffered_14_7 || s->rd_anharmonic || s->cdvdw_exp_repulsion ||
-        s->gwp || s->spectre)
+    if (s->sg || s->dreiding || s->lj_buffered_14_7 || s->rd_anharmonic || s->gwp || s->spectre)
         return "only Lennard-Jones or disp_expansion repulsion / dispersion (with or without axilrod_teller) and point "
                "charges are on the device";
-    /* pairs.c:85-141: these mixing branches come before the disp_expansion one (sg, cdvdw_sig_repulsion, polarvdw and
-     * cdvdw_exp_repulsion are refused above and below) */
-    if (s->disp_expansion && (s->waldmanhagler || s->halgren_mixing || s->cdvdw_9th_repulsion))
-        return "disp_expansion with waldmanhagler / halgren_mixing / cdvdw_9th_repulsion is not on the device";
-    if (s->polarvdw || s->cdvdw_sig_repulsion) return "coupled-dipole van der Waals is not on the device";
-    if (s->cavity_autoreject_absolute) return "cavity_autoreject_absolute needs the pair list";
+    /* pairs.c:85-141: these mixing branches come before the disp_expansion one (sg is refused above, the cdvdw_*
+     * repulsions below) */
+    if (s->disp_expansion && (s->waldmanhagler || s->halgren_mixing))
+        return "disp_expansion with waldmanhagler / halgren_mixing is not on the device";
+    if (s->polarvdw && (s->waldmanhagler || s->halgren_mixing))
+        return "polarvdw with waldmanhagler / halgren_mixing is not on the device";
+    if (s->polarvdw && s->vdw_fh_2be) return "vdw_fh_2be is not on the device";
     if (s->polarization && !s->polar_iterative) return "iterative Thole solver only (polar_iterative on)";
     if (s->polarization && s->damp_type != DAMPING_EXPONENTIAL) return "exponential Thole damping only";
     if (s->polarization && (s->polar_ewald_full || s->polar_wolf_full)) return "polar_ewald_full / polar_wolf_full are not on the device";
     if (s->ensemble == ENSEMBLE_NVE) return "ensemble nve is not supported";
 #endif
+    /* polarvdw: the coupled-dipole term with repulsion-only Lennard-Jones is on the device; the rest is refused by name */
+    if (s->cdvdw_exp_repulsion) return "cdvdw_exp_repulsion is not on the device";
+    if (s->cdvdw_sig_repulsion) return "cdvdw_sig_repulsion is not on the device";
+    if (s->cdvdw_9th_repulsion) return "cdvdw_9th_repulsion is not on the device";
+    if (s->polarvdw == 2) return "polarvdw evects (eigenvectors) is not on the device";
+    if (s->polarvdw == 3) return "polarvdw comp (two-body comparison) is not on the device";
+    if (s->polarvdw && s->feynman_hibbs)
+        return "feynman_hibbs with polarvdw is not on the device (the reference's finite-difference correction divides "
+               "eigensolver noise by 1e-8 and cannot be matched)";
+    if (s->polarvdw && !s->polarization) return "polarvdw without polarization (the reference would read an unbuilt A matrix)";
+    if (s->polarvdw && !s->cavity_autoreject_absolute && s->ensemble != ENSEMBLE_REPLAY)
+        return "cavity_autoreject_absolute must be used with polarvdw + Feynman Hibbs."; /* check_input.c:216-219 */
+    if (s->polarvdw && s->disp_expansion) return "disp_expansion with polarvdw is not on the device";
+    if (s->polarvdw && s->rd_crystal) return "rd_crystal with polarvdw is not on the device";
+    if (s->polarvdw && s->axilrod_teller) return "axilrod_teller with polarvdw is not on the device";
     /* rd_crystal (Lennard-Jones over lattice images) is on the device up to order 4; disp_expansion() ignores it */
     if (s->rd_crystal && s->disp_expansion) return "rd_crystal with disp_expansion is not on the device";
     if (s->rd_crystal && s->rd_crystal_order > 4) return "rd_crystal_order above 4 is not on the device";
@@ -282,9 +300,9 @@ static int image_reserve(shim_state *st, int cap) {
     const size_t b = (size_t)cap * sizeof(double);
     st->x = malloc(b); st->y = malloc(b); st->z = malloc(b); st->q = malloc(b); st->alpha = malloc(b);
     st->eps = malloc(b); st->sig = malloc(b); st->mass = malloc(b);
-    st->c6 = malloc(b); st->c8 = malloc(b); st->c10 = malloc(b); st->c9 = malloc(b);
+    st->c6 = malloc(b); st->c8 = malloc(b); st->c10 = malloc(b); st->c9 = malloc(b); st->omega = malloc(b);
     if (!(st->x && st->y && st->z && st->q && st->alpha && st->eps && st->sig && st->mass && st->c6 && st->c8 && st->c10 &&
-          st->c9))
+          st->c9 && st->omega))
         return -1;
     st->cap = cap;
     return 0;
@@ -322,6 +340,15 @@ static int natoms_of(const molecule_t *m) {
     return k;
 }
 
+/* two moleculetype strings compare equal (what strncmp(a, b, MAXLINE) == 0 says, vdw.c:273) */
+static int same_type(const char *a, const char *b) {
+    for (int k = 0; k < MAXLINE; k++) {
+        if (a[k] != b[k]) return 0;
+        if (!a[k]) break;
+    }
+    return 1;
+}
+
 /* whole configuration, slots = list order */
 static int full_upload(shim_state *st, system_t *system) {
     const int n = system->natoms;
@@ -346,7 +373,7 @@ static int full_upload(shim_state *st, system_t *system) {
             st->x[i] = a->pos[0]; st->y[i] = a->pos[1]; st->z[i] = a->pos[2];
             st->q[i] = a->charge; st->alpha[i] = a->polarizability; st->eps[i] = a->epsilon; st->sig[i] = a->sigma;
             st->mass[i] = a->mass;
-            st->c6[i] = a->c6; st->c8[i] = a->c8; st->c10[i] = a->c10; st->c9[i] = a->c9;
+            st->c6[i] = a->c6; st->c8[i] = a->c8; st->c10[i] = a->c10; st->c9[i] = a->c9; st->omega[i] = a->omega;
             mol[i] = mi; /* list position: distinct per molecule even if PQR ids repeat */
             fz[i] = (uint8_t)(a->frozen != 0);
         }
@@ -382,6 +409,31 @@ static int full_upload(shim_state *st, system_t *system) {
         free(eff);
         if (rc) return hip_fail("set_axilrod_teller");
     }
+    st->vdw_on = (system->polarvdw != 0);
+    if (st->vdw_on) {
+        /* type ids: the first-seen order of moleculetype, which is what the reference's e_iso list is keyed by
+         * (vdw.c:262-320) */
+        int *type = malloc((n > 0 ? n : 1) * sizeof(int));
+        molecule_t **seen = malloc((nm > 0 ? nm : 1) * sizeof(molecule_t *));
+        if (!type || !seen) {
+            free(type); free(seen);
+            error("ENERGY: HIP engine: out of host memory\n");
+            return -1;
+        }
+        int nseen = 0, k = 0;
+        for (int mi = 0; mi < nm; mi++) {
+            molecule_t *m = st->mols[mi];
+            int t = 0;
+            while (t < nseen && !same_type(seen[t]->moleculetype, m->moleculetype)) t++;
+            if (t == nseen) seen[nseen++] = m;
+            for (atom_t *a = m->atoms; a; a = a->next) type[k++] = t;
+        }
+        rc = mpmc_hip_set_vdw(st->ctx, 1, n, st->omega, type);
+        free(type); free(seen);
+        if (rc) return hip_fail("set_vdw");
+    }
+    st->ar_scale = system->cavity_autoreject_absolute ? system->cavity_autoreject_scale : 0.0;
+    if (mpmc_hip_set_autoreject(st->ctx, st->ar_scale)) return hip_fail("set_autoreject");
     st->uploaded = 1;
     st->in_sync = 1;
     st->nnotes = 0;
@@ -475,7 +527,7 @@ static int same_species(const shim_state *st, const molecule_t *m, const residen
         if (k == r->natoms) return 0;
         if (a->charge != st->q[s + k] || a->polarizability != st->alpha[s + k] || a->epsilon != st->eps[s + k] ||
             a->sigma != st->sig[s + k] || a->mass != st->mass[s + k] || a->c6 != st->c6[s + k] || a->c8 != st->c8[s + k] ||
-            a->c10 != st->c10[s + k] || a->c9 != st->c9[s + k])
+            a->c10 != st->c10[s + k] || a->c9 != st->c9[s + k] || a->omega != st->omega[s + k])
             return 0;
     }
     return k == r->natoms;
@@ -586,13 +638,13 @@ static int sync_walk(shim_state *st, system_t *system) {
     for (int f = 0; f < nfresh; f++) {
         resident_t *r = &out[fresh[f]];
         double tx[64], ty[64], tz[64], q[64], al[64], ep[64], sg[64], ms[64];
-        double d6[64], d8[64], d10[64], d9[64]; /* not sent (Lennard-Jones mode), but part of the image same_species() reads */
+        double d6[64], d8[64], d10[64], d9[64], dw[64]; /* not sent (Lennard-Jones mode), but part of the image same_species() reads */
         int k = 0;
         for (atom_t *a = r->mol->atoms; a; a = a->next, k++) {
             if (k == 64) return 1;
             tx[k] = a->pos[0]; ty[k] = a->pos[1]; tz[k] = a->pos[2];
             q[k] = a->charge; al[k] = a->polarizability; ep[k] = a->epsilon; sg[k] = a->sigma; ms[k] = a->mass;
-            d6[k] = a->c6; d8[k] = a->c8; d10[k] = a->c10; d9[k] = a->c9;
+            d6[k] = a->c6; d8[k] = a->c8; d10[k] = a->c10; d9[k] = a->c9; dw[k] = a->omega;
         }
         int s = -1;
         const int rc = mpmc_hip_insert_molecule(st->ctx, k, tx, ty, tz, q, al, ep, sg, ms, r->frozen, &s);
@@ -602,6 +654,7 @@ static int sync_walk(shim_state *st, system_t *system) {
             st->x[s + a] = tx[a]; st->y[s + a] = ty[a]; st->z[s + a] = tz[a];
             st->q[s + a] = q[a]; st->alpha[s + a] = al[a]; st->eps[s + a] = ep[a]; st->sig[s + a] = sg[a]; st->mass[s + a] = ms[a];
             st->c6[s + a] = d6[a]; st->c8[s + a] = d8[a]; st->c10[s + a] = d10[a]; st->c9[s + a] = d9[a];
+            st->omega[s + a] = dw[a];
         }
         r->slot = s;
     }
@@ -660,6 +713,8 @@ int energy_hip_begin(system_t *system) {
         fill_disp_params(system, &dnow);
         if (memcmp(&dnow, &st->disp, sizeof(dnow))) need_upload = 1;
         if ((system->rd_crystal ? system->rd_crystal_order : 0) != st->rdc_order) need_upload = 1;
+        if ((system->polarvdw != 0) != st->vdw_on) need_upload = 1;
+        if ((system->cavity_autoreject_absolute ? system->cavity_autoreject_scale : 0.0) != st->ar_scale) need_upload = 1;
     }
     if (!need_upload && scale_box) {
         const int rc = apply_volume_notes(st, system);
@@ -761,6 +816,25 @@ double energy_hip_end(system_t *system) {
         }
     }
     observables_t *o = system->observables;
+    if (system->cavity_autoreject_absolute) {
+        long long contacts = 0;
+        if (mpmc_hip_get_close_contacts(st->ctx, &contacts)) {
+            hip_fail("get_close_contacts");
+            device_failed(st);
+            return NAN;
+        }
+        if (contacts > 0) {
+            /* energy.c:99-102, :187-194: a bad contact.  The potential energy is MAXVALUE, the rejection is counted, and
+             * the terms of the observables stay what the previous call left (the reference skips their evaluation; here
+             * the device evaluated them beside the count and they are dropped) */
+            system->count_autorejects++;
+            o->energy = MAXVALUE;
+            if (o->N > 0.0) o->spin_ratio /= o->N;     /* energy.c:211 */
+            o->NU = o->N * o->energy;                  /* energy.c:220 */
+            system->last_volume = system->pbc->volume; /* energy.c:223 */
+            return o->energy;
+        }
+    }
     o->rd_energy = r.rd_energy;
     o->coulombic_energy = r.coulombic_energy;
     o->polarization_energy = r.polarization_energy;
@@ -768,6 +842,12 @@ double energy_hip_end(system_t *system) {
     o->three_body_energy = 0.0; /* energy.c:148-151, :194: part of o->energy when axilrod_teller is on */
     if (system->axilrod_teller && mpmc_hip_get_three_body_energy(st->ctx, &o->three_body_energy)) {
         hip_fail("get_three_body_energy");
+        device_failed(st);
+        return NAN;
+    }
+    /* energy.c:165-177: assigned only while polarvdw is on and rd_only is off; part of o->energy then */
+    if (system->polarvdw && !system->rd_only && mpmc_hip_get_vdw_energy(st->ctx, &o->vdw_energy)) {
+        hip_fail("get_vdw_energy");
         device_failed(st);
         return NAN;
     }

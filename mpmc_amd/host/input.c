@@ -127,6 +127,14 @@ int do_command(system_t *system, char **token) {
     INT("corrtime", corrtime);
     REAL("move_factor", move_factor);
     REAL("rot_factor", rot_factor);
+    if (!strcasecmp(k, "move_probability")) { /* input.c:606-615: the deprecated names, still in the sample inputs */
+        output("WARNING: move_probability is deprecated, use move_factor instead\n");
+        return safe_atof(v, &system->move_factor);
+    }
+    if (!strcasecmp(k, "rot_probability")) {
+        output("WARNING: rot_probability is deprecated, use rot_factor instead\n");
+        return safe_atof(v, &system->rot_factor);
+    }
     REAL("temperature", temperature);
     REAL("scale_charge", scale_charge);
     REAL("insert_probability", insert_probability);
@@ -157,6 +165,29 @@ int do_command(system_t *system, char **token) {
     FLAG("axilrod_teller", axilrod_teller); /* input.c:992-1013 */
     FLAG("midzuno_kihara_approx", midzuno_kihara_approx);
     FLAG("rd_crystal", rd_crystal); /* input.c:814-826 */
+    if (!strcasecmp(k, "polarvdw") || !strcasecmp(k, "cdvdw")) { /* input.c:446-475 */
+        if (!strcasecmp(v, "off")) {
+            system->polarvdw = 0;
+            return 0;
+        }
+        if (!strcasecmp(v, "on"))
+            system->polarvdw = 1;
+        else if (!strcasecmp(v, "evects"))
+            system->polarvdw = 2; /* refused by energy_hip.c, by name */
+        else if (!strcasecmp(v, "comp"))
+            system->polarvdw = 3; /* likewise */
+        else
+            return 1;
+        system->polarization = 1;
+        system->polar_iterative = 1;
+        output("INPUT: Forcing polar_iterative ON for CP-VdW.\n");
+        return 0;
+    }
+    FLAG("cdvdw_9th_repulsion", cdvdw_9th_repulsion); /* these three are refused by energy_hip.c, each by name */
+    FLAG("cdvdw_exp_repulsion", cdvdw_exp_repulsion);
+    FLAG("cdvdw_sig_repulsion", cdvdw_sig_repulsion);
+    FLAG("cavity_autoreject_absolute", cavity_autoreject_absolute); /* input.c:413-427 */
+    REAL("cavity_autoreject_scale", cavity_autoreject_scale);
     INT("rd_crystal_order", rd_crystal_order);
     FLAG("read_pqr_box", read_pqr_box_on); /* input.c:1448-1455 */
     FLAG("calc_pressure", calc_pressure);  /* input.c:575-582; refused by name in replay (check_system) */
@@ -299,8 +330,13 @@ molecule_t *read_molecules(FILE *fp, system_t *system) {
         a->polarizability = atof(t[11]);
         a->epsilon = atof(t[12]);
         a->sigma = atof(t[13]);
-        /* t[14], t[15]: omega and gwp_alpha (not used here); then c6, c8, c10 and c9 in atomic units (read_pqr.c:216,
-         * :255-258); absent columns read as 0 */
+        if (system->polarvdw && !system->cdvdw_exp_repulsion && a->sigma != 1.0) { /* read_pqr.c:266-271 */
+            error("warning: setting sigma to 1.0 (due to polarvdw)\n");
+            a->sigma = 1.0;
+        }
+        /* t[14]: omega in atomic units (polarvdw); t[15]: gwp_alpha (not used here); then c6, c8, c10 and c9 in atomic
+         * units (read_pqr.c:216, :253-258); absent columns read as 0 */
+        a->omega = atof(t[14]);
         a->c6 = atof(t[16]);
         a->c8 = atof(t[17]);
         a->c10 = atof(t[18]);
@@ -385,6 +421,18 @@ static int check_system(system_t *system) {
         }
         snprintf(linebuf, MAXLINE, "INPUT: rd crystal order set to %d.\n", system->rd_crystal_order);
         output(linebuf);
+    }
+    if (system->polarvdw && !system->cavity_autoreject_absolute && system->ensemble != ENSEMBLE_REPLAY) {
+        error("INPUT: cavity_autoreject_absolute must be used with polarvdw + Feynman Hibbs.\n"); /* check_input.c:216-221 */
+        return -1;
+    }
+    if (system->polarvdw) output("INPUT: polarvdw (coupled-dipole van der Waals) activated\n"); /* check_input.c:495-497 */
+    if (system->cavity_autoreject_absolute) { /* check_input.c:872-878 */
+        output("INPUT: cavity autoreject absolute activated\n");
+        if ((system->cavity_autoreject_scale <= 0.0) || (system->cavity_autoreject_scale > 1.78)) {
+            error("INPUT: cavity_autoreject_scale either not set or out of range\n");
+            return -1;
+        }
     }
     if (system->ensemble == ENSEMBLE_NPT && !(system->pressure > 0.0)) { /* check_input.c:673-678 */
         error("INPUT: invalid pressure set for NPT\n");
@@ -547,13 +595,15 @@ int write_molecules(system_t *system, const char *filename) {
     int i = 1;
     for (molecule_t *m = system->molecules; m; m = m->next)
         for (atom_t *a = m->atoms; a; a = a->next, i++)
-            /* omega and gwp_alpha (not held here: 0), then c6 c8 c10 c9, as output.c:436-447 writes them: a restart from
-             * this file keeps the dispersion coefficients of a disp_expansion / axilrod_teller run */
+            /* omega (written only while polarvdw is on: every other run's file stays what it was) and gwp_alpha (not held
+             * here: 0), then c6 c8 c10 c9, as output.c:436-447 writes them: a restart from this file keeps the dispersion
+             * coefficients of a disp_expansion / axilrod_teller run and the frequencies of a polarvdw run */
             fprintf(fp, "ATOM  %5d %-4.45s %-3.3s %-1.1s %4d   %8.3f%8.3f%8.3f %8.5f %8.5f %8.5f %8.5f %8.5f %8.5f %8.5f %8.5f "
                         "%8.5f %8.5f %8.5f\n", i,
                     a->atomtype[0] ? a->atomtype : "X", m->moleculetype[0] ? m->moleculetype : "M",
                     m->frozen ? "F" : "M", m->id, a->pos[0], a->pos[1], a->pos[2], a->mass, a->charge / E2REDUCED,
-                    a->polarizability, a->epsilon, a->sigma, 0.0, 0.0, a->c6, a->c8, a->c10, a->c9);
+                    a->polarizability, a->epsilon, a->sigma, system->polarvdw ? a->omega : 0.0, 0.0, a->c6, a->c8, a->c10,
+                    a->c9);
     fprintf(fp, "END\n");
     fclose(fp);
     return 0;

@@ -38,6 +38,7 @@ typedef struct _atom {
     double mass, charge, polarizability, epsilon, sigma;
     double c6, c8, c10; /* disp_expansion: dispersion coefficients in atomic units (structs.h:54, read_pqr.c:255-257) */
     double c9;          /* axilrod_teller: three-body coefficient in atomic units (read_pqr.c:258) */
+    double omega;       /* polarvdw: characteristic frequency in atomic units (structs.h, read_pqr.c:253) */
     double pos[3], wrapped_pos[3];
     double ef_static[3], ef_static_self[3], ef_induced[3], ef_induced_change[3];
     double mu[3], old_mu[3], new_mu[3];
@@ -117,6 +118,13 @@ typedef struct _system {
     int axilrod_teller, midzuno_kihara_approx;
     /* Lennard-Jones over lattice images (structs.h, lj.c:109-276): sent with mpmc_hip_set_rd_crystal() */
     int rd_crystal, rd_crystal_order;
+    /* coupled-dipole many-body van der Waals (structs.h; vdw.c): 1 = on; 2 (evects) and 3 (comp) are read so that
+     * energy_hip.c can refuse them by name, like the three repulsion variants */
+    int polarvdw, cdvdw_exp_repulsion, cdvdw_sig_repulsion, cdvdw_9th_repulsion;
+    /* cavity_autoreject_absolute (energy.c:48-64, :99-102, :187-191): a pair of atoms on different molecules closer than
+     * the scale makes energy() return MAXVALUE; count_autorejects counts those calls */
+    int cavity_autoreject_absolute, count_autorejects;
+    double cavity_autoreject_scale;
     /* ensemble replay (replay.c): the trajectory, whether its REMARK BOX lines set the box, and calc_pressure, which is
      * read so that replay can refuse it by name */
     int read_pqr_box_on, calc_pressure;
