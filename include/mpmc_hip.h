@@ -333,6 +333,32 @@ int mpmc_hip_get_vdw_energy(mpmc_hip_ctx *ctx, double *out);
  * correction (pair + self); zeros while the mode is off. */
 int mpmc_hip_get_vdw_terms(mpmc_hip_ctx *ctx, double terms[5]);
 
+/* The exact Thole dipoles (polar_iterative off, reference src/energy/polar.c:91-95): A mu = E_static is solved directly, by
+ * a blocked fp64 Cholesky factorization of the polarizable sites' matrix on the device and two substitutions
+ * (kernels_exact.h), instead of iteratively.  enable = 0 returns to the iterative solvers.  A setting
+ * of the context like mpmc_hip_set_rd_crystal(): it persists across uploads; not allowed between energy_begin() and
+ * energy_end().  While it is on:
+ *   - polarization_energy = -1/2 sum mu . E_static of the solution, polar_iterations = 0, dipole_rrms = 0, and
+ *     download_dipoles() gives ef_induced and ef_induced_change as zeros (the reference leaves them untouched);
+ *   - polar_gs, polar_gs_ranked, polar_sor, polar_esor, polar_gamma, polar_max_iter and polar_precision are ignored, and
+ *     set_params() accepts a set with neither polar_max_iter nor polar_precision;
+ *   - energy() refuses polar_zodid, polar_palmo and polarvdw (mpmc_hip_set_vdw) by name;
+ *   - insert_molecule / remove_molecule answer 1 (upload the whole configuration again); update_atoms, scale_box,
+ *     energy_begin / _end and several contexts work as before, with the bits of a from-scratch evaluation;
+ *   - the work copy of the matrix, (3 nvpad)^2 doubles beside the resident matrix of the same size, is allocated at the
+ *     first energy(); if it does not fit, energy() fails and names the byte count.
+ * OWNED DEVIATION: a matrix that is not positive definite (a polarization catastrophe) has no Cholesky factor.  The
+ * reference's pivoted LU would return numbers; this engine reports iter_success = 1 (the reference's "solver failed", on
+ * which the Monte Carlo driver rejects the move) and gives the iterative solvers' divergence fallback mu = alpha E_static
+ * with U_pol from those.  The flag is that call's alone.  mpmc_hip_timings in this mode: sweep_ms / sweep_count are the
+ * trailing-update kernels, palmo_ms (option "timing" 2) the whole solve. */
+int mpmc_hip_set_exact_polar(mpmc_hip_ctx *ctx, int enable);
+/* The molecular polarizability tensor of the reference's `polarizability_tensor on` (thole_polarizability.c:27-37),
+ * out[3 p + q] = sum_ij (A^-1)[3i+p][3j+q] in A^3, from three unit-field right-hand sides on the factor of the last
+ * completed energy() (the inverse is never formed).  An error, by name, while the exact mode is off, before an energy()
+ * with polarization has completed in it, or when that call's matrix was not positive definite. */
+int mpmc_hip_get_polarizability_tensor(mpmc_hip_ctx *ctx, double out[9]);
+
 /* cavity_autoreject_absolute (reference energy.c:48-64): with scale = cavity_autoreject_scale > 0 every energy() also
  * counts the pairs of atoms on DIFFERENT molecules -- frozen-frozen pairs included -- whose minimum-image distance is
  * < scale, the distance and the comparison in the reference's fp64 operation order.  0 = off.  A setting of the context

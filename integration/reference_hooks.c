@@ -35,13 +35,11 @@ int hook_do_command(system_t *system, char **token) {
 /* src/io/check_input.c: the twin of the `cuda` guard (:325-341); energy_hip() repeats these checks on every
  * call and fails (never computes something else) when an option it does not implement is on.  `disp_expansion` is no
  * longer among them (default and Schmidt mixing, with or without damp_dispersion / extrapolate_disp_coeffs); the other
- * mixing rules and disp_expansion_mbvdw are refused there, each by name */
+ * mixing rules and disp_expansion_mbvdw are refused there, each by name.  Nor is `polar_iterative off`: the engine solves
+ * the linear system directly then (mpmc_hip_set_exact_polar) */
 int hook_check_system(system_t *system) {
     if (system->hip && system->polarization) {
-        if (!system->polar_iterative) {
-            error("INPUT: HIP engine available for iterative Thole only\n");
-            return -1;
-        } else if (system->damp_type != DAMPING_EXPONENTIAL) {
+        if (system->damp_type != DAMPING_EXPONENTIAL) {
             error("INPUT: HIP engine available for exponential Thole damping only\n");
             return -1;
         }

@@ -42,6 +42,7 @@
 #include "kernels_crystal.h"
 #include "kernels_vdw.h"
 #include "kernels_polar.h"
+#include "kernels_exact.h"
 #include "kernels_gs.h"
 #include "kernels_gs_chain.h"
 #include "kernels_resident.h"
@@ -327,6 +328,7 @@ struct CallState {
     // predicates of the call (enqueue_direct)
     bool do_polar = false;        // the polarization chain runs
     bool gs_mode = false;         // polar_gs or polar_gs_ranked
+    bool exact = false;           // the exact dipoles (mpmc_hip_set_exact_polar): no sweep of any kind runs
     bool two_streams = false;     // the LJ / Ewald kernels run on the side stream beside it
     bool plain_launches = false;  // neither captured into a step graph nor eligible to be ("step_graph" off)
     DirtyBlocks dirty_blocks;             // 64-atom blocks of the atoms moved since the last call
@@ -469,6 +471,16 @@ struct mpmc_hip_ctx {
     bool vdw_iso_summed = false;
     double vdw_energy = 0.0;             // the term of the last completed energy_end() (0 outside the mode)
     double vdw_terms[5] = {0, 0, 0, 0, 0};  // ... and e_total, e_iso, lr_corr, the repulsion sum, its long-range correction
+    // ---- exact dipoles (mpmc_hip_set_exact_polar): blocked Cholesky of view 0's matrix, kernels_exact.h.  A context setting:
+    // it persists across uploads.  Nothing below is allocated while the mode is off.
+    bool exact_polar = false;
+    DevBuf<double> d_chol_W;        // [3 nvpad][3 nvpad] the work copy, L in its lower triangle after a call
+    DevBuf<double> d_chol_vec;      // b, y, x of the substitutions: [3][3][3 nvpad]
+    DevBuf<unsigned> d_chol_flag;   // [0]: a pivot of this call's factorization was not positive
+    DevBuf<double> d_chol_tensor;   // [9]
+    int chol_nv = 0, chol_nvpad = 0;  // the view the factor in d_chol_W is of (chol_nv = 0: none)
+    bool chol_done = false;         // ... and an energy_end() has collected that call
+    bool chol_failed = false;       // ... whose flag word was set
     // ---- cavity_autoreject_absolute (mpmc_hip_set_autoreject): a context setting, persists across uploads
     double autoreject_scale = 0.0;       // 0 = off
     long long close_contacts = 0;        // of the last completed energy_end()
@@ -601,6 +613,8 @@ static DevBox dev_box(const mpmc_hip_ctx *c) {
 
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static int complete_pending_sweep(mpmc_hip_ctx *c);  // engine_polar.inc
+template <int NRHS>
+static int exact_substitute(mpmc_hip_ctx *c, int nv, int nvpad, const double *es);  // engine_polar.inc
 // the polarization result is gone (the configuration it belongs to is being replaced): nobody can ask for the pending sweep
 static void drop_polar_result(mpmc_hip_ctx *c) {
     c->psweep.drop();
@@ -982,7 +996,9 @@ extern "C" int mpmc_hip_set_params(mpmc_hip_ctx *c, const mpmc_hip_params *p) {
         if (p->polar_precision > 0.0 && p->polar_max_iter > 0)
             return fail("MPMC_HIP: cannot specify both polar_precision and polar_max_iter, must pick one");
         if (p->polar_precision < 0.0) return fail("MPMC_HIP: invalid polarization iterative precision specified");
-        if (p->polar_precision == 0.0 && p->polar_max_iter <= 0 && !p->polar_zodid)
+        // (the exact dipoles read no solver parameter: a set without either is accepted while that mode is on, and
+        //  energy() refuses it should the mode be switched off again)
+        if (p->polar_precision == 0.0 && p->polar_max_iter <= 0 && !p->polar_zodid && !c->exact_polar)
             return fail("MPMC_HIP: polar_max_iter must be > 0 when polar_precision is 0");
         if (p->polar_sor && p->polar_esor) return fail("MPMC_HIP: cannot specify both SOR and ESOR SCF methods");
         if (p->polar_gamma < 0.0) return fail("MPMC_HIP: invalid Pre-cond/SOR/ESOR gamma set");
@@ -1124,6 +1140,7 @@ extern "C" int mpmc_hip_upload(mpmc_hip_ctx *c, int n, const double *x, const do
     c->have_polar_result = false;
     c->disp_on = false;  // an upload brings Lennard-Jones parameters until set_dispersion() says otherwise
     c->at_on = false;  // ... and no three-body term until set_axilrod_teller() says otherwise
+    c->chol_nv = 0;     // (the exact dipoles' factor was the old configuration's; the setting itself stays)
     c->vdw_on = false;  // ... and no coupled-dipole term until set_vdw() says otherwise (its e_iso cache stays for that call)
     atoms_replaced(c);
     c->rank_saved.clear();
@@ -1284,6 +1301,46 @@ extern "C" int mpmc_hip_set_rd_crystal(mpmc_hip_ctx *c, int order) {
     c->lrc.valid = false;
     c->all_dirty = true;
     ++c->config_rev;
+    return 0;
+}
+
+// The exact dipoles (polar_iterative off, polar.c:91-95): A mu = E_static by a blocked Cholesky factorization on the device
+// (kernels_exact.h) instead of an iterative solve.  A setting of the context, like set_rd_crystal().
+extern "C" int mpmc_hip_set_exact_polar(mpmc_hip_ctx *c, int enable) {
+    if (!c) return fail("MPMC_HIP: set_exact_polar: null context");
+    if (c->in_flight) return fail("MPMC_HIP: set_exact_polar between energy_begin() and energy_end()");
+    if ((enable != 0) == c->exact_polar) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    if (complete_pending_sweep(c)) return -1;
+    if (c->have_atoms && flush_moves(c)) return -1;  // keep the order of the caller's operations
+    c->exact_polar = enable != 0;
+    c->chol_nv = 0;
+    c->chol_done = c->chol_failed = false;
+    c->all_dirty = true;
+    ++c->config_rev;
+    return 0;
+}
+
+// The molecular polarizability tensor C[p][q] = sum_ij (A^-1)[3i+p][3j+q] (thole_polarizability.c:27-37), without the
+// inverse: column q is the sum over the sites of the dipoles a unit field along q induces -- three more right-hand sides
+// on the factor of the last completed energy().
+extern "C" int mpmc_hip_get_polarizability_tensor(mpmc_hip_ctx *c, double out[9]) {
+    if (!c || !out) return fail("MPMC_HIP: get_polarizability_tensor: null argument");
+    if (c->in_flight) return fail("MPMC_HIP: get_polarizability_tensor between energy_begin() and energy_end()");
+    if (!c->exact_polar)
+        return fail("MPMC_HIP: get_polarizability_tensor: the exact dipoles are off (mpmc_hip_set_exact_polar; the reference: "
+                    "iterative polarizability tensor method not implemented)");
+    if (c->chol_nv <= 0 || !c->chol_done)
+        return fail("MPMC_HIP: get_polarizability_tensor: no energy() with polarization has completed in this mode");
+    if (c->chol_failed)
+        return fail("MPMC_HIP: get_polarizability_tensor: the matrix of the last energy() was not positive definite");
+    HIPCHK(hipSetDevice(c->device));
+    if (exact_substitute<3>(c, c->chol_nv, c->chol_nvpad, nullptr)) return -1;
+    hipLaunchKernelGGL(chol_tensor_kernel, dim3(1), dim3(256), 0, c->stream, c->chol_nv,
+                       (const double *)(c->d_chol_vec + 6 * (size_t)(3 * c->chol_nvpad)), 3 * c->chol_nvpad,
+                       c->d_chol_tensor.get());
+    HIPCHK(hipMemcpyAsync(out, c->d_chol_tensor, 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -1609,7 +1666,7 @@ extern "C" int mpmc_hip_scale_box(mpmc_hip_ctx *c, const double basis[9], double
 static bool gs_order_mode(const mpmc_hip_ctx *c) {  // Gauss-Seidel on the chain kernel: the view order is the caller's
     const mpmc_hip_params &P = c->par;
     return !P.rd_only && P.polarization && !P.polar_zodid && (P.polar_gs || P.polar_gs_ranked) && c->opt.pair_coef != 0 &&
-           c->opt.persistent_gs != 0;
+           c->opt.persistent_gs != 0 && !c->exact_polar;  // (the exact dipoles ignore the solver flags)
 }
 
 static bool edits_supported(const mpmc_hip_ctx *c) {
@@ -1619,6 +1676,7 @@ static bool edits_supported(const mpmc_hip_ctx *c) {
     if (c->at_on) return false;    // axilrod_teller: the same
     if (c->rdc_order) return false;  // rd_crystal: the same
     if (c->vdw_on) return false;     // polarvdw: the same
+    if (c->exact_polar) return false;  // exact dipoles: the expanded matrix is not patched by edits (as on its Gauss-Seidel path)
     // Gauss-Seidel: only with the chain kernel, whose view is rebuilt from the order the caller states afterwards
     if (!P.rd_only && P.polarization && (P.polar_gs || P.polar_gs_ranked) && !gs_order_mode(c)) return false;
     return true;
@@ -2533,7 +2591,8 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
     const mpmc_hip_params &P = c->par;
     CallState &k = c->call;
     k.do_polar = !P.rd_only && P.polarization;
-    k.gs_mode = P.polar_gs || P.polar_gs_ranked;
+    k.exact = k.do_polar && c->exact_polar;
+    k.gs_mode = (P.polar_gs || P.polar_gs_ranked) && !k.exact;
     // ---- fork: LJ / Ewald kernels (fp64-VALU bound) run on stream2 while the polarization chain
     // (HBM bound) runs on the main stream -- the device-side analogue of the reference starting its
     // polarization worker before the other energy terms (energy.c:108-129, :181-186).
@@ -2549,7 +2608,7 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
     //  inside setup_view() -- the move rides in update_coef_moves_kernel too, as a launch of its own in front of the block
     //  matrices instead of apply_moves_kernel + update_coef_kernel; the side stream, whose ranking kernels read the
     //  coordinates, applies the same move for itself as before (side_apply).  Option "gs_fuse_moves".)
-    k.moves_deferred = c->opt.fuse_moves && c->pending.n > 0 && k.plain_launches && do_polar && !P.polar_zodid &&
+    k.moves_deferred = c->opt.fuse_moves && c->pending.n > 0 && k.plain_launches && do_polar && !P.polar_zodid && !k.exact &&
                        (!k.gs_mode || (c->opt.gs_fuse_moves && gs_order_mode(c))) && P.polar_precision == 0.0 && c->opt.overlap &&
                        c->opt.pair_coef && !c->all_dirty && c->view[0].C_valid && c->view[0].pos_valid;
     // Without polarization the pair kernel is the first kernel of the step that reads coordinates: the move rides in it.
@@ -2753,7 +2812,7 @@ static bool graph_eligible(mpmc_hip_ctx *c) {
     const mpmc_hip_params &P = c->par;
     const SweepView &v = c->view[0];
     if (!c->opt.graph || is_timed_call(c) || !c->opt.incremental || !c->opt.incremental_pairs ||
-        !c->opt.pair_coef || c->disp_on || c->at_on || c->rdc_order || c->vdw_on || c->autoreject_scale != 0.0)
+        !c->opt.pair_coef || c->disp_on || c->at_on || c->rdc_order || c->vdw_on || c->autoreject_scale != 0.0 || c->exact_polar)
         return false;
     if (P.rd_only || !P.polarization || P.polar_zodid || P.polar_gs || P.polar_gs_ranked || P.polar_precision != 0.0 ||
         P.polar_max_iter <= 0)
@@ -2869,6 +2928,21 @@ extern "C" int mpmc_hip_energy_begin(mpmc_hip_ctx *c) {
     } else {
         c->vdw_iso.clear();  // the mode is off: its e_iso cache goes
     }
+    if (c->exact_polar && c->par.polarization && !c->par.rd_only) {
+        if (c->par.polar_zodid)
+            return fail("MPMC_HIP: energy: polar_zodid and polar_iterative are incompatible: the exact dipoles "
+                        "(mpmc_hip_set_exact_polar) with polar_zodid are refused");  // check_input.c:349-353
+        if (c->par.polar_palmo)
+            return fail("MPMC_HIP: energy: the exact dipoles (mpmc_hip_set_exact_polar) with polar_palmo are not implemented "
+                        "(the reference would add a stale ef_induced_change)");
+        if (c->vdw_on)
+            return fail("MPMC_HIP: energy: the exact dipoles (mpmc_hip_set_exact_polar) with polarvdw (mpmc_hip_set_vdw) are not "
+                        "implemented (the reference forces the iterative solver there)");
+    } else if (c->par.polarization && !c->par.rd_only && !c->par.polar_zodid && c->par.polar_precision == 0.0 &&
+               c->par.polar_max_iter <= 0) {
+        return fail("MPMC_HIP: polar_max_iter must be > 0 when polar_precision is 0");  // (accepted by set_params in the exact mode)
+    }
+    if (!c->exact_polar) c->chol_nv = 0;
     HIPCHK(hipSetDevice(c->device));
     if (c->vdw_on && !c->par.rd_only && vdw_ensure_iso(c)) return -1;
     if (c->resident_off && c->resident_backoff > 0 && (long)c->energy_calls >= c->resident_retry_at)
@@ -3004,7 +3078,13 @@ extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
     clock_gettime(CLOCK_MONOTONIC, &ts2);
     c->host_wait_s += (ts2.tv_sec - ts1.tv_sec) + 1e-9 * (ts2.tv_nsec - ts1.tv_nsec);
     const bool do_polar = c->call.do_polar, timed_call = c->call.timed;
-    const int polar_iterations = c->call.iterations, iter_success = c->call.iter_success;
+    const int polar_iterations = c->call.iterations;
+    // (exact dipoles: the factorization's flag word came with the record, in the slot the iterative paths keep <rrms> in)
+    const int iter_success = c->call.exact ? (c->h_res[R_RRMS] != 0.0 ? 1 : 0) : c->call.iter_success;
+    if (c->call.exact) {
+        c->chol_done = true;
+        c->chol_failed = iter_success != 0;
+    }
     const int gs_err = (int)c->h_res[R_GS_ERR];
     c->h_gserr[0] = gs_err & 1;
     c->h_gserr[1] = (gs_err >> 1) & 1;
@@ -3053,7 +3133,7 @@ extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
     c->vdw_terms[3] = c->vdw_on ? r[R_DISP] : 0.0;
     c->vdw_terms[4] = c->vdw_on ? r[R_DISP_LRC] : 0.0;
     c->close_contacts = c->autoreject_scale != 0.0 ? (long long)r[R_CONTACTS] : 0;
-    out->dipole_rrms = do_polar ? r[R_RRMS] : 0.0;
+    out->dipole_rrms = (do_polar && !c->call.exact) ? r[R_RRMS] : 0.0;
     out->volume = c->volume;
     out->cutoff = c->cutoff;
     out->ewald_alpha = c->ewald_alpha;

@@ -801,6 +801,100 @@ static int launch_resident(mpmc_hip_ctx *c, SweepView &v, const DevBox &bx, cons
     return 0;
 }
 
+// ---- exact dipoles (mpmc_hip_set_exact_polar, kernels_exact.h): the work copy the factorization runs in, the vectors of
+// the substitutions (b, y, x: three right-hand sides each, stride 3 nvpad), the call's flag word and the tensor's nine
+// sums.  Allocated on first use; a copy that does not fit is an error, by byte count.
+static int ensure_exact_work(mpmc_hip_ctx *c, const SweepView &v) {
+    const size_t lda = 3 * (size_t)v.nvpad, need = lda * lda;
+    if (c->d_chol_W.size() < need) {
+        c->chol_nv = 0;  // (whatever factor was there goes with its buffer)
+        if (c->d_chol_W.alloc(need) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("MPMC_HIP: energy: exact polarization: the work copy of the %zu x %zu matrix, %zu bytes, does not fit "
+                        "the device", lda, lda, need * sizeof(double));
+        }
+    }
+    if (c->d_chol_vec.size() < 9 * lda) HIPCHK(c->d_chol_vec.alloc(9 * lda));
+    if (!c->d_chol_flag) HIPCHK(c->d_chol_flag.alloc(2));
+    if (!c->d_chol_tensor) HIPCHK(c->d_chol_tensor.alloc(9));
+    return 0;
+}
+
+// A = L L^T of the view's matrix in the work copy: one copy, then diagonal block / panel / trailing update per panel of 64
+// rows (the last panel has only its diagonal block): 3 np - 1 launches.  On timed calls the trailing updates carry their
+// own begin / end timestamps (class T_SWEEP).
+static int exact_factor(mpmc_hip_ctx *c, const SweepView &v) {
+    const int n = 3 * v.nv, lda = 3 * v.nvpad, np = (n + kCholNB - 1) / kCholNB;
+    hipLaunchKernelGGL(chol_copy_kernel, dim3(np, np), dim3(kCholThreads), 0, c->stream, (const double *)v.A, lda, n,
+                       c->d_chol_W.get(), c->d_chol_flag.get());
+    for (int k = 0; k < np; ++k) {
+        hipLaunchKernelGGL(chol_diag_kernel, dim3(1), dim3(kCholThreads), 0, c->stream, c->d_chol_W.get(), lda, k,
+                           c->d_chol_flag.get());
+        const int m = np - 1 - k;
+        if (m == 0) break;
+        hipLaunchKernelGGL(chol_panel_kernel, dim3(m), dim3(kCholThreads), 0, c->stream, c->d_chol_W.get(), lda, k);
+        HIPCHK(launch_timed(c, T_SWEEP, chol_trail_kernel, dim3(m, m), dim3(kCholThreads), 0, c->stream, c->d_chol_W.get(),
+                            lda, k));
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// L L^T x = b for NRHS right-hand sides on the factor in the work copy: x in the third of the three vectors.
+// 2 np + 1 launches.
+template <int NRHS>
+static int exact_substitute(mpmc_hip_ctx *c, int nv, int nvpad, const double *es) {
+    const int n = 3 * nv, lda = 3 * nvpad, np = (n + kCholNB - 1) / kCholNB;
+    double *b = c->d_chol_vec, *y = b + 3 * (size_t)lda, *x = y + 3 * (size_t)lda;
+    hipLaunchKernelGGL(chol_rhs_kernel<NRHS>, dim3(np), dim3(64), 0, c->stream, es, n, lda, b);
+    for (int k = 0; k < np; ++k)
+        hipLaunchKernelGGL(chol_fwd_kernel<NRHS>, dim3(np - k), dim3(kCholThreads), 0, c->stream, (const double *)c->d_chol_W.get(), lda,
+                           k, b, y, lda);
+    for (int k = np - 1; k >= 0; --k)
+        hipLaunchKernelGGL(chol_bwd_kernel<NRHS>, dim3(k + 1), dim3(kCholThreads), 0, c->stream, (const double *)c->d_chol_W.get(), lda,
+                           k, y, x, lda);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// polar() with polar_iterative off (polar.c:91-95): the view's matrix is kept resident and updated as for the
+// Gauss-Seidel kernels, the static field is gathered as ever, then A mu = E_static is solved directly.  No sweep, no
+// ranking, no resident solver, no deferral: polar_iterations = 0, E_ind and dE_ind stay zero (the reference leaves them
+// untouched on this path).  The flag word of the factorization travels in the record slot behind U_pol.
+static int run_exact_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx) {
+    SweepView *V = &c->view[0];
+    if (setup_view(c, *V, a, bx, true, false, true)) return -1;
+    if (launch_field(c, a, bx)) return -1;
+    c->call.resident = false;
+    c->psweep.drop();
+    hipLaunchKernelGGL(init_view_kernel, dim3(V->nvpad / 64), dim3(64 * kFieldGroups), 0, c->stream, V->nv, V->nvpad,
+                       V->d_idx, V->palpha, c->d_fieldpart, c->es_slots, c->npad, 1.0, V->es, V->mu0, V->efind, V->efchg,
+                       V->rrms, c->d_errmax, (unsigned *)nullptr, (unsigned *)nullptr, (double *)nullptr, 0,
+                       (size_t)3 * V->nvpad);
+    if (ensure_exact_work(c, *V)) return -1;
+    {
+        ScopedTimer t(c, T_PALMO);  // (the whole solve; the trailing updates alone are the call's T_SWEEP records)
+        if (exact_factor(c, *V)) return -1;
+        // the device is busy now: feed the LJ / Ewald stream
+        if (c->call.enqueue_side) c->call.enqueue_side();
+        if (exact_substitute<1>(c, V->nv, V->nvpad, V->es)) return -1;
+        hipLaunchKernelGGL(chol_energy_kernel, dim3(1), dim3(256), 0, c->stream, V->nv, V->nvpad,
+                           (const double *)(c->d_chol_vec + 6 * (size_t)(3 * V->nvpad)), (const double *)V->palpha,
+                           (const double *)V->es, (const unsigned *)c->d_chol_flag.get(), V->mu1.get(), c->d_res + R_UPOL);
+    }
+    c->chol_nv = V->nv;
+    c->chol_nvpad = V->nvpad;
+    {
+        ScopedTimer t(c, T_EVPAIR);
+    }
+    c->result_view = V;
+    c->result_mu = V->mu1;
+    c->results_scattered = false;
+    c->energy_nt = 0;
+    c->have_polar_result = true;
+    return 0;
+}
+
 static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, int *n_iter, int *iter_success) {
     const mpmc_hip_params &P = c->par;
     const int npad = c->npad, n = c->n;
@@ -810,6 +904,7 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
     *iter_success = 0;
     c->energy_nt = 0;
     c->call.gs_sweeps = 0;
+    if (c->call.exact) return run_exact_polarization(c, a, bx);
     // ---- ranking metric (pairs.c:337-360), needed from the 2nd sweep on.
     // Speculative form: the ranked view (1) of the previous call is assumed to be still the right walk (a single-
     // molecule move changes the metric only when molecules come within 1.5 r_min of each other); its data are brought

@@ -19,6 +19,7 @@ EXPORTS = [
     "mpmc_hip_upload", "mpmc_hip_set_dispersion", "mpmc_hip_set_axilrod_teller", "mpmc_hip_get_three_body_energy",
     "mpmc_hip_set_rd_crystal", "mpmc_hip_set_vdw", "mpmc_hip_get_vdw_energy", "mpmc_hip_get_vdw_terms",
     "mpmc_hip_set_autoreject", "mpmc_hip_get_close_contacts",
+    "mpmc_hip_set_exact_polar", "mpmc_hip_get_polarizability_tensor",
     "mpmc_hip_update_atoms", "mpmc_hip_insert_molecule", "mpmc_hip_remove_molecule",
     "mpmc_hip_slot_count", "mpmc_hip_set_sweep_order", "mpmc_hip_energy", "mpmc_hip_energy_begin", "mpmc_hip_energy_end",
     "mpmc_hip_download_dipoles",
@@ -119,10 +120,11 @@ AT_NAMES = ["axilrod_teller", "midzuno_kihara_approx"]  # mpmc_hip_set_axilrod_t
 RDC_NAMES = ["rd_crystal", "rd_crystal_order"]  # mpmc_hip_set_rd_crystal (reference keywords)
 VDW_NAMES = ["polarvdw", "cdvdw"]  # mpmc_hip_set_vdw (reference keywords)
 AUTOREJECT_NAMES = ["cavity_autoreject_absolute", "cavity_autoreject_scale"]  # mpmc_hip_set_autoreject (reference keywords)
+EXACT_NAMES = ["polar_iterative"]  # mpmc_hip_set_exact_polar (reference keyword; 0 = the exact dipoles)
 VDW_TERMS = ["e_total", "e_iso", "lr_corr", "repulsion", "repulsion_lrc"]  # mpmc_hip_get_vdw_terms, in its order
 # flags that make_params() leaves to others: pbc_cutoff is a box property at this boundary (set_box), the rest are the
 # arguments of the calls above (Engine.load_system)
-NOT_PARAMS = frozenset(["pbc_cutoff"] + DISP_NAMES + AT_NAMES + RDC_NAMES + VDW_NAMES + AUTOREJECT_NAMES)
+NOT_PARAMS = frozenset(["pbc_cutoff"] + DISP_NAMES + AT_NAMES + RDC_NAMES + VDW_NAMES + AUTOREJECT_NAMES + EXACT_NAMES)
 AT_ALPHA_AU = 6.7483345  # A^3 -> Bohr^3, as the reference writes it (axilrod_teller.cpp:115)
 
 _lib = None
@@ -160,6 +162,8 @@ def load():
     lib.mpmc_hip_set_vdw.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     lib.mpmc_hip_get_vdw_energy.argtypes = [vp, dp]
     lib.mpmc_hip_get_vdw_terms.argtypes = [vp, dp]
+    lib.mpmc_hip_set_exact_polar.argtypes = [vp, C.c_int]
+    lib.mpmc_hip_get_polarizability_tensor.argtypes = [vp, dp]
     lib.mpmc_hip_set_autoreject.argtypes = [vp, C.c_double]
     lib.mpmc_hip_get_close_contacts.argtypes = [vp, C.POINTER(C.c_longlong)]
     lib.mpmc_hip_update_atoms.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
@@ -327,6 +331,19 @@ class Engine:
         _chk(self.lib.mpmc_hip_get_vdw_terms(self.ctx, t))
         return dict(zip(VDW_TERMS, [float(x) for x in t]))
 
+    def set_exact_polar(self, enable):
+        """The exact Thole dipoles (mpmc_hip_set_exact_polar; the reference's polar_iterative off): A mu = E_static by a
+        Cholesky factorization on the device instead of an iterative solve.  A context setting: it persists across
+        uploads."""
+        _chk(self.lib.mpmc_hip_set_exact_polar(self.ctx, int(bool(enable))))
+
+    def polarizability_tensor(self):
+        """The 3 x 3 molecular polarizability tensor (A^3) of the last completed energy() in the exact mode
+        (mpmc_hip_get_polarizability_tensor; the reference's polarizability_tensor on)."""
+        t = (C.c_double * 9)()
+        _chk(self.lib.mpmc_hip_get_polarizability_tensor(self.ctx, t))
+        return np.array([float(x) for x in t]).reshape(3, 3)
+
     def set_autoreject(self, scale):
         """cavity_autoreject_absolute (mpmc_hip_set_autoreject): scale = cavity_autoreject_scale; 0 switches it off.  A
         context setting: it persists across uploads."""
@@ -349,7 +366,10 @@ class Engine:
         disp_expansion, + the three-body coefficients when they carry axilrod_teller, + omega and the type ids when they
         carry polarvdw).  cavity_autoreject_absolute + cavity_autoreject_scale switch the close-contact count on; without
         them it is switched off.  rd_crystal / rd_crystal_order among
-        the flags switch the image sum on (order 1 when only rd_crystal is given); without them it is switched off."""
+        the flags switch the image sum on (order 1 when only rd_crystal is given); without them it is switched off.
+        polar_iterative = 0 together with polarization switches the exact dipoles on; anything else switches them off."""
+        self.set_exact_polar("polar_iterative" in params and not params["polar_iterative"]
+                             and bool(params.get("polarization")))
         self.set_params(**params)
         self.set_rd_crystal(int(params.get("rd_crystal_order", 1)) if params.get("rd_crystal") else 0)
         self.set_autoreject(float(params.get("cavity_autoreject_scale", 0.0))

@@ -97,6 +97,7 @@ def load():
     lib.host_read_frame.argtypes = [vp, C.c_char_p, C.c_int]
     lib.host_unsupported.argtypes = [vp]
     lib.host_unsupported.restype = C.c_char_p
+    lib.host_get_polarizability_tensor.argtypes = [vp, vp]
     lib.volume_change.argtypes = [vp]
     lib.volume_change.restype = None
     lib.revert_volume_change.argtypes = [vp]
@@ -111,7 +112,8 @@ def config_text(flags, extra=None):
              "polar_esor", "polar_palmo", "polar_rrms", "polar_zodid", "polar_wolf", "polar_ewald", "wolf",
              "disp_expansion", "damp_dispersion", "extrapolate_disp_coeffs", "schmidt_mixing", "axilrod_teller",
              "midzuno_kihara_approx", "rd_crystal", "read_pqr_box", "calc_pressure", "polarvdw", "cdvdw",
-             "cavity_autoreject_absolute", "cdvdw_exp_repulsion", "cdvdw_sig_repulsion", "cdvdw_9th_repulsion"}
+             "cavity_autoreject_absolute", "cdvdw_exp_repulsion", "cdvdw_sig_repulsion", "cdvdw_9th_repulsion",
+             "polar_iterative", "polarizability_tensor"}
     lines = []
     for k, v in flags.items():
         if k in ("polarvdw", "cdvdw") and isinstance(v, str):
@@ -124,7 +126,8 @@ def config_text(flags, extra=None):
             lines.append("%s %r" % (k, v))
     if flags.get("polarization"):
         lines.append("polar_damp_type exponential")
-        lines.append("polar_iterative on")
+        if "polar_iterative" not in flags:  # (polar_iterative=0: the exact dipoles)
+            lines.append("polar_iterative on")
     for k, v in (extra or {}).items():
         lines.append("%s %s" % (k, v))
     return "\n".join(lines) + "\n"
@@ -201,6 +204,13 @@ class HostSystem:
         v = np.ascontiguousarray(d, dtype=np.float64)
         if self.lib.host_displace_molecule(self.ptr, int(index), v.ctypes.data) != 0:
             raise IndexError(index)
+
+    def polarizability_tensor(self):
+        """The 3 x 3 molecular polarizability tensor (A^3) of the last energy(): polar_iterative=0 only."""
+        out = np.zeros(9)
+        if self.lib.host_get_polarizability_tensor(self.ptr, out.ctypes.data) != 0:
+            raise engine.EngineError(engine.load().mpmc_hip_last_error().decode())
+        return out.reshape(3, 3)
 
     def vdw(self):
         """polarvdw / cavity_autoreject_absolute state: the keywords as read, count_autorejects, observables->vdw_energy."""

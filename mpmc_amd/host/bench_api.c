@@ -10,6 +10,7 @@
 int host_apply_config(system_t *system, const char *text) {
     char line[MAXLINE], tok[10][MAXLINE], *token[10];
     for (int i = 0; i < 10; i++) token[i] = tok[i];
+    system->polar_iterative = 1; /* a system built from arrays iterates unless the text says `polar_iterative off` */
     const char *p = text;
     while (*p) {
         size_t len = strcspn(p, "\n");
@@ -22,7 +23,6 @@ int host_apply_config(system_t *system, const char *text) {
                tok[8], tok[9]);
         if (do_command(system, token)) return 1;
     }
-    system->polar_iterative = 1;
     pbc(system);
     if (system->ensemble == ENSEMBLE_UVT && !system->user_fugacities) system->fugacity = system->pressure;
     if (system->ensemble == ENSEMBLE_UVT && !(system->fugacity > 0.0)) return 1;
@@ -300,6 +300,10 @@ int host_read_frame(system_t *system, const char *path, int index) {
 }
 /* the reason energy() would refuse this system, or NULL */
 const char *host_unsupported(system_t *system) { return energy_hip_unsupported(system); }
+/* polarizability_tensor: the tensor of the last energy() (no printing); non-zero when the engine refuses */
+int host_get_polarizability_tensor(system_t *system, double out[9]) {
+    return energy_hip_polarizability_tensor(system, out, 0);
+}
 
 /* ---- npt ---------------------------------------------------------------------------------------------------- */
 void host_get_basis(system_t *system, double basis[9]) {

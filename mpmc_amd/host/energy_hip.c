@@ -50,6 +50,7 @@ typedef struct shim_state {
     int uploaded; /* a configuration is resident */
     int rdc_order; /* rd_crystal_order as sent with that upload (0: rd_crystal off) */
     int vdw_on;    /* polarvdw as sent with that upload */
+    int exact;     /* the exact dipoles (polarization with polar_iterative off) as sent with that upload */
     double ar_scale; /* cavity_autoreject_scale as sent with that upload (0: cavity_autoreject_absolute off) */
     int failed;   /* device / ABI failure of the last call */
     mpmc_hip_params params; /* as last sent */
@@ -239,11 +240,19 @@ static const char *unsupported(const system_t *s) {
     if (s->polarvdw && (s->waldmanhagler || s->halgren_mixing))
         return "polarvdw with waldmanhagler / halgren_mixing is not on the device";
     if (s->polarvdw && s->vdw_fh_2be) return "vdw_fh_2be is not on the device";
-    if (s->polarization && !s->polar_iterative) return "iterative Thole solver only (polar_iterative on)";
     if (s->polarization && s->damp_type != DAMPING_EXPONENTIAL) return "exponential Thole damping only";
     if (s->polarization && (s->polar_ewald_full || s->polar_wolf_full)) return "polar_ewald_full / polar_wolf_full are not on the device";
     if (s->ensemble == ENSEMBLE_NVE) return "ensemble nve is not supported";
 #endif
+    /* polar_iterative off: the exact dipoles are on the device (mpmc_hip_set_exact_polar); the rest is refused by name */
+    if (s->polarization && !s->polar_iterative && s->polar_zodid)
+        return "ZODID and matrix inversion cannot both be set! (polar_zodid with polar_iterative off)"; /* check_input.c:349-353 */
+    if (s->polarization && !s->polar_iterative && s->polar_palmo)
+        return "polar_palmo with polar_iterative off is not on the device (the reference would add a stale ef_induced_change)";
+    if (s->polarization && !s->polar_iterative && s->polarvdw)
+        return "polarvdw with polar_iterative off is not on the device (the reference forces the iterative solver there)";
+    if (s->polarizability_tensor && s->polar_iterative)
+        return "iterative polarizability tensor method not implemented"; /* check_input.c:343-347 */
     /* polarvdw: the coupled-dipole term with repulsion-only Lennard-Jones is on the device; the rest is refused by name */
     if (s->cdvdw_exp_repulsion) return "cdvdw_exp_repulsion is not on the device";
     if (s->cdvdw_sig_repulsion) return "cdvdw_sig_repulsion is not on the device";
@@ -384,6 +393,9 @@ static int full_upload(shim_state *st, system_t *system) {
     for (int p = 0; p < 3; p++)
         for (int r = 0; r < 3; r++) basis[3 * p + r] = system->pbc->basis[p][r];
     fill_params(system, &st->params);
+    /* (in front of the parameters: the exact mode takes a set with neither polar_max_iter nor polar_precision) */
+    st->exact = (system->polarization && !system->polar_iterative);
+    if (mpmc_hip_set_exact_polar(st->ctx, st->exact)) return hip_fail("set_exact_polar");
     int rc = mpmc_hip_set_params(st->ctx, &st->params);
     if (!rc) rc = mpmc_hip_set_box(st->ctx, basis, system->pbc->cutoff);
     if (!rc) rc = mpmc_hip_upload(st->ctx, n, st->x, st->y, st->z, st->q, st->alpha, st->eps, st->sig, st->mass, mol, fz);
@@ -714,6 +726,7 @@ int energy_hip_begin(system_t *system) {
         if (memcmp(&dnow, &st->disp, sizeof(dnow))) need_upload = 1;
         if ((system->rd_crystal ? system->rd_crystal_order : 0) != st->rdc_order) need_upload = 1;
         if ((system->polarvdw != 0) != st->vdw_on) need_upload = 1;
+        if ((system->polarization && !system->polar_iterative) != st->exact) need_upload = 1;
         if ((system->cavity_autoreject_absolute ? system->cavity_autoreject_scale : 0.0) != st->ar_scale) need_upload = 1;
     }
     if (!need_upload && scale_box) {
@@ -858,6 +871,26 @@ double energy_hip_end(system_t *system) {
     o->NU = o->N * o->energy;                        /* energy.c:219 */
     system->last_volume = system->pbc->volume;       /* energy.c:222 */
     return o->energy;
+}
+
+/* `polarizability_tensor on` (polar.c:98-104, thole_polarizability.c): the 3 x 3 molecular tensor of the last energy(),
+ * tensor[3 p + q] in A^3, from the device's factor (mpmc_hip_get_polarizability_tensor).  print != 0: the reference's block through
+ * output() as well -- header, rules, three %.4f rows, the isotropic term, XX/ZZ.  OWNED DEVIATION: the reference dumps the
+ * A and B matrices in front of the block; this layer never forms B and prints neither. */
+int energy_hip_polarizability_tensor(system_t *system, double tensor[9], int print) {
+    shim_state *st = state_of(system, 0);
+    if (!st || !st->ctx) return -1;
+    if (mpmc_hip_get_polarizability_tensor(st->ctx, tensor)) return hip_fail("get_polarizability_tensor");
+    if (!print) return 0;
+    /* (through output(), the tree's writer to stdout, as one block) */
+    char buf[2 * MAXLINE];
+    snprintf(buf, sizeof(buf),
+             "POLARIZATION: polarizability tensor (A^3):\n##########################\n%.4f %.4f %.4f \n%.4f %.4f %.4f \n"
+             "%.4f %.4f %.4f \n##########################\nisotropic = %.4f\nXX/ZZ = %.4f\n",
+             tensor[0], tensor[1], tensor[2], tensor[3], tensor[4], tensor[5], tensor[6], tensor[7], tensor[8],
+             (tensor[0] + tensor[4] + tensor[8]) / 3.0, tensor[0] / tensor[8]);
+    output(buf);
+    return 0;
 }
 
 /* A non-finite return with energy_hip_failed() == 0 is a bad contact, which mc.c treats as a reject

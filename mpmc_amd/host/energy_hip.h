@@ -60,6 +60,12 @@ int energy_hip_download_dipoles(system_t *system);
  * when the dipoles are asked for: mpmc_hip_timings.pending_sweeps), so a driver pays them once per corrtime block */
 int energy_hip_corrtime(system_t *system);
 
+/* `polarizability_tensor on` with polar_iterative off: the molecular polarizability tensor of the last energy_hip(),
+ * tensor[3 p + q] in A^3; print != 0 also writes the reference's block (thole_polarizability.c:50-70) to stdout.  The reference
+ * prints it inside the first polar() and leaves with die(0); here the driver calls this after its first energy() and
+ * returns 0.  Non-zero: no context, or the engine refused (its message goes to error()). */
+int energy_hip_polarizability_tensor(system_t *system, double tensor[9], int print);
+
 /* cleanup() (src/main/cleanup.c): destroys the device context and the side table entry */
 void energy_hip_cleanup(system_t *system);
 

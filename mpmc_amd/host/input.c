@@ -204,7 +204,8 @@ int do_command(system_t *system, char **token) {
     INT("ewald_kmax", ewald_kmax);
     if (!strcasecmp(k, "pbc_cutoff")) return safe_atof(v, &system->pbc->cutoff);
     FLAG("polarization", polarization);
-    FLAG("polar_iterative", polar_iterative);
+    FLAG("polar_iterative", polar_iterative);             /* input.c:1146-1153; off: the exact dipoles */
+    FLAG("polarizability_tensor", polarizability_tensor); /* input.c:1126-1133 */
     FLAG("polar_ewald", polar_ewald);
     if (!strcasecmp(k, "polar_ewald_alpha")) {
         system->polar_ewald_alpha_set = 1;
@@ -444,9 +445,17 @@ static int check_system(system_t *system) {
         return -1;
     }
     if (system->polarization) {
-        if (!system->polar_iterative && !system->polar_zodid) {
-            error("INPUT: HIP acceleration available for iterative Thole only\n"); /* check_input.c:325-328 */
+        if (system->polar_iterative && system->polarizability_tensor) { /* check_input.c:343-347 */
+            error("INPUT: iterative polarizability tensor method not implemented\n");
             return -1;
+        }
+        if (!system->polar_iterative && system->polar_zodid) { /* check_input.c:349-353 */
+            error("INPUT: ZODID and matrix inversion cannot both be set!\n");
+            return -1;
+        }
+        if (!system->polar_iterative) { /* check_input.c:486-492 */
+            output("INPUT: Matrix polarization activated\n");
+            if (system->polarizability_tensor) output("INPUT: Polarizability tensor calculation activated\n");
         }
         if (system->damp_type != 2) {
             error("INPUT: Thole damping method not specified (exponential only)\n");

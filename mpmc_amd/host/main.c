@@ -23,7 +23,12 @@ int main(int argc, char **argv) {
     snprintf(linebuf, MAXLINE, "MAIN: %d atoms, HIP energy engine on device %d\n", system->natoms, device);
     output(linebuf);
     int rc = 0;
-    if (system->ensemble == ENSEMBLE_TE) {
+    if (system->polarizability_tensor && system->polarization && !system->polar_iterative) {
+        /* polar.c:98-104: the first polar() prints the molecular tensor and the run ends there, successfully */
+        double tensor[9];
+        energy(system);
+        rc = energy_hip_failed(system) ? -1 : energy_hip_polarizability_tensor(system, tensor, 1);
+    } else if (system->ensemble == ENSEMBLE_TE) {
         const double e = energy(system);
         if (energy_hip_failed(system)) rc = -1;
         const observables_t *o = system->observables;

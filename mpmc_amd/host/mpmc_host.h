@@ -107,6 +107,7 @@ typedef struct _system {
     int rd_only, rd_lrc, feynman_hibbs, feynman_hibbs_order, wrapall, wolf;
     int ewald_alpha_set, ewald_kmax, polar_ewald_alpha_set;
     double ewald_alpha, polar_ewald_alpha;
+    int polarizability_tensor; /* structs.h:429: print the molecular tensor after the first energy() and leave (exact dipoles only) */
     int polarization, polar_iterative, polar_ewald, polar_zodid, polar_palmo, polar_gs, polar_gs_ranked, polar_sor,
         polar_esor, polar_max_iter, polar_wolf, polar_rrms, damp_type;
     double polar_gamma, polar_damp, polar_precision, polar_wolf_alpha;
