@@ -207,7 +207,9 @@ void mpmc_hip_destroy(mpmc_hip_ctx *ctx);
  *   "gs_fault_sweep"      test hook: in sweep number `value` of a call one block is never published (the call must
  *                          fail with a hand-off error, tests/test_gpu_parity.py);
  *   "step_graph"          (default 0): replay a steady-state MC step as a HIP graph (bit-identical; measured
- *                          slower than direct launches on ROCm 7.2). */
+ *                          slower than direct launches on ROCm 7.2);
+ *   "cavity_incremental"  (default 1): 0 = mpmc_hip_cavity_update() answers 1 to every non-empty edit (A/B; same bits).
+ *                          A knob of the cavity grid, kept with the grid's state: it touches nothing of an evaluation. */
 int mpmc_hip_set_option(mpmc_hip_ctx *ctx, const char *name, int value);
 
 void mpmc_hip_default_params(mpmc_hip_params *p);
@@ -369,6 +371,38 @@ int mpmc_hip_get_polarizability_tensor(mpmc_hip_ctx *ctx, double out[9]);
  * returns 0 and the count is that of the configuration. */
 int mpmc_hip_set_autoreject(mpmc_hip_ctx *ctx, double scale);
 int mpmc_hip_get_close_contacts(mpmc_hip_ctx *ctx, long long *count);
+
+/* cavity_bias (reference src/mc/cavity.c:17-179): the cavity grid.  With G = cavity_grid_size and P = G^3, grid point
+ * g = (i G + j) G + k sits at the fractional coordinates ((i+1)/(G+1), (j+1)/(G+1), (k+1)/(G+1)) - 1/2 of the cell,
+ *     pos[p] = ((b[0][p] c0 + b[1][p] c1) + b[2][p] c2) - 0.5 b[0][p] - 0.5 b[1][p] - 0.5 b[2][p]
+ * evaluated left to right in fp64 without contraction.  occupancy[g] = the number of binned positions w with
+ * sqrt(((gx-wx)^2 + (gy-wy)^2) + (gz-wz)^2) < cavity_radius -- no minimum image: the caller passes the reference's
+ * wrapped_pos -- decided exactly as a correctly rounded sqrt decides (the device compares the square with the smallest
+ * double T whose square root is >= cavity_radius).  A point is open when its occupancy is 0; a dart hits when it is closer
+ * than cavity_radius, in the same sense, to some open point.
+ * The grid is state of the context, independent of the atom slots: upload, update_atoms, insert / remove and energy()
+ * leave it alone; the caller names the positions that are binned, that leave and that enter.  set_box / scale_box move
+ * the points and invalidate the occupancy.  None of these calls is allowed between energy_begin() and energy_end().
+ *   set_cavity_grid   grid_size 1 .. 64 and cavity_radius > 0 switch the grid on (a larger grid_size is refused by name);
+ *                     grid_size 0 switches it off.  A setting like mpmc_hip_set_rd_crystal(): it persists across uploads.
+ *                     The occupancy is invalid until the next cavity_bin.
+ *   cavity_bin        the from-scratch occupancy of these n positions (n = 0 is valid); replaces what was there.
+ *   cavity_update     first the edit: occupancy += (in points within the radius) - (out points within it), n_out = n_in =
+ *                     0 allowed; then the list of the open points in ascending g and its length *cavities_open; then
+ *                     the darts (dart_xyz [n_darts][3], n_darts = 0 allowed): *hits = how many of them hit.
+ *                     Return 0 = done; 1 = cannot be done incrementally (more than 16 points either way, option
+ *                     "cavity_incremental" 0 with a non-empty edit, or no valid occupancy): cavity_bin the current
+ *                     positions and call again with an empty edit; < 0 = error.
+ *   cavity_point      the index-th open point of the last cavity_update, by flat index and position; an index outside
+ *                     [0, cavities_open) is an error.
+ *   download_cavity_grid  occupancy [P] and pos [P][3], for tests and tools; either pointer may be NULL, not both.
+ * Option "cavity_incremental" (default 1; mpmc_hip_set_option): 0 = cavity_update answers 1 to every non-empty edit (A/B). */
+int mpmc_hip_set_cavity_grid(mpmc_hip_ctx *ctx, int grid_size, double radius);
+int mpmc_hip_cavity_bin(mpmc_hip_ctx *ctx, int n, const double *x, const double *y, const double *z);
+int mpmc_hip_cavity_update(mpmc_hip_ctx *ctx, int n_out, const double *out_xyz, int n_in, const double *in_xyz,
+                           int n_darts, const double *dart_xyz, int *cavities_open, int *hits);
+int mpmc_hip_cavity_point(mpmc_hip_ctx *ctx, int index, int *grid_index, double pos[3]);
+int mpmc_hip_download_cavity_grid(mpmc_hip_ctx *ctx, int *occupancy, double *pos);
 
 /* New coordinates for atoms [first, first+count): the delta after one MC move
  * (make_move perturbs one molecule, mc_moves.c:567). */

@@ -168,6 +168,22 @@ void hook_volume_change(system_t *system, const double delta_pos[3]) {
     if (hip_delta) energy_hip_note_volume_change(system, hip_delta);
     free(hip_delta);
 }
+/* src/mc/cavity.c, cavity_update_grid() (:112), first statement: with `hip on` the grid lives on the device.  The binding
+ * draws the darts of cavity_volume() itself (same get_rand() calls, same order) and fills cavities_open, cavity_volume
+ * and nodestats->cavity_bias_probability; system->cavity_grid stays unused (setup_cavity_grid() may still allocate it) */
+void hook_cavity_update_grid(system_t *system) {
+    if (system->hip) {
+        energy_hip_cavity_update(system);
+        return;
+    }
+    /* ... unchanged CPU path ... */
+}
+/* src/mc/mc_moves.c, make_move(), MOVETYPE_INSERT under cavity_bias (:587-606): the scan of cavity_grid that lists the
+ * open points is skipped, the position of the random_index-th open point comes from the device.  `random_index` and
+ * `com` are the function's own variables; the draw of random_index (:603) stays where it is, in front of this line */
+void hook_make_move_cavity_point(system_t *system, int random_index, double com[3]) {
+    if (system->hip) energy_hip_cavity_point(system, random_index, com);
+}
 /* restore(), default branch (:778-797), where the backup is linked into the list in place of the altered node: */
 void hook_restore_displace(system_t *system) {
     energy_hip_note_moved(system, system->checkpoint->molecule_backup, system->checkpoint->molecule_altered);

@@ -49,6 +49,7 @@
 #include "kernels_symv.h"
 #include "kernels_coef.h"
 #include "kernels_volume.h"
+#include "kernels_cavity.h"
 
 using namespace mpmc;
 
@@ -484,6 +485,25 @@ struct mpmc_hip_ctx {
     // ---- cavity_autoreject_absolute (mpmc_hip_set_autoreject): a context setting, persists across uploads
     double autoreject_scale = 0.0;       // 0 = off
     long long close_contacts = 0;        // of the last completed energy_end()
+    // ---- cavity_bias (mpmc_hip_set_cavity_grid): the cavity grid, kernels_cavity.h.  A context setting: it persists across
+    // uploads and is independent of the atom slots -- the caller names the positions that are binned, leave and enter.
+    int cav_G = 0, cav_P = 0;            // cavity_grid_size (0 = off) and G^3
+    double cav_radius = 0.0, cav_T = 0.0;  // cavity_radius; the smallest double with sqrt(T) >= radius
+    DevBuf<double> d_cav_pos;            // [3][P] grid point positions ...
+    bool cav_pos_valid = false;          // ... of the current box
+    DevBuf<int> d_cav_occ;               // [P]
+    bool cav_occ_valid = false;          // binned since the grid was set / the box changed
+    DevBuf<int> d_cav_open;              // [P] open_list of the last update
+    int cav_open = -1;                   // its length (-1: no update since the occupancy was last replaced)
+    int cav_incremental = 1;             // option "cavity_incremental": 0 = cavity_update answers 1 to every non-empty edit
+    DevBuf<int> d_cav_blk;               // [2][ceil(P / 256)] open points per workgroup, and their exclusive scan
+    DevBuf<int> d_cav_cnt;               // [CAV_NCOUNTER]
+    DevBuf<double> d_cav_atoms, d_cav_darts;  // [3][n] positions of a full bin; [n_darts][3]
+    DevBuf<int> d_cav_dart_hit;          // [n_darts] 1 = the dart lies in an open sphere
+    PinnedBuf<double> h_cav_stage;       // pinned staging of either (each call that fills it waits for its copy)
+    PinnedBuf<double> h_cav;             // pinned, mapped: the CavRecord
+    double *h_cav_dev = nullptr;
+    unsigned long long cav_seq = 0;
     double lrc_cached = 0.0;
     DevBuf<KVec> d_kvec;
     int nk = 0;
@@ -789,6 +809,12 @@ static const OptionRow kOptions[] = {
 
 extern "C" int mpmc_hip_set_option(mpmc_hip_ctx *c, const char *name, int value) {
     if (!c || !name) return fail("MPMC_HIP: set_option: null argument");
+    // The cavity grid's knob is state of that grid, not of an evaluation: kOptions below holds the knobs of energy(), whose
+    // change completes pending sweeps and retires a captured step; this one touches neither.
+    if (!strcmp(name, "cavity_incremental")) {
+        c->cav_incremental = value;
+        return 0;
+    }
     if (complete_pending_sweep(c)) return -1;  // (launched under the options of the call it belongs to)
     ++c->config_rev;
     for (const OptionRow &o : kOptions) {
@@ -975,6 +1001,8 @@ static void params_or_grid_changed(mpmc_hip_ctx *c) {
 // apply_box(): the sums of parameters, cutoff and volume (those over positions go with all_dirty)
 static void box_changed(mpmc_hip_ctx *c) {
     c->lrc.valid = c->disp_lrc.valid = c->rdc_static.valid = c->rep_lrc.valid = c->vdw_lrc.valid = false;
+    c->cav_pos_valid = c->cav_occ_valid = false;  // the cavity grid's points are fractions of the cell
+    c->cav_open = -1;
 }
 // upload(): everything per-atom (the pair / field partials go with all_dirty; the rd_crystal SETTING stays)
 static void atoms_replaced(mpmc_hip_ctx *c) {
@@ -3201,6 +3229,218 @@ extern "C" int mpmc_hip_download_ranking(mpmc_hip_ctx *c, double *rank_metric, i
         }
         memcpy(ranked_array, perm.data(), c->n * sizeof(int));
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// CavityGrid: the grid of cavity_bias (kernels_cavity.h).  State of the context that nothing but
+// these calls and a box change touches: it knows no atom slot, so upload(), update_atoms(), insert / remove and energy()
+// leave it alone.  Everything runs on the main stream; update and point wait for their record.
+// ---------------------------------------------------------------------------------------------
+// the smallest double T with sqrt(T) >= radius: sqrt(s) < radius <=> s < T for every s (sqrt is monotone)
+static double cavity_threshold(double radius) {
+    double t = radius * radius;
+    while (std::sqrt(t) < radius) t = std::nextafter(t, INFINITY);
+    for (;;) {
+        const double below = std::nextafter(t, 0.0);
+        if (below == t || std::sqrt(below) < radius) break;
+        t = below;
+    }
+    return t;
+}
+
+static int cavity_grid_dim(const mpmc_hip_ctx *c) { return (c->cav_P + kCavThreads - 1) / kCavThreads; }
+
+static int cavity_ensure_points(mpmc_hip_ctx *c) {
+    if (c->cav_pos_valid) return 0;
+    if (!c->have_box) return fail("MPMC_HIP: cavity grid: no box set");
+    CavityFrac f;
+    memset(&f, 0, sizeof(f));
+    for (int i = 0; i < c->cav_G; ++i) f.c[i] = ((double)(i + 1)) / ((double)(c->cav_G + 1));
+    CavityBasis bs;
+    memcpy(bs.b, c->basis, sizeof(bs.b));
+    hipLaunchKernelGGL(cavity_points_kernel, dim3(cavity_grid_dim(c)), dim3(kCavThreads), 0, c->stream, c->cav_G, f, bs,
+                       c->d_cav_pos.get(), c->d_cav_pos.get() + c->cav_P, c->d_cav_pos.get() + 2 * (size_t)c->cav_P);
+    HIPCHK(hipGetLastError());
+    c->cav_pos_valid = true;
+    return 0;
+}
+
+// `count` doubles from the caller to `dst` through the pinned staging buffer; the caller of this waits for the stream
+// before the staging buffer is filled again
+static int cavity_stage(mpmc_hip_ctx *c, DevBuf<double> &dst, const double *const *src, const size_t *len, int nsrc) {
+    size_t count = 0;
+    for (int k = 0; k < nsrc; ++k) count += len[k];
+    if (count == 0) return 0;
+    if (dst.size() < count || c->h_cav_stage.size() < count) {
+        HIPCHK(hipStreamSynchronize(c->stream));  // (growth only: an earlier launch may still read the old buffer)
+        if (dst.size() < count) HIPCHK(dst.alloc(count + count / 2));
+        if (c->h_cav_stage.size() < count) HIPCHK(c->h_cav_stage.alloc(count + count / 2));
+    }
+    size_t at = 0;
+    for (int k = 0; k < nsrc; ++k) {
+        memcpy(c->h_cav_stage + at, src[k], len[k] * sizeof(double));
+        at += len[k];
+    }
+    HIPCHK(hipMemcpyAsync(dst, c->h_cav_stage, count * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
+extern "C" int mpmc_hip_set_cavity_grid(mpmc_hip_ctx *c, int grid_size, double radius) {
+    if (!c) return fail("MPMC_HIP: set_cavity_grid: null context");
+    if (c->in_flight) return fail("MPMC_HIP: set_cavity_grid between energy_begin() and energy_end()");
+    if (grid_size < 0 || grid_size > kCavMaxGrid)
+        return fail("MPMC_HIP: set_cavity_grid: cavity_grid %d is not supported (1 .. %d; 0 = off)", grid_size, kCavMaxGrid);
+    if (grid_size > 0 && (!(radius > 0.0) || !std::isfinite(radius)))
+        return fail("MPMC_HIP: set_cavity_grid: invalid cavity grid or radius specified (cavity_radius %g)", radius);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));  // (an earlier launch may still read the buffers replaced below)
+    c->cav_pos_valid = c->cav_occ_valid = false;
+    c->cav_open = -1;
+    if (grid_size == 0) {
+        c->cav_G = c->cav_P = 0;
+        c->d_cav_pos.reset();
+        c->d_cav_occ.reset();
+        c->d_cav_open.reset();
+        c->d_cav_blk.reset();
+        return 0;
+    }
+    const size_t P = (size_t)grid_size * grid_size * grid_size;
+    c->cav_G = 0;  // (off, should an allocation below fail)
+    if (c->d_cav_pos.size() != 3 * P) {
+        HIPCHK(c->d_cav_pos.alloc(3 * P));
+        HIPCHK(c->d_cav_occ.alloc(P));
+        HIPCHK(c->d_cav_open.alloc(P));
+        HIPCHK(c->d_cav_blk.alloc(2 * ((P + kCavThreads - 1) / kCavThreads)));
+    }
+    if (!c->d_cav_cnt) HIPCHK(c->d_cav_cnt.alloc(CAV_NCOUNTER));
+    if (!c->h_cav) {
+        HIPCHK(c->h_cav.alloc(CR_COUNT, hipHostMallocMapped));
+        memset(c->h_cav, 0, CR_COUNT * sizeof(double));
+        HIPCHK(hipHostGetDevicePointer((void **)&c->h_cav_dev, c->h_cav, 0));
+    }
+    c->cav_G = grid_size;
+    c->cav_P = (int)P;
+    c->cav_radius = radius;
+    c->cav_T = cavity_threshold(radius);
+    return 0;
+}
+
+static int cavity_check(mpmc_hip_ctx *c, const char *what) {
+    if (!c) return fail("MPMC_HIP: %s: null context", what);
+    if (c->in_flight) return fail("MPMC_HIP: %s between energy_begin() and energy_end()", what);
+    if (c->cav_G == 0) return fail("MPMC_HIP: %s: the cavity grid is off (mpmc_hip_set_cavity_grid)", what);
+    HIPCHK(hipSetDevice(c->device));
+    return 0;
+}
+
+extern "C" int mpmc_hip_cavity_bin(mpmc_hip_ctx *c, int n, const double *x, const double *y, const double *z) {
+    if (cavity_check(c, "cavity_bin")) return -1;
+    if (n < 0) return fail("MPMC_HIP: cavity_bin: n = %d", n);
+    if (n > 0 && (!x || !y || !z)) return fail("MPMC_HIP: cavity_bin: null argument");
+    if (cavity_ensure_points(c)) return -1;
+    c->cav_occ_valid = false;
+    c->cav_open = -1;
+    const double *src[3] = {x, y, z};
+    const size_t len[3] = {(size_t)n, (size_t)n, (size_t)n};
+    if (cavity_stage(c, c->d_cav_atoms, src, len, 3)) return -1;
+    const double *a = c->d_cav_atoms, *g = c->d_cav_pos;
+    const size_t P = (size_t)c->cav_P;
+    hipLaunchKernelGGL(cavity_bin_kernel, dim3(cavity_grid_dim(c)), dim3(kCavThreads), 0, c->stream, c->cav_P, g, g + P,
+                       g + 2 * P, n, a, a + n, a + 2 * (size_t)n, c->cav_T, c->d_cav_occ.get());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));  // (the staging buffer is free again; a full bin is the rare path)
+    c->cav_occ_valid = true;
+    return 0;
+}
+
+extern "C" int mpmc_hip_cavity_update(mpmc_hip_ctx *c, int n_out, const double *out_xyz, int n_in, const double *in_xyz,
+                                      int n_darts, const double *dart_xyz, int *cavities_open, int *hits) {
+    if (cavity_check(c, "cavity_update")) return -1;
+    if (n_out < 0 || n_in < 0 || n_darts < 0)
+        return fail("MPMC_HIP: cavity_update: negative count (%d out, %d in, %d darts)", n_out, n_in, n_darts);
+    if ((n_out > 0 && !out_xyz) || (n_in > 0 && !in_xyz) || (n_darts > 0 && !dart_xyz) || !cavities_open || !hits)
+        return fail("MPMC_HIP: cavity_update: null argument");
+    if (!c->cav_occ_valid || n_out > kCavMaxEdit || n_in > kCavMaxEdit) return 1;
+    if (n_out + n_in > 0 && !c->cav_incremental) return 1;
+    CavityEdit ed;
+    memset(&ed, 0, sizeof(ed));
+    ed.n_out = n_out;
+    ed.n_in = n_in;
+    if (n_out > 0) memcpy(ed.out, out_xyz, 3 * (size_t)n_out * sizeof(double));
+    if (n_in > 0) memcpy(ed.in, in_xyz, 3 * (size_t)n_in * sizeof(double));
+    const size_t nd = 3 * (size_t)n_darts;
+    if (cavity_stage(c, c->d_cav_darts, &dart_xyz, &nd, 1)) return -1;
+    if (c->d_cav_dart_hit.size() < (size_t)n_darts) {
+        HIPCHK(hipStreamSynchronize(c->stream));  // (growth only)
+        HIPCHK(c->d_cav_dart_hit.alloc((size_t)n_darts + (size_t)n_darts / 2));
+    }
+    const double *g = c->d_cav_pos;
+    const size_t P = (size_t)c->cav_P;
+    const int nb = cavity_grid_dim(c);
+    int *blk_open = c->d_cav_blk, *blk_off = c->d_cav_blk.get() + nb;
+    hipLaunchKernelGGL(cavity_edit_kernel, dim3(nb), dim3(kCavThreads), 0, c->stream, c->cav_P, g, g + P, g + 2 * P, ed,
+                       c->cav_T, c->d_cav_occ.get(), blk_open);
+    hipLaunchKernelGGL(cavity_scan_kernel, dim3(1), dim3(kCavThreads), 0, c->stream, nb, (const int *)blk_open, blk_off,
+                       c->d_cav_cnt.get(), n_darts, c->d_cav_dart_hit.get());
+    hipLaunchKernelGGL(cavity_scatter_kernel, dim3(nb), dim3(kCavThreads), 0, c->stream, c->cav_P,
+                       (const int *)c->d_cav_occ, (const int *)blk_off, c->d_cav_open.get());
+    if (n_darts > 0) {
+        // the open list is shared out over enough workgroups to fill the device: the darts alone are too few waves
+        const int dart_blocks = (n_darts + kCavThreads - 1) / kCavThreads;
+        const int slices = std::max(1, std::min(nb, (4 * c->num_cus + dart_blocks - 1) / dart_blocks));
+        hipLaunchKernelGGL(cavity_darts_kernel, dim3(dart_blocks, slices), dim3(kCavThreads), 0, c->stream, n_darts,
+                           (const double *)c->d_cav_darts, (const int *)c->d_cav_open, g, g + P, g + 2 * P, c->cav_T,
+                           (const int *)c->d_cav_cnt, c->d_cav_dart_hit.get());
+    }
+    const double seq = (double)++c->cav_seq;
+    hipLaunchKernelGGL(cavity_publish_kernel, dim3(1), dim3(kCavThreads), 0, c->stream, n_darts,
+                       (const int *)c->d_cav_dart_hit, (const int *)c->d_cav_cnt, c->h_cav_dev, seq);
+    HIPCHK(hipGetLastError());
+    if (wait_sequence(c->h_cav + CR_SEQ, seq, c->stream)) return -1;
+    if (c->h_cav[CR_SEQ] != seq) return fail("MPMC_HIP: cavity_update: the record did not arrive");
+    c->cav_open = (int)c->h_cav[CR_OPEN];
+    *cavities_open = c->cav_open;
+    *hits = (int)c->h_cav[CR_HITS];
+    return 0;
+}
+
+extern "C" int mpmc_hip_cavity_point(mpmc_hip_ctx *c, int index, int *grid_index, double pos[3]) {
+    if (cavity_check(c, "cavity_point")) return -1;
+    if (!grid_index || !pos) return fail("MPMC_HIP: cavity_point: null argument");
+    if (c->cav_open < 0) return fail("MPMC_HIP: cavity_point: no cavity_update since the occupancy was replaced");
+    if (index < 0 || index >= c->cav_open)
+        return fail("MPMC_HIP: cavity_point: index %d outside the %d open points", index, c->cav_open);
+    const double *g = c->d_cav_pos;
+    const size_t P = (size_t)c->cav_P;
+    const double seq = (double)++c->cav_seq;
+    hipLaunchKernelGGL(cavity_pick_kernel, dim3(1), dim3(64), 0, c->stream, index, (const int *)c->d_cav_open, g, g + P,
+                       g + 2 * P, c->h_cav_dev, seq);
+    HIPCHK(hipGetLastError());
+    if (wait_sequence(c->h_cav + CR_SEQ, seq, c->stream)) return -1;
+    if (c->h_cav[CR_SEQ] != seq) return fail("MPMC_HIP: cavity_point: the record did not arrive");
+    *grid_index = (int)c->h_cav[CR_PICK_G];
+    for (int p = 0; p < 3; ++p) pos[p] = c->h_cav[CR_PICK_X + p];
+    return 0;
+}
+
+extern "C" int mpmc_hip_download_cavity_grid(mpmc_hip_ctx *c, int *occupancy, double *pos) {
+    if (cavity_check(c, "download_cavity_grid")) return -1;
+    if (!occupancy && !pos) return fail("MPMC_HIP: download_cavity_grid: null argument");
+    const size_t P = (size_t)c->cav_P;
+    if (occupancy) {
+        if (!c->cav_occ_valid) return fail("MPMC_HIP: download_cavity_grid: no occupancy (mpmc_hip_cavity_bin) for this grid and box");
+        HIPCHK(hipMemcpyAsync(occupancy, c->d_cav_occ, P * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (pos) {
+        if (cavity_ensure_points(c)) return -1;
+        std::vector<double> soa(3 * P);
+        HIPCHK(hipMemcpyAsync(soa.data(), c->d_cav_pos, 3 * P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (size_t g = 0; g < P; ++g)
+            for (int p = 0; p < 3; ++p) pos[3 * g + p] = soa[p * P + g];
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
 

@@ -19,6 +19,8 @@ EXPORTS = [
     "mpmc_hip_upload", "mpmc_hip_set_dispersion", "mpmc_hip_set_axilrod_teller", "mpmc_hip_get_three_body_energy",
     "mpmc_hip_set_rd_crystal", "mpmc_hip_set_vdw", "mpmc_hip_get_vdw_energy", "mpmc_hip_get_vdw_terms",
     "mpmc_hip_set_autoreject", "mpmc_hip_get_close_contacts",
+    "mpmc_hip_set_cavity_grid", "mpmc_hip_cavity_bin", "mpmc_hip_cavity_update", "mpmc_hip_cavity_point",
+    "mpmc_hip_download_cavity_grid",
     "mpmc_hip_set_exact_polar", "mpmc_hip_get_polarizability_tensor",
     "mpmc_hip_update_atoms", "mpmc_hip_insert_molecule", "mpmc_hip_remove_molecule",
     "mpmc_hip_slot_count", "mpmc_hip_set_sweep_order", "mpmc_hip_energy", "mpmc_hip_energy_begin", "mpmc_hip_energy_end",
@@ -166,6 +168,12 @@ def load():
     lib.mpmc_hip_get_polarizability_tensor.argtypes = [vp, dp]
     lib.mpmc_hip_set_autoreject.argtypes = [vp, C.c_double]
     lib.mpmc_hip_get_close_contacts.argtypes = [vp, C.POINTER(C.c_longlong)]
+    ip = C.POINTER(C.c_int)
+    lib.mpmc_hip_set_cavity_grid.argtypes = [vp, C.c_int, C.c_double]
+    lib.mpmc_hip_cavity_bin.argtypes = [vp, C.c_int, vp, vp, vp]
+    lib.mpmc_hip_cavity_update.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, ip, ip]
+    lib.mpmc_hip_cavity_point.argtypes = [vp, C.c_int, ip, dp]
+    lib.mpmc_hip_download_cavity_grid.argtypes = [vp, vp, vp]
     lib.mpmc_hip_update_atoms.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     lib.mpmc_hip_insert_molecule.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
     lib.mpmc_hip_remove_molecule.argtypes = [vp, C.c_int, C.c_int]
@@ -354,6 +362,50 @@ class Engine:
         v = C.c_longlong(0)
         _chk(self.lib.mpmc_hip_get_close_contacts(self.ctx, C.byref(v)))
         return v.value
+
+    def set_cavity_grid(self, grid_size, radius=0.0):
+        """The cavity grid of cavity_bias (mpmc_hip_set_cavity_grid): grid_size = cavity_grid (1 .. 64; 0 switches it off),
+        radius = cavity_radius.  A context setting: it persists across uploads; the occupancy is invalid until cavity_bin()."""
+        _chk(self.lib.mpmc_hip_set_cavity_grid(self.ctx, int(grid_size), float(radius)))
+        self.cavity_points = int(grid_size) ** 3
+
+    def cavity_bin(self, pos):
+        """The from-scratch occupancy of these positions [n, 3] (mpmc_hip_cavity_bin); n = 0 is valid."""
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        cols = [np.ascontiguousarray(pos[:, k]) for k in range(3)]
+        _chk(self.lib.mpmc_hip_cavity_bin(self.ctx, pos.shape[0], *[a.ctypes.data for a in cols]))
+
+    def cavity_update(self, out_pos=(), in_pos=(), darts=()):
+        """The edit (positions that leave / enter, [n, 3] each), the ordered list of the open points and the darts
+        ([n, 3]) in one call (mpmc_hip_cavity_update).  Returns (cavities_open, hits), or None when the engine asks for
+        cavity_bin() and a call with an empty edit instead."""
+        arrs = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3) for a in (out_pos, in_pos, darts)]
+        n_open, hits = C.c_int(-1), C.c_int(-1)
+        args = []
+        for a in arrs:
+            args += [a.shape[0], a.ctypes.data if a.shape[0] else None]
+        rc = self.lib.mpmc_hip_cavity_update(self.ctx, *args, C.byref(n_open), C.byref(hits))
+        if rc < 0:
+            _chk(rc)
+        if rc > 0:
+            return None
+        return n_open.value, hits.value
+
+    def cavity_point(self, index):
+        """(flat grid index, position [3]) of the index-th open point of the last cavity_update()."""
+        g = C.c_int(-1)
+        pos = (C.c_double * 3)()
+        _chk(self.lib.mpmc_hip_cavity_point(self.ctx, int(index), C.byref(g), pos))
+        return g.value, np.array([pos[0], pos[1], pos[2]])
+
+    def cavity_grid(self, occupancy=True):
+        """(occupancy [P] int32, positions [P, 3]) of the cavity grid (mpmc_hip_download_cavity_grid); occupancy=False gives
+        None in its place (there is none before the first cavity_bin() of a grid or box)."""
+        P = self.cavity_points
+        occ = np.zeros(P, dtype=np.int32) if occupancy else None
+        pos = np.zeros((P, 3))
+        _chk(self.lib.mpmc_hip_download_cavity_grid(self.ctx, occ.ctypes.data if occupancy else None, pos.ctypes.data))
+        return occ, pos
 
     def three_body_energy(self):
         """observables->three_body_energy of the last completed energy(); 0 while the term is off."""

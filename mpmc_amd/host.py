@@ -98,6 +98,12 @@ def load():
     lib.host_unsupported.argtypes = [vp]
     lib.host_unsupported.restype = C.c_char_p
     lib.host_get_polarizability_tensor.argtypes = [vp, vp]
+    lib.host_get_cavity_flags.argtypes = [vp, vp]
+    lib.host_get_cavity_flags.restype = None
+    lib.host_get_cavity.argtypes = [vp, vp]
+    lib.host_get_cavity.restype = C.c_int
+    lib.host_get_cavity_darts.argtypes = [vp, vp]
+    lib.host_get_cavity_darts.restype = None
     lib.volume_change.argtypes = [vp]
     lib.volume_change.restype = None
     lib.revert_volume_change.argtypes = [vp]
@@ -112,7 +118,8 @@ def config_text(flags, extra=None):
              "polar_esor", "polar_palmo", "polar_rrms", "polar_zodid", "polar_wolf", "polar_ewald", "wolf",
              "disp_expansion", "damp_dispersion", "extrapolate_disp_coeffs", "schmidt_mixing", "axilrod_teller",
              "midzuno_kihara_approx", "rd_crystal", "read_pqr_box", "calc_pressure", "polarvdw", "cdvdw",
-             "cavity_autoreject_absolute", "cdvdw_exp_repulsion", "cdvdw_sig_repulsion", "cdvdw_9th_repulsion",
+             "cavity_autoreject_absolute", "cavity_bias", "cdvdw_exp_repulsion", "cdvdw_sig_repulsion",
+             "cdvdw_9th_repulsion",
              "polar_iterative", "polarizability_tensor"}
     lines = []
     for k, v in flags.items():
@@ -218,6 +225,29 @@ class HostSystem:
         self.lib.host_get_vdw(self.ptr, out.ctypes.data)
         return dict(polarvdw=int(out[0]), cavity_autoreject_absolute=int(out[1]), cavity_autoreject_scale=out[2],
                     count_autorejects=int(out[3]), vdw_energy=out[4])
+
+    def cavity_flags(self):
+        """cavity_bias, cavity_grid and cavity_radius as read."""
+        out = np.zeros(3)
+        self.lib.host_get_cavity_flags(self.ptr, out.ctypes.data)
+        return dict(cavity_bias=int(out[0]), cavity_grid=int(out[1]), cavity_radius=out[2])
+
+    def cavity(self):
+        """The cavity-bias state after the last make_move(): the grid's counts for the configuration the move started from,
+        the running means, and whether the move takes the biased acceptance."""
+        out = np.zeros(10)
+        self.lib.host_get_cavity(self.ptr, out.ctypes.data)
+        return dict(cavities_open=int(out[0]), hits=int(out[1]), n_darts=int(out[2]), cavity_volume=out[3],
+                    cavity_bias_probability=out[4], avg_nodestats=out[5], avg_observables=out[6],
+                    biased_move=int(out[7]), boltzmann_factor=out[8], trial_energy=out[9])
+
+    def cavity_darts(self):
+        """The dart positions [n, 3] of the last make_move()'s grid update."""
+        out = np.zeros(10)
+        n = self.lib.host_get_cavity(self.ptr, out.ctypes.data)
+        darts = np.zeros((max(n, 0), 3))
+        self.lib.host_get_cavity_darts(self.ptr, darts.ctypes.data)
+        return darts
 
     def observables(self):
         out = np.zeros(8)

@@ -31,7 +31,18 @@ int host_apply_config(system_t *system, const char *text) {
     if (system->cavity_autoreject_absolute &&                                     /* check_input.c:872-878 */
         ((system->cavity_autoreject_scale <= 0.0) || (system->cavity_autoreject_scale > 1.78)))
         return 1;
+    if (check_cavity_bias(system)) return 1; /* check_input.c:880-892 */
     return 0;
+}
+
+/* what mc() does behind every step's accept / reject for one walker: the running means of the node statistics
+ * (mc.c:362) and, at every corrtime, their average over the walkers -- here the one (mc.c:438, :470) */
+static void step_statistics(system_t *system) {
+    update_nodestats(system->nodestats, system->avg_nodestats);
+    if (system->corrtime > 0 && !(system->step % system->corrtime)) {
+        clear_avg_nodestats(system);
+        update_root_nodestats(system, system->avg_nodestats, system->avg_observables);
+    }
 }
 
 /* run `nsteps` more MC steps on an initialised chain; returns accepted count */
@@ -40,6 +51,7 @@ int host_mc_steps(system_t *system, int nsteps) {
     if (system->step == 0 && system->avg_observables->counter == 0.0) {
         /* first call: initial energy + first checkpoint, as mc() does */
         system->observables->volume = system->pbc->volume;
+        if (system->cavity_bias) energy_hip_cavity_update(system); /* mc.c:245: the draws of its darts only */
         double e = energy(system);
         if (energy_hip_failed(system) || e != e) return -1;
         checkpoint(system);
@@ -67,6 +79,7 @@ int host_mc_steps(system_t *system, int nsteps) {
             ++system->nodestats->reject;
             if (volume_move) ++system->nodestats->reject_volume;
         }
+        step_statistics(system);
     }
     return system->nodestats->accept - acc0;
 }
@@ -81,6 +94,7 @@ int host_mc_steps_multi(system_t **systems, int nwalkers, int nsteps) {
         system_t *system = systems[w];
         if (system->step == 0 && system->avg_observables->counter == 0.0) {
             system->observables->volume = system->pbc->volume;
+            if (system->cavity_bias) energy_hip_cavity_update(system); /* mc.c:245 */
             double e = energy(system);
             if (energy_hip_failed(system) || e != e) return -1;
             checkpoint(system);
@@ -120,6 +134,7 @@ int host_mc_steps_multi(system_t **systems, int nwalkers, int nsteps) {
                 restore(system);
                 ++system->nodestats->reject;
             }
+            step_statistics(system);
         }
         if (failed) return -1;
     }
@@ -334,4 +349,37 @@ void host_force_volume_move(system_t *system, double new_volume, int revert) {
         memcpy(system->observables, system->checkpoint->observables, sizeof(observables_t));
         revert_volume_change(system);
     }
+}
+
+/* ---- cavity_bias ----------------------------------------------------------------------------------------------- */
+/* the keywords as read: cavity_bias, cavity_grid, cavity_radius */
+void host_get_cavity_flags(system_t *system, double out[3]) {
+    out[0] = (double)system->cavity_bias;
+    out[1] = (double)system->cavity_grid_size;
+    out[2] = system->cavity_radius;
+}
+/* the state after the last make_move(): cavities_open, hits and number of the darts, cavity_volume,
+ * nodestats->cavity_bias_probability, its running mean over this walker's steps (avg_nodestats), the corrtime mean over
+ * the walkers (avg_observables), checkpoint->biased_move, nodestats->boltzmann_factor, the last trial's energy (kept by the binding: restore() takes a
+ * rejected one out of the observables).  Returns the number of darts. */
+int host_get_cavity(system_t *system, double out[10]) {
+    int hits = 0;
+    const int n_darts = energy_hip_cavity_darts(system, NULL, &hits);
+    out[0] = (double)system->cavities_open;
+    out[1] = (double)hits;
+    out[2] = (double)n_darts;
+    out[3] = system->cavity_volume;
+    out[4] = system->nodestats->cavity_bias_probability;
+    out[5] = system->avg_nodestats->cavity_bias_probability;
+    out[6] = system->avg_observables->cavity_bias_probability;
+    out[7] = (double)system->checkpoint->biased_move;
+    out[8] = system->nodestats->boltzmann_factor;
+    out[9] = energy_hip_last_energy(system);
+    return n_darts;
+}
+/* the last make_move()'s dart positions, [n][3] with n = host_get_cavity()'s answer */
+void host_get_cavity_darts(system_t *system, double *darts) {
+    const double *d = NULL;
+    const int n = energy_hip_cavity_darts(system, &d, NULL);
+    if (d && n > 0) memcpy(darts, d, 3 * (size_t)n * sizeof(double));
 }

@@ -41,6 +41,13 @@ typedef struct {
     int slot, natoms, frozen;
 } resident_t;
 
+/* a molecule the cavity grid's occupancy holds: its list node then, and its run in the flat coordinate arrays */
+typedef struct {
+    molecule_t *mol;
+    atom_t *atoms;
+    int first, natoms, frozen;
+} cavity_entry_t;
+
 typedef struct shim_state {
     system_t *system;
     mpmc_hip_ctx *ctx;
@@ -53,6 +60,7 @@ typedef struct shim_state {
     int exact;     /* the exact dipoles (polarization with polar_iterative off) as sent with that upload */
     double ar_scale; /* cavity_autoreject_scale as sent with that upload (0: cavity_autoreject_absolute off) */
     int failed;   /* device / ABI failure of the last call */
+    double last_energy; /* what the last energy_hip_end() returned (restore() takes a rejected trial's out of the observables) */
     mpmc_hip_params params; /* as last sent */
     /* host image of the device, by DEVICE SLOT (the engine keeps its own atom order once molecules are inserted
      * or removed): coordinates as last sent, and the parameters that tell species apart */
@@ -74,6 +82,21 @@ typedef struct shim_state {
     /* noted volume moves (energy_hip_note_volume_change): one displacement per resident molecule, in list order */
     int nvol, vol_notes_off;
     double *vol_delta[4];
+    /* cavity_bias (energy_hip_cavity_update): the grid as sent, and what the device's occupancy was last given -- the
+     * molecules in LIST order with their coordinates as read then (raw) and as binned (wrapped), flat, molecule after
+     * molecule.  Independent of the residents above: the grid knows no device slot, and at the top of make_move() the
+     * resident configuration still is the previous trial's. */
+    mpmc_hip_ctx *cav_ctx; /* the context the grid was set on */
+    int cav_grid;
+    double cav_radius;
+    int cav_valid; /* the table below is what the device holds */
+    cavity_entry_t *cav, *cav2;
+    int ncav, cav_cap;
+    double *cav_raw, *cav_raw2, *cav_wrapped, *cav_wrapped2; /* [3 * cav_atoms_cap] each */
+    int cav_atoms, cav_atoms_cap;
+    double *cav_darts; /* [cav_ndarts][3]: the last call's dart positions */
+    int cav_ndarts, cav_darts_cap, cav_hits;
+    int cav_failed; /* a device / ABI failure in a cavity call: the next energy_hip() reports it (sticky) */
     int timing;
     mpmc_hip_timings tsum;
     int walker_rank, walker_nranks;
@@ -116,6 +139,8 @@ void energy_hip_cleanup(system_t *system) {
     free_image(st);
     for (int v = 0; v < st->nvol; v++) free(st->vol_delta[v]);
     free(st->res); free(st->res2); free(st->mols);
+    free(st->cav); free(st->cav2); free(st->cav_raw); free(st->cav_raw2); free(st->cav_wrapped); free(st->cav_wrapped2);
+    free(st->cav_darts);
     free(st);
 }
 
@@ -130,6 +155,10 @@ mpmc_hip_ctx *energy_hip_context(system_t *system) {
 int energy_hip_failed(system_t *system) {
     shim_state *st = state_of(system, 0);
     return st ? st->failed : 0;
+}
+double energy_hip_last_energy(system_t *system) {
+    shim_state *st = state_of(system, 0);
+    return st ? st->last_energy : 0.0;
 }
 void energy_hip_enable_timing(system_t *system, int on) {
     shim_state *st = state_of(system, 1);
@@ -697,6 +726,260 @@ static int sync_walk(shim_state *st, system_t *system) {
     return 0;
 }
 
+/* ---- cavity_bias: the grid of the reference's src/mc/cavity.c on the device ---------------------------------------- */
+
+/* a failure of a cavity call: its message, energy()'s failure channel (the next energy_hip() stops the chain), and the
+ * table dropped */
+static int cavity_failed(shim_state *st, const char *what) {
+    if (what) hip_fail(what);
+    if (!st) return -1;
+    st->failed = 1;
+    st->cav_failed = 1;
+    st->cav_valid = 0;
+    return -1;
+}
+
+static int cavity_reserve(shim_state *st, int nmol, int natoms) {
+    if (st->cav_cap < nmol) {
+        const int cap = 2 * nmol + 64;
+        cavity_entry_t *a = realloc(st->cav, cap * sizeof(cavity_entry_t)), *b = realloc(st->cav2, cap * sizeof(cavity_entry_t));
+        if (a) st->cav = a;
+        if (b) st->cav2 = b;
+        if (!a || !b) return -1;
+        st->cav_cap = cap;
+    }
+    if (st->cav_atoms_cap < natoms) {
+        const int cap = 2 * natoms + 64;
+        double **arr[4] = {&st->cav_raw, &st->cav_raw2, &st->cav_wrapped, &st->cav_wrapped2};
+        int bad = 0;
+        for (int k = 0; k < 4; k++) { /* (realloc keeps what the live pair holds) */
+            double *p = realloc(*arr[k], 3 * (size_t)cap * sizeof(double));
+            if (p) *arr[k] = p;
+            else bad = 1;
+        }
+        if (bad) return -1;
+        st->cav_atoms_cap = cap;
+    }
+    return 0;
+}
+
+/* wrapped_pos of one molecule as wrapall() leaves it (output.c:142-183): the tree's own function on a list of one */
+static void cavity_wrap_one(molecule_t *m, pbc_t *pbc) {
+    molecule_t *next = m->next;
+    m->next = NULL;
+    wrapall(m, pbc);
+    m->next = next;
+}
+
+/* list node m as entry e with its coordinates at atom offset `first` of raw / wrapped (wrapped_pos must be current) */
+static void cavity_record(cavity_entry_t *e, molecule_t *m, int first, double *raw, double *wrapped) {
+    int k = first;
+    for (atom_t *a = m->atoms; a; a = a->next, k++)
+        for (int p = 0; p < 3; p++) {
+            raw[3 * k + p] = a->pos[p];
+            wrapped[3 * k + p] = a->wrapped_pos[p];
+        }
+    e->mol = m; e->atoms = m->atoms; e->first = first; e->natoms = k - first; e->frozen = (m->frozen != 0);
+}
+
+/* does list node m still hold exactly what entry e was binned from?  (same_place() for this table) */
+static int cavity_same(const shim_state *st, const molecule_t *m, const cavity_entry_t *e) {
+    if ((m->frozen != 0) != e->frozen) return 0;
+    if (e->frozen) return m->atoms == e->atoms || natoms_of(m) == e->natoms;
+    int k = 0, moved = 0;
+    const double *raw = st->cav_raw + 3 * (size_t)e->first;
+    for (const atom_t *a = m->atoms; a; a = a->next, k++) {
+        if (k == e->natoms) return 0;
+        moved |= (a->pos[0] != raw[3 * k]) | (a->pos[1] != raw[3 * k + 1]) | (a->pos[2] != raw[3 * k + 2]);
+    }
+    return k == e->natoms && !moved;
+}
+
+/* The difference between what was last binned and the list as it is now -- the accepted configuration at the top of
+ * make_move() -- as the points that leave (out_xyz) and enter (in_xyz) the occupancy, at most 16 each.  Front to back as
+ * sync_walk(): a node that holds what an entry holds is that entry; else the node is new if the node behind it is the
+ * entry (an insertion goes in front of the molecule it was copied from), the entry is gone if the node is the next entry,
+ * and else the node is the entry displaced.  Only new and displaced molecules are wrapped.  Returns 1 when no such
+ * difference can be stated (the caller bins from scratch). */
+static int cavity_diff(shim_state *st, system_t *system, double *out_xyz, int *n_out, double *in_xyz, int *n_in) {
+    const int nm = list_to_array(st, system);
+    if (nm < 0) return 1;
+    if (cavity_reserve(st, nm, st->cav_atoms + 16)) return 1; /* (at most 16 atoms enter, or the answer is 1) */
+    molecule_t **mols = st->mols;
+    cavity_entry_t *old = st->cav, *out = st->cav2;
+    int i = 0, j = 0, n2 = 0, at = 0;
+    *n_out = *n_in = 0;
+    while (i < nm || j < st->ncav) {
+        int keep = 0, fresh = 0, gone = 0;
+        if (i < nm && j < st->ncav && cavity_same(st, mols[i], &old[j]))
+            keep = 1;
+        else if (i + 1 < nm && j < st->ncav && cavity_same(st, mols[i + 1], &old[j]))
+            fresh = 1;
+        else if (i < nm && j + 1 < st->ncav && cavity_same(st, mols[i], &old[j + 1]))
+            gone = 1;
+        else if (i < nm && j < st->ncav && !old[j].frozen && !mols[i]->frozen && natoms_of(mols[i]) == old[j].natoms)
+            fresh = gone = 1; /* displaced: leaves where it was, enters where it is */
+        else if (i == nm)
+            gone = 1;
+        else if (j == st->ncav)
+            fresh = 1;
+        else
+            return 1;
+        if (keep) {
+            const int n = old[j].natoms;
+            memcpy(st->cav_raw2 + 3 * (size_t)at, st->cav_raw + 3 * (size_t)old[j].first, 3 * (size_t)n * sizeof(double));
+            memcpy(st->cav_wrapped2 + 3 * (size_t)at, st->cav_wrapped + 3 * (size_t)old[j].first, 3 * (size_t)n * sizeof(double));
+            out[n2] = old[j++];
+            out[n2].mol = mols[i];
+            out[n2].atoms = mols[i++]->atoms;
+            out[n2++].first = at;
+            at += n;
+            continue;
+        }
+        if (gone) {
+            const int n = old[j].natoms;
+            if (*n_out + n > 16) return 1;
+            memcpy(out_xyz + 3 * *n_out, st->cav_wrapped + 3 * (size_t)old[j].first, 3 * (size_t)n * sizeof(double));
+            *n_out += n;
+            j++;
+        }
+        if (fresh) {
+            const int n = natoms_of(mols[i]);
+            if (*n_in + n > 16 || at + n > st->cav_atoms_cap) return 1;
+            cavity_wrap_one(mols[i], system->pbc);
+            cavity_record(&out[n2++], mols[i++], at, st->cav_raw2, st->cav_wrapped2);
+            memcpy(in_xyz + 3 * *n_in, st->cav_wrapped2 + 3 * (size_t)at, 3 * (size_t)n * sizeof(double));
+            *n_in += n;
+            at += n;
+        }
+    }
+    st->cav = out; st->cav2 = old;
+    double *t = st->cav_raw; st->cav_raw = st->cav_raw2; st->cav_raw2 = t;
+    t = st->cav_wrapped; st->cav_wrapped = st->cav_wrapped2; st->cav_wrapped2 = t;
+    st->ncav = n2;
+    st->cav_atoms = at;
+    return 0;
+}
+
+/* the from-scratch occupancy: every molecule wrapped (wrapall(), as pairs.c:334 does on every step), recorded, binned */
+static int cavity_full_bin(shim_state *st, system_t *system) {
+    const int nm = list_to_array(st, system);
+    int natoms = 0;
+    for (int k = 0; k < nm; k++) natoms += natoms_of(st->mols[k]);
+    if (nm < 0 || cavity_reserve(st, nm, natoms)) {
+        error("ENERGY: HIP engine: out of host memory\n");
+        return cavity_failed(st, NULL);
+    }
+    wrapall(system->molecules, system->pbc);
+    int at = 0;
+    for (int k = 0; k < nm; k++) {
+        cavity_record(&st->cav[k], st->mols[k], at, st->cav_raw, st->cav_wrapped);
+        at += st->cav[k].natoms;
+    }
+    st->ncav = nm;
+    st->cav_atoms = at;
+    double *x = malloc(3 * (size_t)(at > 0 ? at : 1) * sizeof(double));
+    if (!x) {
+        error("ENERGY: HIP engine: out of host memory\n");
+        return cavity_failed(st, NULL);
+    }
+    double *y = x + at, *z = x + 2 * (size_t)at;
+    for (int k = 0; k < at; k++) {
+        x[k] = st->cav_wrapped[3 * k]; y[k] = st->cav_wrapped[3 * k + 1]; z[k] = st->cav_wrapped[3 * k + 2];
+    }
+    const int rc = mpmc_hip_cavity_bin(st->ctx, at, x, y, z);
+    free(x);
+    if (rc) return cavity_failed(st, "cavity_bin");
+    st->cav_valid = 1;
+    return 0;
+}
+
+/* cavity_update_grid() (cavity.c:112-179) for the accepted configuration the lists hold: system->cavities_open,
+ * system->cavity_volume and nodestats->cavity_bias_probability.  The darts of cavity_volume() are drawn here with the
+ * tree's get_rand(), three per dart, whether or not anything is open, and their positions formed as cavity.c:52-61 does.
+ * Before the first energy_hip() there is no device context: the call then takes its draws and nothing else -- mc() makes
+ * it once in front of the first energy() (mc.c:245), and nothing reads that call's results.  Returns 0, or -1 after a
+ * device / ABI failure, which the next energy_hip() reports in its own channel. */
+int energy_hip_cavity_update(system_t *system) {
+    shim_state *st = state_of(system, 1);
+    const int num_darts = (int)(system->pbc->volume * 0.1); /* DARTSCALE, defines.h:67 */
+    const int P = system->cavity_grid_size * system->cavity_grid_size * system->cavity_grid_size;
+    if (!st) {
+        error("ENERGY: HIP engine: out of host memory\n");
+        return -1;
+    }
+    if (num_darts > st->cav_darts_cap) {
+        double *d = realloc(st->cav_darts, 3 * (size_t)num_darts * sizeof(double));
+        if (!d) {
+            error("ENERGY: HIP engine: out of host memory\n");
+            return cavity_failed(st, NULL);
+        }
+        st->cav_darts = d;
+        st->cav_darts_cap = num_darts;
+    }
+    for (int throw = 0; throw < num_darts; throw++) {
+        double grid_vec[3];
+        for (int p = 0; p < 3; p++) grid_vec[p] = -0.5 + get_rand(system);
+        for (int p = 0; p < 3; p++) {
+            double v = system->pbc->basis[0][p] * grid_vec[0];
+            v = v + system->pbc->basis[1][p] * grid_vec[1];
+            v = v + system->pbc->basis[2][p] * grid_vec[2];
+            st->cav_darts[3 * throw + p] = v;
+        }
+    }
+    st->cav_ndarts = num_darts > 0 ? num_darts : 0;
+    st->cav_hits = 0;
+    system->cavities_open = 0;
+    system->cavity_volume = 0;
+    system->nodestats->cavity_bias_probability = 0;
+    if (!st->ctx) return 0; /* the call in front of the first energy(): the draws only */
+    if (st->cav_ctx != st->ctx || st->cav_grid != system->cavity_grid_size || st->cav_radius != system->cavity_radius) {
+        if (mpmc_hip_set_cavity_grid(st->ctx, system->cavity_grid_size, system->cavity_radius))
+            return cavity_failed(st, "set_cavity_grid");
+        st->cav_ctx = st->ctx;
+        st->cav_grid = system->cavity_grid_size;
+        st->cav_radius = system->cavity_radius;
+        st->cav_valid = 0;
+    }
+    double out_xyz[3 * 16], in_xyz[3 * 16];
+    int n_out = 0, n_in = 0, open = 0, hits = 0, rc = 1;
+    if (st->cav_valid) rc = cavity_diff(st, system, out_xyz, &n_out, in_xyz, &n_in);
+    if (rc == 0) {
+        rc = mpmc_hip_cavity_update(st->ctx, n_out, out_xyz, n_in, in_xyz, st->cav_ndarts, st->cav_darts, &open, &hits);
+        if (rc < 0) return cavity_failed(st, "cavity_update");
+    }
+    if (rc > 0) { /* no difference to state, or the engine wants the whole occupancy again (a new box, A/B option) */
+        if (cavity_full_bin(st, system)) return -1;
+        if (mpmc_hip_cavity_update(st->ctx, 0, NULL, 0, NULL, st->cav_ndarts, st->cav_darts, &open, &hits))
+            return cavity_failed(st, "cavity_update");
+    }
+    st->cav_hits = hits;
+    system->cavities_open = open;
+    system->nodestats->cavity_bias_probability = ((double)open) / ((double)P); /* cavity.c:103 */
+    const double fraction_hits = ((double)hits) / ((double)num_darts);          /* cavity.c:68-69 */
+    system->cavity_volume = fraction_hits * system->pbc->volume;
+    return 0;
+}
+
+/* make_move()'s scan of cavity_grid (mc_moves.c:590-606): the position of the index-th open point of the last
+ * energy_hip_cavity_update(), in (i, j, k) order */
+int energy_hip_cavity_point(system_t *system, int index, double com[3]) {
+    shim_state *st = state_of(system, 0);
+    int grid_index = -1;
+    com[0] = com[1] = com[2] = 0;
+    if (!st || !st->ctx) return cavity_failed(st, NULL);
+    if (mpmc_hip_cavity_point(st->ctx, index, &grid_index, com)) return cavity_failed(st, "cavity_point");
+    return 0;
+}
+
+/* the last energy_hip_cavity_update()'s darts ([n][3], owned by the binding) and how many of them hit; returns n */
+int energy_hip_cavity_darts(system_t *system, const double **darts, int *hits) {
+    shim_state *st = state_of(system, 0);
+    if (darts) *darts = st ? st->cav_darts : NULL;
+    if (hits) *hits = st ? st->cav_hits : 0;
+    return st ? st->cav_ndarts : 0;
+}
+
 /* First half of energy(): bring the device in line with the lists and enqueue the evaluation. */
 int energy_hip_begin(system_t *system) {
     const double t0 = now_s();
@@ -706,6 +989,10 @@ int energy_hip_begin(system_t *system) {
         return -1;
     }
     st->failed = 0;
+    if (st->cav_failed) { /* the failure of a cavity grid call is reported here, in energy()'s own channel */
+        error("ENERGY: HIP engine: the cavity grid failed on the device\n");
+        return device_failed(st);
+    }
     const char *why = unsupported(system);
     if (why) {
         char buf[2 * MAXLINE];
@@ -758,6 +1045,7 @@ int energy_hip_begin(system_t *system) {
         if (st->ctx && system->natoms > st->capacity) { /* uvt grew past the context */
             mpmc_hip_destroy(st->ctx);
             st->ctx = NULL;
+            st->cav_ctx = NULL; /* the cavity grid went with it */
         }
         if (!st->ctx) {
             /* head-room for insertions: a context is sized once, like the reference's pair-list growth steps */
@@ -845,6 +1133,7 @@ double energy_hip_end(system_t *system) {
             if (o->N > 0.0) o->spin_ratio /= o->N;     /* energy.c:211 */
             o->NU = o->N * o->energy;                  /* energy.c:220 */
             system->last_volume = system->pbc->volume; /* energy.c:223 */
+            st->last_energy = o->energy;
             return o->energy;
         }
     }
@@ -870,6 +1159,7 @@ double energy_hip_end(system_t *system) {
     if (o->N > 0.0) o->spin_ratio /= o->N;           /* energy.c:214 */
     o->NU = o->N * o->energy;                        /* energy.c:219 */
     system->last_volume = system->pbc->volume;       /* energy.c:222 */
+    st->last_energy = o->energy;
     return o->energy;
 }
 

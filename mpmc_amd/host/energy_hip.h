@@ -66,12 +66,27 @@ int energy_hip_corrtime(system_t *system);
  * returns 0.  Non-zero: no context, or the engine refused (its message goes to error()). */
 int energy_hip_polarizability_tensor(system_t *system, double tensor[9], int print);
 
+/* cavity_bias: cavity_update_grid() (src/mc/cavity.c:112-179) on the device, for the accepted configuration the lists hold
+ * at the top of make_move().  Draws the 3 * (int)(0.1 V) numbers of cavity_volume()'s darts with get_rand() in the
+ * reference's order, wraps only the molecules that changed since its last call (their wrapped_pos is wrapall()'s), sends
+ * the difference to the engine's grid (mpmc_hip_cavity_update) or bins everything again when the engine asks for it, and
+ * fills system->cavities_open, system->cavity_volume and nodestats->cavity_bias_probability.  Before the first
+ * energy_hip() (mc.c:245) it takes the draws only.  A device / ABI failure is reported by the next energy_hip() through
+ * energy_hip_failed(): it never becomes a rejected move. */
+int energy_hip_cavity_update(system_t *system);
+/* the position of the index-th open grid point of that call in (i, j, k) order: what make_move()'s scan of cavity_grid
+ * (mc_moves.c:590-606) gives the biased insertion as centre of mass */
+int energy_hip_cavity_point(system_t *system, int index, double com[3]);
+/* that call's dart positions ([n][3], owned by the binding) and hit count; returns n (tests, tools) */
+int energy_hip_cavity_darts(system_t *system, const double **darts, int *hits);
+
 /* cleanup() (src/main/cleanup.c): destroys the device context and the side table entry */
 void energy_hip_cleanup(system_t *system);
 
 /* plumbing */
 void energy_hip_set_device(system_t *system, int device); /* default: rank % device count (mirror: 0) */
 mpmc_hip_ctx *energy_hip_context(system_t *system);       /* NULL before the first energy_hip() */
+double energy_hip_last_energy(system_t *system);          /* the last energy_hip()'s return value (a rejected trial's too) */
 void energy_hip_enable_timing(system_t *system, int on);
 void energy_hip_get_timings(system_t *system, mpmc_hip_timings *out);
 void energy_hip_profile_report(void);

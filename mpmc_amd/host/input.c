@@ -70,6 +70,7 @@ static system_t *alloc_system(void) {
     system->pbc = calloc(1, sizeof(pbc_t));
     system->observables = calloc(1, sizeof(observables_t));
     system->nodestats = calloc(1, sizeof(nodestats_t));
+    system->avg_nodestats = calloc(1, sizeof(avg_nodestats_t));
     system->avg_observables = calloc(1, sizeof(avg_observables_t));
     system->checkpoint = calloc(1, sizeof(checkpoint_t));
     system->checkpoint->observables = calloc(1, sizeof(observables_t));
@@ -188,6 +189,9 @@ int do_command(system_t *system, char **token) {
     FLAG("cdvdw_sig_repulsion", cdvdw_sig_repulsion);
     FLAG("cavity_autoreject_absolute", cavity_autoreject_absolute); /* input.c:413-427 */
     REAL("cavity_autoreject_scale", cavity_autoreject_scale);
+    FLAG("cavity_bias", cavity_bias); /* input.c:397-412 */
+    INT("cavity_grid", cavity_grid_size);
+    REAL("cavity_radius", cavity_radius);
     INT("rd_crystal_order", rd_crystal_order);
     FLAG("read_pqr_box", read_pqr_box_on); /* input.c:1448-1455 */
     FLAG("calc_pressure", calc_pressure);  /* input.c:575-582; refused by name in replay (check_system) */
@@ -395,6 +399,30 @@ void pbc(system_t *system) {
     rb[2][2] = iv * (b[0][0] * b[1][1] - b[0][1] * b[1][0]);
 }
 
+/* cavity_bias (check_input.c:880-892), shared with host_apply_config().  Outside `ensemble uvt` the reference would only
+ * burn random numbers on the grid, and the device grid holds at most 64^3 points: both are refused by name. */
+int check_cavity_bias(system_t *system) {
+    char linebuf[MAXLINE];
+    if (!system->cavity_bias) return 0;
+    if ((system->cavity_grid_size <= 0) || (system->cavity_radius <= 0.0)) {
+        error("INPUT: invalid cavity grid or radius specified\n");
+        return -1;
+    }
+    if (system->ensemble != ENSEMBLE_UVT) {
+        error("INPUT: cavity_bias needs ensemble uvt (it biases insertions and removals only)\n");
+        return -1;
+    }
+    if (system->cavity_grid_size > 64) {
+        error("INPUT: cavity_grid above 64 is not on the device\n");
+        return -1;
+    }
+    output("INPUT: cavity-biased umbrella sampling activated\n");
+    snprintf(linebuf, MAXLINE, "INPUT: cavity grid size is %dx%dx%d points with a sphere radius of %.3f A\n",
+             system->cavity_grid_size, system->cavity_grid_size, system->cavity_grid_size, system->cavity_radius);
+    output(linebuf);
+    return 0;
+}
+
 /* the checks of reference src/io/check_input.c that concern this path */
 static int check_system(system_t *system) {
     char linebuf[MAXLINE];
@@ -435,6 +463,7 @@ static int check_system(system_t *system) {
             return -1;
         }
     }
+    if (check_cavity_bias(system)) return -1;
     if (system->ensemble == ENSEMBLE_NPT && !(system->pressure > 0.0)) { /* check_input.c:673-678 */
         error("INPUT: invalid pressure set for NPT\n");
         return -1;
@@ -588,6 +617,7 @@ void free_system(system_t *system) {
     free(system->pbc);
     free(system->observables);
     free(system->nodestats);
+    free(system->avg_nodestats);
     free(system->avg_observables);
     if (system->checkpoint) {
         if (system->checkpoint->molecule_backup) free_molecule(system, system->checkpoint->molecule_backup);

@@ -307,6 +307,11 @@ void checkpoint(system_t *system) {
 /* apply what checkpoint() decided (reference make_move(), src/mc/mc_moves.c:567-741) */
 void make_move(system_t *system) {
     checkpoint_t *cp = system->checkpoint;
+    /* update the cavity grid prior to making a move (mc_moves.c:577-580): on the device, for the accepted configuration */
+    if (system->cavity_bias) {
+        energy_hip_cavity_update(system); /* (a device failure stops the chain at the next energy()) */
+        cp->biased_move = 0;
+    }
     if (cp->movetype == MOVETYPE_VOLUME) { /* (needs no picked molecule) */
         volume_change(system);
         return;
@@ -316,10 +321,20 @@ void make_move(system_t *system) {
         case MOVETYPE_INSERT: {
             /* insert a copy of the picked molecule at a random position and orientation */
             double rand[3], com[3];
-            for (int p = 0; p < 3; p++) rand[p] = 0.5 - get_rand(system);
-            for (int p = 0; p < 3; p++) {
-                com[p] = 0;
-                for (int q = 0; q < 3; q++) com[p] += system->pbc->basis[q][p] * rand[q];
+            if (system->cavity_bias && system->cavities_open) { /* umbrella sampling, mc_moves.c:585-608 */
+                /* doing a biased move - this flag lets boltzmann_factor() know about it */
+                cp->biased_move = 1;
+                /* insert randomly at one of the free cavity points: the reference lists them in (i, j, k) order, the
+                 * device keeps that list */
+                const int random_index =
+                    (system->cavities_open - 1) - (int)rint(((double)(system->cavities_open - 1)) * get_rand(system));
+                energy_hip_cavity_point(system, random_index, com);
+            } else {
+                for (int p = 0; p < 3; p++) rand[p] = 0.5 - get_rand(system);
+                for (int p = 0; p < 3; p++) {
+                    com[p] = 0;
+                    for (int q = 0; q < 3; q++) com[p] += system->pbc->basis[q][p] * rand[q];
+                }
             }
             energy_hip_note_list_changed(system);
             system->movable_valid = 0;
@@ -340,6 +355,13 @@ void make_move(system_t *system) {
             break;
         }
         case MOVETYPE_REMOVE:
+            if (system->cavity_bias) { /* mc_moves.c:675-681 */
+                if (get_rand(system) < pow((1.0 - system->avg_observables->cavity_bias_probability),
+                                           ((double)system->cavity_grid_size * system->cavity_grid_size * system->cavity_grid_size)))
+                    cp->biased_move = 0;
+                else
+                    cp->biased_move = 1;
+            }
             energy_hip_note_list_changed(system);
             system->movable_valid = 0;
             /* remove 'altered' from the list */
@@ -411,13 +433,23 @@ void restore(system_t *system) {
     checkpoint(system);
 }
 
-/* reference boltzmann_factor(), src/mc/mc.c:37-135: NVT, and UVT without cavity bias (one sorbate type) */
+/* reference boltzmann_factor(), src/mc/mc.c:37-135: NVT, NPT, and UVT with and without cavity bias (one sorbate type) */
 void boltzmann_factor(system_t *system, double initial_energy, double final_energy) {
     const double delta_energy = final_energy - initial_energy;
     double bf = exp(-delta_energy / system->temperature);
     if (system->ensemble == ENSEMBLE_UVT) {
         const double fugacity = system->fugacity;
-        if (system->checkpoint->movetype == MOVETYPE_INSERT)
+        /* if biased_move is not set no cavity was available: the normal evaluation below (mc.c:53-77) */
+        if (system->cavity_bias && system->checkpoint->biased_move) {
+            if (system->checkpoint->movetype == MOVETYPE_INSERT)
+                bf = (system->cavity_volume * system->avg_nodestats->cavity_bias_probability * fugacity * ATM2REDUCED /
+                      (system->temperature * system->observables->N)) *
+                     exp(-delta_energy / system->temperature);
+            else if (system->checkpoint->movetype == MOVETYPE_REMOVE)
+                bf = (system->temperature * (system->observables->N + 1.0)) /
+                     (system->cavity_volume * system->avg_nodestats->cavity_bias_probability * fugacity * ATM2REDUCED) *
+                     exp(-delta_energy / system->temperature);
+        } else if (system->checkpoint->movetype == MOVETYPE_INSERT)
             bf = system->pbc->volume * fugacity * ATM2REDUCED / (system->temperature * (double)(system->observables->N)) *
                  exp(-delta_energy / system->temperature);
         else if (system->checkpoint->movetype == MOVETYPE_REMOVE)
@@ -445,7 +477,37 @@ void write_observables(FILE *fp, system_t *system, observables_t *o, double core
 typedef struct {
     observables_t observables;
     double polarization_iterations;
+    avg_nodestats_t avg_nodestats;
 } walker_record_t;
+
+/* each walker's running means over its steps (reference update_nodestats(), src/io/average.c:55-80; the reference's
+ * function-static counter is avg_nodestats->steps here, one per walker) */
+void update_nodestats(nodestats_t *nodestats, avg_nodestats_t *avg_nodestats) {
+    const int counter = ++avg_nodestats->steps;
+    const double factor = ((double)(counter - 1)) / ((double)(counter));
+    avg_nodestats->cavity_bias_probability =
+        factor * avg_nodestats->cavity_bias_probability + nodestats->cavity_bias_probability / ((double)counter);
+    avg_nodestats->cavity_bias_probability_sq =
+        factor * avg_nodestats->cavity_bias_probability_sq +
+        nodestats->cavity_bias_probability * nodestats->cavity_bias_probability / ((double)counter);
+}
+
+/* at every corrtime, in front of the loop over the walkers (average.c:351-376) */
+void clear_avg_nodestats(system_t *system) {
+    system->avg_nodestats->counter = 0;
+    system->avg_observables->cavity_bias_probability = 0;
+    system->avg_observables->cavity_bias_probability_sq = 0;
+}
+
+/* ... and once per walker inside it (average.c:378-400): the mean over the walkers of their running means */
+void update_root_nodestats(system_t *system, avg_nodestats_t *avg_nodestats, avg_observables_t *avg_observables) {
+    const double m = (double)(++system->avg_nodestats->counter);
+    const double factor = (m - 1.0) / m;
+    avg_observables->cavity_bias_probability =
+        factor * avg_observables->cavity_bias_probability + avg_nodestats->cavity_bias_probability / m;
+    avg_observables->cavity_bias_probability_sq =
+        factor * avg_observables->cavity_bias_probability_sq + avg_nodestats->cavity_bias_probability_sq / m;
+}
 
 static void update_averages(system_t *system, const observables_t *o, double polarization_iterations) {
     avg_observables_t *a = system->avg_observables;
@@ -465,6 +527,10 @@ int mc(system_t *system) {
     char linebuf[MAXLINE];
     system->observables->volume = system->pbc->volume;
     system->observables->temperature = 0;
+
+    /* update the grid for the first time (mc.c:245): there is no device context yet and nothing reads this call's
+     * results -- make_move() updates again before any use -- so it only takes the draws of its darts */
+    if (system->cavity_bias) energy_hip_cavity_update(system);
 
     /* get the initial energy of the system */
     system->step = 0;
@@ -536,6 +602,8 @@ int mc(system_t *system) {
         }
         system->nodestats->acceptance_rate =
             (double)system->nodestats->accept / (double)(system->nodestats->accept + system->nodestats->reject);
+        /* each node calculates its stats (mc.c:362) */
+        update_nodestats(system->nodestats, system->avg_nodestats);
 
         /* do this every correlation time */
         if (!(system->step % system->corrtime)) {
@@ -544,16 +612,20 @@ int mc(system_t *system) {
             memset(&snd, 0, sizeof(snd));
             snd.observables = *system->observables;
             snd.polarization_iterations = system->nodestats->polarization_iterations;
+            snd.avg_nodestats = *system->avg_nodestats;
             if (walkers_gather(system, &snd, (int)sizeof(snd), rcv) < 0) {
                 free(rcv);
                 return -1;
             }
-            if (!rank)
+            if (!rank) {
+                clear_avg_nodestats(system); /* mc.c:438: avoid double-counting */
                 for (int j = 0; j < size; j++) {
                     if (system->fp_energy)
                         write_observables(system->fp_energy, system, &rcv[j].observables, system->temperature);
+                    update_root_nodestats(system, &rcv[j].avg_nodestats, system->avg_observables);
                     update_averages(system, &rcv[j].observables, rcv[j].polarization_iterations);
                 }
+            }
         }
     }
     free(rcv);

@@ -74,15 +74,25 @@ typedef struct _nodestats {
     int accept_volume, reject_volume; /* npt (mc.c:164-165, :189-190) */
     double boltzmann_factor, acceptance_rate, acceptance_rate_displace;
     double polarization_iterations;
+    double cavity_bias_probability; /* cavity_bias: open grid points / all grid points of this step (cavity.c:85-107) */
 } nodestats_t;
+
+/* per-walker running means over the steps (structs.h:142-150, average.c:55-80) */
+typedef struct _avg_nodestats {
+    int counter; /* walkers averaged in at this corrtime (average.c:355, :381) */
+    int steps;   /* steps averaged in: the function-static counter of the reference's update_nodestats(), here per walker */
+    double cavity_bias_probability, cavity_bias_probability_sq;
+} avg_nodestats_t;
 
 typedef struct _avg_observables {
     double energy, energy_sq, coulombic_energy, rd_energy, polarization_energy, polarization_iterations;
     double counter;
+    /* cavity_bias: mean over the walkers of their running means, redone at every corrtime (average.c:369-370, :398-399) */
+    double cavity_bias_probability, cavity_bias_probability_sq;
 } avg_observables_t;
 
 typedef struct _checkpoint {
-    int movetype;
+    int movetype, biased_move; /* biased_move: the move takes the cavity-biased acceptance (mc_moves.c:587, :675-681) */
     molecule_t *molecule_altered, *molecule_backup; /* as in the reference: the backup is a deep copy */
     molecule_t *head, *tail;                        /* neighbours of molecule_altered in the list */
     int altered_index;                              /* its rank among the movable molecules */
@@ -126,6 +136,10 @@ typedef struct _system {
      * the scale makes energy() return MAXVALUE; count_autorejects counts those calls */
     int cavity_autoreject_absolute, count_autorejects;
     double cavity_autoreject_scale;
+    /* cavity_bias (structs.h:402-406, cavity.c, mc_moves.c:577-608, :675-681, mc.c:54-77): insertions go to open points of
+     * a cavity_grid_size^3 grid; the grid itself lives on the device (energy_hip_cavity_update) */
+    int cavity_bias, cavity_grid_size, cavities_open;
+    double cavity_radius, cavity_volume;
     /* ensemble replay (replay.c): the trajectory, whether its REMARK BOX lines set the box, and calc_pressure, which is
      * read so that replay can refuse it by name */
     int read_pqr_box_on, calc_pressure;
@@ -137,6 +151,7 @@ typedef struct _system {
     molecule_t *molecules;
     observables_t *observables;
     nodestats_t *nodestats;
+    avg_nodestats_t *avg_nodestats;
     avg_observables_t *avg_observables;
     checkpoint_t *checkpoint;
     double last_volume;
@@ -155,6 +170,7 @@ system_t *read_config(char *input_file);
 int do_command(system_t *system, char **token);
 molecule_t *read_molecules(FILE *fp, system_t *system);
 void pbc(system_t *system);
+int check_cavity_bias(system_t *system); /* the cavity_bias block of check_system(): 0 = fine (or off), -1 = refused */
 /* build a system from flat arrays (what tests and bench.py use instead of a PQR file) */
 system_t *system_from_arrays(int n, const double *pos, const double *charge, const double *polarizability,
                              const double *epsilon, const double *sigma, const double *mass, const int *molecule,
@@ -179,6 +195,10 @@ void checkpoint(system_t *system);
 void restore(system_t *system);
 void make_move(system_t *system);
 void boltzmann_factor(system_t *system, double initial_energy, double final_energy);
+/* node statistics (reference src/io/average.c:55-80, :351-400; the cavity_bias members only) */
+void update_nodestats(nodestats_t *nodestats, avg_nodestats_t *avg_nodestats);
+void clear_avg_nodestats(system_t *system);
+void update_root_nodestats(system_t *system, avg_nodestats_t *avg_nodestats, avg_observables_t *avg_observables);
 double get_rand(system_t *system);
 void seed_rng(system_t *system, unsigned int seed);
 molecule_t *copy_molecule(system_t *system, molecule_t *src);
