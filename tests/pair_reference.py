@@ -297,13 +297,7 @@ def ewald_field_recip(system, params):
     vol, rb, rc = pbc(system["basis"], params.get("pbc_cutoff", 0.0))
     ea = params["polar_ewald_alpha"] if params.get("polar_ewald_alpha_set") else 3.5 / rc
     kmax = int(params.get("ewald_kmax", 7))
-    ks = []
-    for l0 in range(0, kmax + 1):
-        for l1 in range(0 if l0 == 0 else -kmax, kmax + 1):
-            for l2 in range(1 if (l0 == 0 and l1 == 0) else -kmax, kmax + 1):
-                if l0 * l0 + l1 * l1 + l2 * l2 <= kmax * kmax:
-                    ks.append((l0, l1, l2))
-    kv = 2.0 * math.pi * (np.asarray(ks, dtype=np.float64) @ rb.T)  # k_p = 2 pi sum_q recip[p][q] l_q
+    kv = 2.0 * math.pi * (kvector_list(kmax).astype(np.float64) @ rb.T)  # k_p = 2 pi sum_q recip[p][q] l_q
     ef = np.zeros((len(pos), 3), LD)
     for c0 in range(0, len(kv), 256):
         k = kv[c0:c0 + 256]
@@ -314,6 +308,89 @@ def ewald_field_recip(system, params):
         f1, f2 = (q[:, None] * co).sum(axis=0), (q[:, None] * si).sum(axis=0)
         ef += (si * f1 - co * f2) @ w
     return ef * (8 * PI / LD(vol))
+
+
+def kvector_list(kmax):
+    """the half sphere of coulombic.c:56-60 and polar_ewald.c:85-100, in loop order"""
+    ks = []
+    for l0 in range(0, kmax + 1):
+        for l1 in range(0 if l0 == 0 else -kmax, kmax + 1):
+            for l2 in range(1 if (l0 == 0 and l1 == 0) else -kmax, kmax + 1):
+                if l0 * l0 + l1 * l1 + l2 * l2 <= kmax * kmax:
+                    ks.append((l0, l1, l2))
+    return np.asarray(ks, dtype=np.int64).reshape(-1, 3)
+
+
+U64 = 2.0 ** -53
+C_PHASE = 8  # roundings between the inputs and a phase, see ewald_recip_energy()
+C_WEIGHT = 19  # roundings between k, S(k) and a term of the k sum, see ewald_recip_energy()
+
+
+def ewald_recip_energy(system, params):
+    """coulombic_reciprocal(), coulombic.c:42-95: U = (4 pi / V) sum_k exp(-k^2 / 4 a^2) / k^2 |S(k)|^2 over the half
+    sphere, S(k) = sum q_a e^{i k.x_a} over the atoms that are not frozen and carry a charge.  Returns (U, dU): the value
+    in longdouble and the bound of an fp64 evaluation's distance from it.
+
+    The phases are fp64 as the reference forms them (k_p = sum_q 2 pi recip[p][q] l_q accumulated in q, k.x accumulated in
+    p): they are arguments of cos / sin, so their rounding is part of the answer's definition only up to the bound below.
+    cos / sin of the fp64 phase, the products, S(k), the weights and the k sum are longdouble.
+
+    dS_k = sum_a |q_a| (C_PHASE u Phi_ak + 2u) + N u sum_a |q_a|,   Phi_ak = sum_p |k_p x_ap|
+    dU   = (4 pi / V) sum_k w_k (2 |S_k| dS_k + dS_k^2) + (C_WEIGHT + nk + max k^2/4a^2) u U
+    C_PHASE: k_p is three products of two factors and two additions (4, relative to sum_q |2 pi recip[p][q] l_q|), k.x a
+    product and two additions (3), one to spare for another association (2 pi (recip l)): 8.  2u: cos / sin to 1 ulp
+    (at most u absolute) and the product with q.  N u: the sum of N terms in any order.  C_WEIGHT: k^2 (3), 4 a^2 (2), the
+    quotient (1), exp (1 ulp = 2u, and u of its argument), / k^2 (1 + 3), |S|^2 (3), the product (1), 4 pi / V (3): 19;
+    nk u for the k sum."""
+    pos = np.ascontiguousarray(system["pos"], dtype=np.float64)
+    q = np.asarray(system["charge"], dtype=np.float64)
+    frozen = np.asarray(system["frozen"]).astype(bool)
+    vol, rb, rc = pbc(system["basis"], params.get("pbc_cutoff", 0.0))
+    ea = params["ewald_alpha"] if params.get("ewald_alpha_set") else 3.5 / rc
+    ls = kvector_list(int(params.get("ewald_kmax", 7))).astype(np.float64)
+    sel = ~frozen & (q != 0.0)
+    x, qs = pos[sel], q[sel]
+    N = len(qs)
+    kv = np.zeros((len(ls), 3))
+    kabs = np.zeros((len(ls), 3))
+    for p in range(3):
+        for c in range(3):
+            t = 2.0 * math.pi * rb[p][c] * ls[:, c]
+            kv[:, p] = kv[:, p] + t
+            kabs[:, p] = kabs[:, p] + np.abs(t)
+    total, dtotal, argmax = LD(0), LD(0), 0.0
+    qa = np.abs(qs).astype(LD)
+    for c0 in range(0, len(kv), 256):
+        k = kv[c0:c0 + 256]
+        ph = x[:, 0:1] * k[None, :, 0]
+        ph = ph + x[:, 1:2] * k[None, :, 1]
+        ph = ph + x[:, 2:3] * k[None, :, 2]
+        phl = ph.astype(LD)
+        re = (qs.astype(LD)[:, None] * np.cos(phl)).sum(axis=0)
+        im = (qs.astype(LD)[:, None] * np.sin(phl)).sum(axis=0)
+        Phi = np.abs(x).astype(LD) @ kabs[c0:c0 + 256].T.astype(LD)
+        dS = (qa[:, None] * (C_PHASE * U64 * Phi + 2 * U64)).sum(axis=0) + N * U64 * qa.sum()
+        k2 = (k.astype(LD) ** 2).sum(axis=1)
+        arg = k2 / (4 * LD(ea) * LD(ea))
+        argmax = max(argmax, float(arg.max()))
+        w = np.exp(-arg) / k2
+        S = np.sqrt(re * re + im * im)
+        total += (w * (re * re + im * im)).sum()
+        dtotal += (w * (2 * S * dS + dS * dS)).sum()
+    f = 4 * PI / LD(vol)
+    U = f * total
+    return U, float(f * dtotal + (C_WEIGHT + len(kv) + argmax) * U64 * abs(U))
+
+
+def ewald_self_energy(system, params):
+    """coulombic_self(), coulombic.c:97-112: -sum alpha q^2 / sqrt(pi) over the atoms that are not frozen (pi is the
+    reference's fp64 M_PI).  Returns (U_self in longdouble, the number of terms)."""
+    q = np.asarray(system["charge"], dtype=np.float64)
+    frozen = np.asarray(system["frozen"]).astype(bool)
+    _, _, rc = pbc(system["basis"], params.get("pbc_cutoff", 0.0))
+    ea = params["ewald_alpha"] if params.get("ewald_alpha_set") else 3.5 / rc
+    qs = q[~frozen].astype(LD)
+    return -(LD(ea) * qs * qs / np.sqrt(PI)).sum(), int(len(qs))
 
 
 def sums(table, system, params):
