@@ -469,7 +469,9 @@ int mpmc_hip_download_dipoles(mpmc_hip_ctx *ctx, double *mu, double *ef_static, 
 /* system->A_matrix of the last energy(): [3n][3n] row-major (thole_matrix.c:38-146). */
 int mpmc_hip_download_amatrix(mpmc_hip_ctx *ctx, double *A);
 
-/* atom->rank_metric [n] and the final sweep order [n] (polar_gs_ranked). */
+/* atom->rank_metric [n] and the final sweep order [n] (polar_gs_ranked), both over mpmc_hip_slot_count() slots.  After
+ * insert / remove the order is the stable sort of the order stated by mpmc_hip_set_sweep_order(): the polarizable
+ * sites appear in it in the order they were swept in (sites without polarizability and holes keep their slot's place). */
 int mpmc_hip_download_ranking(mpmc_hip_ctx *ctx, double *rank_metric, int *ranked_array);
 
 int mpmc_hip_get_timings(mpmc_hip_ctx *ctx, mpmc_hip_timings *t);

@@ -3223,6 +3223,15 @@ extern "C" int mpmc_hip_download_ranking(mpmc_hip_ctx *c, double *rank_metric, i
         // the identity by the metric -- made here, on demand, from the metric the last ranked call was sorted from
         std::vector<int> perm(c->n);
         std::iota(perm.begin(), perm.end(), 0);
+        // ... of the order the sweeps started from: after insert / remove that is the order the caller stated
+        // (mpmc_hip_set_sweep_order), not the slot order.  The polarizable sites take, in the stated order, the places the
+        // polarizable sites have in slot order (the identity while the view is the upload's).
+        const SweepView &v0 = c->view[0];
+        if (gs_order_mode(c) && !c->order_stale && (int)v0.slot_of_atom.size() == c->n) {
+            size_t k = 0;
+            for (int a = 0; a < c->n && k < v0.h_idx.size(); ++a)
+                if (v0.slot_of_atom[a] >= 0) perm[a] = v0.h_idx[k++];
+        }
         if (c->perm_ranked && (int)c->rank_saved.size() == c->n) {
             const double *rk = c->rank_saved.data();
             std::stable_sort(perm.begin(), perm.end(), [rk](int x, int y) { return rk[x] > rk[y]; });
