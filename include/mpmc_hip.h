@@ -302,6 +302,60 @@ int mpmc_hip_get_three_body_energy(mpmc_hip_ctx *ctx, double *out);
  * tiles of the moved atoms' blocks are summed again, with the bits of a from-scratch evaluation. */
 int mpmc_hip_set_rd_crystal(mpmc_hip_ctx *ctx, int order);
 
+/* The pair potentials of the reference's energy() beside plain Lennard-Jones (src/energy/energy.c:132-145), and the
+ * Lennard-Jones mixing rules of pairs.c:84-211.  With r the minimum-image distance and sigma_ij, eps_ij the mixed values,
+ * rd_energy becomes a dense sum over the unordered pairs that are not frozen-frozen of
+ *   MPMC_HIP_RD_SG             Silvera-Goldman (sg.c:13-91): every pair with r < cutoff, same-molecule pairs included; the
+ *                              per-atom eps / sigma are not read.  x = r / 0.529177249,
+ *                              U = exp(1.713 - 1.5671 x - 0.00993 x^2) - (12.14/x^6 + 215.2/x^8 + 4813.9/x^10 - 143.1/x^9) f,
+ *                              f = exp(-(8.321/x - 1)^2) for x < 8.321, else 1; under feynman_hibbs the second-order term
+ *                              of sg.c:56-72 as written there (whatever feynman_hibbs_order says; mass of the molecule of
+ *                              the pair's first atom); times 3.15774655e5.  In this form energy() computes what it computes
+ *                              under rd_only: coulombic_energy = polarization_energy = 0 (energy.c:108, :154).
+ *                              OWNED DEVIATION: the reference sums uninitialised distances for frozen-frozen pairs here.
+ *   MPMC_HIP_RD_DREIDING       exp-6, gamma = 12 (dreiding.c:13-108): pairs with !(r > cutoff) that are not rd-excluded;
+ *                              eps_ij (t - 2 (r / sigma_ij)^-6), t = 0 for an attractive-only pair, 1e40 for
+ *                              r < 0.4 sigma_ij, else exp(12 (1 - r / sigma_ij)).  1e40 is finite: it is passed through.
+ *   MPMC_HIP_RD_BUFFERED_14_7  Halgren's buffered 14-7 (lj_buffered_14_7.c:6-35): the same pairs;
+ *                              eps_ij (1.07 / (rho + 0.07))^7 (1.12 / (rho^7 + 0.12) - 2), rho = r / sigma_ij.
+ *   MPMC_HIP_RD_LJ             Lennard-Jones as lj.c:165-276 has it without rd_crystal -- r - 1e-12 < cutoff, attractive-only
+ *                              pairs, lj_fh_corr at order 2 or 4, under rd_lrc the pair correction with the MIXED values
+ *                              and the self correction with the atom's own -- so that the mixing rules reach it.  With
+ *                              MPMC_HIP_RD_MIX_LB it restates the standard path (dense, without its screen).
+ * rd-excluded is the standard path's rule: same molecule, or one of the four per-atom eps / sigma is 0.  DREIDING and the
+ * buffered 14-7 have no Feynman-Hibbs term and no long-range correction, as in the reference.
+ * mixing, evaluated per pair on the device from the upload's per-atom eps / sigma:
+ *   MPMC_HIP_RD_MIX_LB              Lorentz-Berthelot, |sigma| and attractive-only for a negative sigma (pairs.c:200-211)
+ *   MPMC_HIP_RD_MIX_WALDMAN_HAGLER  sigma_ij = ((s_i^6 + s_j^6) / 2)^(1/6), eps_ij = sqrt(e_i e_j) 2 s_i^3 s_j^3 / (s_i^6 + s_j^6)
+ *   MPMC_HIP_RD_MIX_HALGREN         sigma_ij = (s_i^3 + s_j^3) / (s_i^2 + s_j^2), eps_ij = 4 e_i e_j / (sqrt e_i + sqrt e_j)^2,
+ *                                   each 0 unless both values are > 0
+ *   MPMC_HIP_RD_MIX_C6              sigma_ij = (s_i + s_j) / 2, eps_ij = 64 sqrt(e_i e_j) s_i^3 s_j^3 / (s_i + s_j)^6
+ * form = 0 returns to the standard path, whose results keep their bits.  A setting of the context like
+ * mpmc_hip_set_rd_crystal(): it carries no per-atom data and persists across uploads; not allowed between energy_begin()
+ * and energy_end().  While a form is on, insert_molecule / remove_molecule answer 1 (upload the whole configuration
+ * again); update_atoms, scale_box, energy_begin / _end, several contexts and axilrod_teller work as before, and after a
+ * move only the tiles of the moved atoms' blocks are summed again, with the bits of a from-scratch evaluation.  energy()
+ * refuses, by name: a form together with disp_expansion, rd_crystal or polarvdw; MPMC_HIP_RD_MIX_WALDMAN_HAGLER with a
+ * negative sigma in the upload (the reference never assigns such a pair's epsilon); MPMC_HIP_RD_SG with a mixing other than
+ * MPMC_HIP_RD_MIX_LB (the reference ignores the mixing there). */
+enum {
+    MPMC_HIP_RD_LJ = 1,
+    MPMC_HIP_RD_SG = 2,
+    MPMC_HIP_RD_DREIDING = 3,
+    MPMC_HIP_RD_BUFFERED_14_7 = 4
+};
+enum {
+    MPMC_HIP_RD_MIX_LB = 0,
+    MPMC_HIP_RD_MIX_WALDMAN_HAGLER = 1,
+    MPMC_HIP_RD_MIX_HALGREN = 2,
+    MPMC_HIP_RD_MIX_C6 = 3
+};
+typedef struct mpmc_hip_rd_form_params {
+    int form;   /* 0 = the standard path, or MPMC_HIP_RD_* */
+    int mixing; /* MPMC_HIP_RD_MIX_* */
+} mpmc_hip_rd_form_params;
+int mpmc_hip_set_rd_form(mpmc_hip_ctx *ctx, const mpmc_hip_rd_form_params *p);
+
 /* polarvdw (alias cdvdw), the coupled-dipole many-body van der Waals term (reference src/energy/vdw.c:579-632; added to
  * potential_energy at energy.c:194 and reported as observables->vdw_energy; not computed under rd_only):
  *     vdw_energy = e_total - e_iso + lr_corr.

@@ -38,6 +38,7 @@
 #include "device_common.h"
 #include "kernels_pair.h"
 #include "kernels_disp.h"
+#include "kernels_rdforms.h"
 #include "kernels_at.h"
 #include "kernels_crystal.h"
 #include "kernels_vdw.h"
@@ -449,6 +450,14 @@ struct mpmc_hip_ctx {
     TileSum rdc_static;             // [ntile*ntile] the long-range correction at cutoff_c, R_DISP_LRC; valid covers the self
                                     // part (R_RDC_SELF) too: both are those of the current parameters, box and rd_lrc
     int rdc_static_lrc = -1;        // the rd_lrc they were made under
+    // ---- the other pair potentials (mpmc_hip_set_rd_form): Silvera-Goldman, DREIDING, buffered 14-7, and Lennard-Jones
+    // under any mixing rule, kernels_rdforms.h.  A context setting like rd_crystal.  The LJ kernels are handed d_zero.
+    int rd_form = 0;                // RdForm; 0 = the standard path
+    int rd_mix = 0;                 // RdMix
+    TileSum rdf;                    // [ntile*ntile] the dense pair sum, R_DISP
+    TileSum rdf_lrc;                // [ntile*ntile] the LJ form's long-range correction, R_DISP_LRC
+    bool negative_sigma = false;    // the upload holds a sigma < 0 (Waldman-Hagler leaves such a pair's epsilon unset)
+    mpmc_hip_params par_user;       // what set_params() brought; `par` is that with rd_only forced on under the SG form
     // ---- polarvdw (mpmc_hip_set_vdw): coupled-dipole many-body van der Waals + repulsion-only Lennard-Jones, kernels_vdw.h.
     // The LJ kernels are handed d_zero, as under disp_expansion.
     bool vdw_on = false;
@@ -592,8 +601,8 @@ static DevAtoms dev_atoms(const mpmc_hip_ctx *c) {
     a.z = c->d_z;
     a.q = c->d_q;
     a.alpha = c->d_alpha;
-    a.eps = (c->disp_on || c->rdc_order || c->vdw_on) ? c->d_zero : c->d_eps;
-    a.sig = (c->disp_on || c->rdc_order || c->vdw_on) ? c->d_zero : c->d_sig;
+    a.eps = (c->disp_on || c->rdc_order || c->vdw_on || c->rd_form) ? c->d_zero : c->d_eps;
+    a.sig = (c->disp_on || c->rdc_order || c->vdw_on || c->rd_form) ? c->d_zero : c->d_sig;
     a.molmass = c->d_molmass;
     a.mol = c->d_mol;
     a.flags = c->d_flags;
@@ -990,17 +999,19 @@ extern "C" void mpmc_hip_destroy(mpmc_hip_ctx *c) {
 // all_dirty, or the moved blocks cannot be listed: every sum over positions (the static ones read no coordinate)
 static void positions_unknown(mpmc_hip_ctx *c) {
     c->pair_part_valid = c->field_part_valid = c->disp.valid = c->rdc.valid = c->at.valid = false;
-    c->rep.valid = c->vdw.valid = false;
+    c->rep.valid = c->vdw.valid = c->rdf.valid = false;
 }
 // set_params(), or insert_molecule() grew the tile grid.  Not c->at: no parameter enters the three-body term, and the grid
 // cannot grow in its mode (edits_supported()); a full triple pass after every set_params() would be wasted.
 static void params_or_grid_changed(mpmc_hip_ctx *c) {
     c->pair_part_valid = c->field_part_valid = c->disp.valid = c->rdc.valid = false;
     c->rep.valid = c->vdw.valid = false;  // (polar_damp enters the matrix)
+    c->rdf.valid = false;
 }
 // apply_box(): the sums of parameters, cutoff and volume (those over positions go with all_dirty)
 static void box_changed(mpmc_hip_ctx *c) {
     c->lrc.valid = c->disp_lrc.valid = c->rdc_static.valid = c->rep_lrc.valid = c->vdw_lrc.valid = false;
+    c->rdf_lrc.valid = false;
     c->cav_pos_valid = c->cav_occ_valid = false;  // the cavity grid's points are fractions of the cell
     c->cav_open = -1;
 }
@@ -1008,6 +1019,7 @@ static void box_changed(mpmc_hip_ctx *c) {
 static void atoms_replaced(mpmc_hip_ctx *c) {
     c->lrc.valid = c->disp.valid = c->disp_lrc.valid = c->at.valid = c->rdc.valid = c->rdc_static.valid = false;
     c->rep.valid = c->rep_lrc.valid = c->vdw.valid = c->vdw_lrc.valid = false;
+    c->rdf.valid = c->rdf_lrc.valid = false;
 }
 
 // reference src/io/check_input.c:318-470 (the subset that concerns this path)
@@ -1035,7 +1047,9 @@ extern "C" int mpmc_hip_set_params(mpmc_hip_ctx *c, const mpmc_hip_params *p) {
     if (p->polar_damp != c->par.polar_damp) c->all_dirty = true;
     params_or_grid_changed(c);
     ++c->config_rev;
+    c->par_user = *p;
     c->par = *p;
+    if (c->rd_form == kRdFormSG) c->par.rd_only = 1;  // energy.c:108, :154: no electrostatics, no polarization under sg
     c->have_params = true;
     c->kvecf_valid = false;
     c->kvec_valid = false;
@@ -1170,6 +1184,8 @@ extern "C" int mpmc_hip_upload(mpmc_hip_ctx *c, int n, const double *x, const do
     c->at_on = false;  // ... and no three-body term until set_axilrod_teller() says otherwise
     c->chol_nv = 0;     // (the exact dipoles' factor was the old configuration's; the setting itself stays)
     c->vdw_on = false;  // ... and no coupled-dipole term until set_vdw() says otherwise (its e_iso cache stays for that call)
+    c->negative_sigma = false;
+    for (int i = 0; i < n; ++i) c->negative_sigma = c->negative_sigma || sigma[i] < 0.0;
     atoms_replaced(c);
     c->rank_saved.clear();
     c->perm_ranked = false;
@@ -1327,6 +1343,46 @@ extern "C" int mpmc_hip_set_rd_crystal(mpmc_hip_ctx *c, int order) {
     c->rdc.valid = c->rdc_static.valid = false;
     c->pair_part_valid = false;  // the Lennard-Jones kernels change between real and zero parameters
     c->lrc.valid = false;
+    c->all_dirty = true;
+    ++c->config_rev;
+    return 0;
+}
+
+// The pair potentials beside plain Lennard-Jones (kernels_rdforms.h): form 0 returns to the standard path.  A setting of
+// the context, like set_rd_crystal().  Under the SG form the context evaluates what it evaluates under rd_only.
+extern "C" int mpmc_hip_set_rd_form(mpmc_hip_ctx *c, const mpmc_hip_rd_form_params *p) {
+    if (!c || !p) return fail("MPMC_HIP: set_rd_form: null argument");
+    if (c->in_flight) return fail("MPMC_HIP: set_rd_form between energy_begin() and energy_end()");
+    if (p->form < 0 || p->form > MPMC_HIP_RD_BUFFERED_14_7)
+        return fail("MPMC_HIP: set_rd_form: form %d outside 0 .. %d", p->form, MPMC_HIP_RD_BUFFERED_14_7);
+    if (p->mixing < 0 || p->mixing > MPMC_HIP_RD_MIX_C6)
+        return fail("MPMC_HIP: set_rd_form: mixing %d outside 0 .. %d", p->mixing, MPMC_HIP_RD_MIX_C6);
+    const int mix = p->form ? p->mixing : 0;
+    if (p->form == c->rd_form && mix == c->rd_mix) return 0;  // nothing to change: no partial sum is thrown away
+    HIPCHK(hipSetDevice(c->device));
+    if (complete_pending_sweep(c)) return -1;
+    if (c->have_atoms && flush_moves(c)) return -1;  // keep the order of the caller's operations
+    if (p->form) {
+        const size_t ntile = c->max_npad / 64;
+        if (alloc_zero_params(c)) return -1;
+        if (!c->rdf.part) {
+            HIPCHK(c->rdf.part.alloc(ntile * ntile));
+            HIPCHK(c->rdf_lrc.part.alloc(ntile * ntile));
+        }
+    }
+    const bool rd_only_changes = (p->form == kRdFormSG) != (c->rd_form == kRdFormSG);
+    c->rd_form = p->form;
+    c->rd_mix = mix;
+    c->rdf.valid = c->rdf_lrc.valid = false;
+    c->pair_part_valid = false;  // the Lennard-Jones kernels change between real and zero parameters
+    c->lrc.valid = false;
+    if (rd_only_changes && c->have_params) {  // as a set_params() that changes rd_only
+        c->par = c->par_user;
+        if (c->rd_form == kRdFormSG) c->par.rd_only = 1;
+        params_or_grid_changed(c);
+        c->kvecf_valid = false;
+        c->kvec_valid = false;
+    }
     c->all_dirty = true;
     ++c->config_rev;
     return 0;
@@ -1703,6 +1759,7 @@ static bool edits_supported(const mpmc_hip_ctx *c) {
     if (c->disp_on) return false;  // disp_expansion: no device-side insert / remove (the caller uploads again)
     if (c->at_on) return false;    // axilrod_teller: the same
     if (c->rdc_order) return false;  // rd_crystal: the same
+    if (c->rd_form) return false;    // set_rd_form: the same
     if (c->vdw_on) return false;     // polarvdw: the same
     if (c->exact_polar) return false;  // exact dipoles: the expanded matrix is not patched by edits (as on its Gauss-Seidel path)
     // Gauss-Seidel: only with the chain kernel, whose view is rebuilt from the order the caller states afterwards
@@ -2451,6 +2508,47 @@ static int launch_rdc(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipS
     });
 }
 
+// set_rd_form: the dense pair sum of the form, and under rd_lrc the LJ form's long-range correction when the parameters,
+// the mixing, the cutoff or the volume changed.  `a` carries zero epsilon / sigma in this mode: these kernels get the real
+// ones.
+static int launch_rdform(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipStream_t sb) {
+    const int ntile = c->npad / 64;
+    DevAtoms lj = a;
+    lj.eps = c->d_eps;
+    lj.sig = c->d_sig;
+    RdFormParams fp;
+    fp.mixing = c->rd_mix;
+    fp.fh = c->par.feynman_hibbs ? 1 : 0;
+    fp.fh_order = c->par.feynman_hibbs_order;
+    fp.temperature = c->par.temperature;
+    if (c->rd_form == kRdFormLJ && c->par.rd_lrc) {
+        const int mix = c->rd_mix;
+        if (static_pass(c, c->rdf_lrc, !c->rdf_lrc.valid, ntile * ntile, R_DISP_LRC, sb, [&] {
+                hipLaunchKernelGGL(rdform_lrc_kernel, dim3(ntile, ntile), dim3(64 * kRdFormLrcWaves), 0, sb, lj, bx, mix,
+                                   c->rdf_lrc.part);
+            }))
+            return -1;
+    } else {
+        c->call.res_zero_mask |= 1u << R_DISP_LRC;
+        c->rdf_lrc.valid = false;
+    }
+    return tile_pass(c, c->rdf, ntile * ntile, R_DISP, sb, [&](const DirtyBlocks &sel) {
+        const dim3 grid(ntile, sel.n > 0 ? sel.n : ntile), block(64 * kRdFormWaves);
+        double *part = c->rdf.part;
+        const MoveList &mv = c->call.pair_moves;
+        switch (c->rd_form) {
+        case kRdFormLJ: hipLaunchKernelGGL(rdform_tile_kernel<kRdFormLJ>, grid, block, 0, sb, lj, bx, fp, sel, part, mv); break;
+        case kRdFormSG: hipLaunchKernelGGL(rdform_tile_kernel<kRdFormSG>, grid, block, 0, sb, lj, bx, fp, sel, part, mv); break;
+        case kRdFormDreiding:
+            hipLaunchKernelGGL(rdform_tile_kernel<kRdFormDreiding>, grid, block, 0, sb, lj, bx, fp, sel, part, mv);
+            break;
+        default:
+            hipLaunchKernelGGL(rdform_tile_kernel<kRdFormBuffered147>, grid, block, 0, sb, lj, bx, fp, sel, part, mv);
+            break;
+        }
+    });
+}
+
 // axilrod_teller: the block-triple sum (behind the pair and the dispersion launch); the order of the sum over all its
 // partials is a function of the block count only.
 static int launch_at(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipStream_t sb) {
@@ -2733,6 +2831,10 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
         } else if (c->vdw_on) {
             // ---- polarvdw: repulsion-only Lennard-Jones, then the coupled-dipole term (it owns R_AT and R_RDC_SELF here)
             if (launch_vdw(c, a, bx, sb)) return -1;
+        } else if (c->rd_form) {
+            // ---- set_rd_form: the dense sum of the form, and the LJ form's long-range correction
+            if (launch_rdform(c, a, bx, sb)) return -1;
+            k.res_zero_mask |= 1u << R_RDC_SELF;
         } else {
             k.res_zero_mask |= (1u << R_DISP) | (1u << R_DISP_LRC) | (1u << R_RDC_SELF);
         }
@@ -2840,7 +2942,8 @@ static bool graph_eligible(mpmc_hip_ctx *c) {
     const mpmc_hip_params &P = c->par;
     const SweepView &v = c->view[0];
     if (!c->opt.graph || is_timed_call(c) || !c->opt.incremental || !c->opt.incremental_pairs ||
-        !c->opt.pair_coef || c->disp_on || c->at_on || c->rdc_order || c->vdw_on || c->autoreject_scale != 0.0 || c->exact_polar)
+        !c->opt.pair_coef || c->disp_on || c->at_on || c->rdc_order || c->vdw_on || c->rd_form || c->autoreject_scale != 0.0 ||
+        c->exact_polar)
         return false;
     if (P.rd_only || !P.polarization || P.polar_zodid || P.polar_gs || P.polar_gs_ranked || P.polar_precision != 0.0 ||
         P.polar_max_iter <= 0)
@@ -2943,6 +3046,21 @@ extern "C" int mpmc_hip_energy_begin(mpmc_hip_ctx *c) {
     if (c->disp_on && c->rdc_order)
         return fail("MPMC_HIP: energy: rd_crystal with disp_expansion is not implemented (the reference's disp_expansion() "
                     "ignores rd_crystal)");
+    if (c->rd_form) {
+        if (c->disp_on)
+            return fail("MPMC_HIP: energy: a pair potential of set_rd_form with disp_expansion (mpmc_hip_set_dispersion) is not "
+                        "implemented");
+        if (c->rdc_order)
+            return fail("MPMC_HIP: energy: a pair potential of set_rd_form with rd_crystal (mpmc_hip_set_rd_crystal) is not "
+                        "implemented");
+        if (c->vdw_on)
+            return fail("MPMC_HIP: energy: a pair potential of set_rd_form with polarvdw (mpmc_hip_set_vdw) is not implemented");
+        if (c->rd_form != kRdFormSG && c->rd_mix == kRdMixWaldmanHagler && c->negative_sigma)
+            return fail("MPMC_HIP: energy: waldmanhagler mixing with a negative sigma is refused (the reference never assigns "
+                        "the epsilon of such a pair)");
+        if (c->rd_form == kRdFormSG && c->rd_mix != kRdMixLB)
+            return fail("MPMC_HIP: energy: the sg form takes no mixing rule (the reference ignores it there): set mixing lb");
+    }
     if (c->vdw_on) {
         if (c->disp_on)
             return fail("MPMC_HIP: energy: polarvdw with disp_expansion (mpmc_hip_set_dispersion) is not implemented");
@@ -3136,6 +3254,7 @@ extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
     const double rd = c->disp_on     ? (r[R_RD_PAIR] + r[R_LRC]) + (r[R_DISP] + r[R_DISP_LRC])
                       : c->rdc_order ? (r[R_RD_PAIR] + r[R_LRC]) + ((r[R_DISP] + r[R_RDC_SELF]) + r[R_DISP_LRC])
                       : c->vdw_on    ? (r[R_RD_PAIR] + r[R_LRC]) + (r[R_DISP] + r[R_DISP_LRC])  // polarvdw: repulsion only
+                      : c->rd_form   ? (r[R_RD_PAIR] + r[R_LRC]) + (r[R_DISP] + r[R_DISP_LRC])  // set_rd_form: the same slots
                                      : r[R_RD_PAIR] + r[R_LRC];
     const double real = r[R_ES_REAL] - r[R_ES_INTRA];
     const bool ewald = !P.rd_only && !P.wolf;

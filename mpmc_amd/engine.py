@@ -17,7 +17,7 @@ EXPORTS = [
     "mpmc_hip_destroy", "mpmc_hip_set_option", "mpmc_hip_default_params", "mpmc_hip_set_params", "mpmc_hip_set_box",
     "mpmc_hip_scale_box",
     "mpmc_hip_upload", "mpmc_hip_set_dispersion", "mpmc_hip_set_axilrod_teller", "mpmc_hip_get_three_body_energy",
-    "mpmc_hip_set_rd_crystal", "mpmc_hip_set_vdw", "mpmc_hip_get_vdw_energy", "mpmc_hip_get_vdw_terms",
+    "mpmc_hip_set_rd_crystal", "mpmc_hip_set_rd_form", "mpmc_hip_set_vdw", "mpmc_hip_get_vdw_energy", "mpmc_hip_get_vdw_terms",
     "mpmc_hip_set_autoreject", "mpmc_hip_get_close_contacts",
     "mpmc_hip_set_cavity_grid", "mpmc_hip_cavity_bin", "mpmc_hip_cavity_update", "mpmc_hip_cavity_point",
     "mpmc_hip_download_cavity_grid",
@@ -116,17 +116,28 @@ class DispParams(C.Structure):
     ]
 
 
+class RdFormParams(C.Structure):
+    """mpmc_hip_rd_form_params: the pair potential and the Lennard-Jones mixing rule (mpmc_hip_set_rd_form)."""
+    _fields_ = [
+        ("form", C.c_int),
+        ("mixing", C.c_int),
+    ]
+
+
+RD_FORMS = {"off": 0, "lj": 1, "sg": 2, "dreiding": 3, "lj_buffered_14_7": 4}  # MPMC_HIP_RD_*
+RD_MIXINGS = {"lb": 0, "waldmanhagler": 1, "halgren_mixing": 2, "c6_mixing": 3}  # MPMC_HIP_RD_MIX_*
 PARAM_NAMES = [f[0] for f in Params._fields_]
 DISP_NAMES = [f[0] for f in DispParams._fields_]
 AT_NAMES = ["axilrod_teller", "midzuno_kihara_approx"]  # mpmc_hip_set_axilrod_teller (reference keywords)
 RDC_NAMES = ["rd_crystal", "rd_crystal_order"]  # mpmc_hip_set_rd_crystal (reference keywords)
+RDFORM_NAMES = ["sg", "dreiding", "lj_buffered_14_7", "waldmanhagler", "halgren_mixing", "c6_mixing"]  # mpmc_hip_set_rd_form
 VDW_NAMES = ["polarvdw", "cdvdw"]  # mpmc_hip_set_vdw (reference keywords)
 AUTOREJECT_NAMES = ["cavity_autoreject_absolute", "cavity_autoreject_scale"]  # mpmc_hip_set_autoreject (reference keywords)
 EXACT_NAMES = ["polar_iterative"]  # mpmc_hip_set_exact_polar (reference keyword; 0 = the exact dipoles)
 VDW_TERMS = ["e_total", "e_iso", "lr_corr", "repulsion", "repulsion_lrc"]  # mpmc_hip_get_vdw_terms, in its order
 # flags that make_params() leaves to others: pbc_cutoff is a box property at this boundary (set_box), the rest are the
 # arguments of the calls above (Engine.load_system)
-NOT_PARAMS = frozenset(["pbc_cutoff"] + DISP_NAMES + AT_NAMES + RDC_NAMES + VDW_NAMES + AUTOREJECT_NAMES + EXACT_NAMES)
+NOT_PARAMS = frozenset(["pbc_cutoff"] + DISP_NAMES + AT_NAMES + RDC_NAMES + RDFORM_NAMES + VDW_NAMES + AUTOREJECT_NAMES + EXACT_NAMES)
 AT_ALPHA_AU = 6.7483345  # A^3 -> Bohr^3, as the reference writes it (axilrod_teller.cpp:115)
 
 _lib = None
@@ -161,6 +172,7 @@ def load():
     lib.mpmc_hip_set_axilrod_teller.argtypes = [vp, C.c_int, C.c_int, vp]
     lib.mpmc_hip_get_three_body_energy.argtypes = [vp, dp]
     lib.mpmc_hip_set_rd_crystal.argtypes = [vp, C.c_int]
+    lib.mpmc_hip_set_rd_form.argtypes = [vp, C.POINTER(RdFormParams)]
     lib.mpmc_hip_set_vdw.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     lib.mpmc_hip_get_vdw_energy.argtypes = [vp, dp]
     lib.mpmc_hip_get_vdw_terms.argtypes = [vp, dp]
@@ -230,6 +242,17 @@ def effective_c9(system, midzuno_kihara_approx=False):
         c6 = np.asarray(system.get("c6", np.zeros(n)), dtype=np.float64)
         return np.ascontiguousarray(3.0 / 4.0 * alpha * AT_ALPHA_AU * c6)
     return np.ascontiguousarray(system.get("c9", np.zeros(n)), dtype=np.float64)
+
+
+def rd_form_of(params):
+    """(form, mixing) names of set_rd_form() for a flag set: the first of sg / dreiding / lj_buffered_14_7 that is on,
+    else "lj" when a mixing rule is named, else "off"; two mixing rules are the reference's input error
+    (check_input.c:1277-1281)."""
+    mix = [m for m in ("waldmanhagler", "halgren_mixing", "c6_mixing") if params.get(m)]
+    if len(mix) > 1:
+        raise ValueError("INPUT: more than one mixing rule specified")
+    form = next((f for f in ("sg", "dreiding", "lj_buffered_14_7") if params.get(f)), "lj" if mix else "off")
+    return form, (mix[0] if mix else "lb")
 
 
 class Engine:
@@ -314,6 +337,18 @@ class Engine:
         """Lennard-Jones over lattice images (mpmc_hip_set_rd_crystal): order = rd_crystal_order, 1 .. 4; 0 switches the
         mode off.  A context setting: it persists across uploads."""
         _chk(self.lib.mpmc_hip_set_rd_crystal(self.ctx, int(order)))
+
+    def set_rd_form(self, form, mixing="lb"):
+        """The pair potential of rd_energy (mpmc_hip_set_rd_form): form "sg", "dreiding", "lj_buffered_14_7" or "lj"
+        (Lennard-Jones on the dense path, for the mixing rules), "off" / None / 0 for the standard path; mixing "lb",
+        "waldmanhagler", "halgren_mixing" or "c6_mixing".  A context setting: it persists across uploads."""
+        form = "off" if not form else form
+        if form not in RD_FORMS:
+            raise ValueError("unknown rd form %r (one of %s)" % (form, ", ".join(RD_FORMS)))
+        if mixing not in RD_MIXINGS:
+            raise ValueError("unknown mixing rule %r (one of %s)" % (mixing, ", ".join(RD_MIXINGS)))
+        p = RdFormParams(RD_FORMS[form], RD_MIXINGS[mixing])
+        _chk(self.lib.mpmc_hip_set_rd_form(self.ctx, C.byref(p)))
 
     def set_vdw(self, system, enable=True):
         """Coupled-dipole van der Waals + repulsion-only Lennard-Jones (mpmc_hip_set_vdw), after upload(): the per-atom
@@ -419,11 +454,15 @@ class Engine:
         carry polarvdw).  cavity_autoreject_absolute + cavity_autoreject_scale switch the close-contact count on; without
         them it is switched off.  rd_crystal / rd_crystal_order among
         the flags switch the image sum on (order 1 when only rd_crystal is given); without them it is switched off.
-        polar_iterative = 0 together with polarization switches the exact dipoles on; anything else switches them off."""
+        polar_iterative = 0 together with polarization switches the exact dipoles on; anything else switches them off.
+        sg / dreiding / lj_buffered_14_7 switch that pair potential on (set_rd_form), waldmanhagler / halgren_mixing /
+        c6_mixing name its mixing rule and, without another form, switch the dense Lennard-Jones form on; without any of
+        the six the standard path is restored."""
         self.set_exact_polar("polar_iterative" in params and not params["polar_iterative"]
                              and bool(params.get("polarization")))
         self.set_params(**params)
         self.set_rd_crystal(int(params.get("rd_crystal_order", 1)) if params.get("rd_crystal") else 0)
+        self.set_rd_form(*rd_form_of(params))
         self.set_autoreject(float(params.get("cavity_autoreject_scale", 0.0))
                             if params.get("cavity_autoreject_absolute") else 0.0)
         self.set_box(system["basis"], params.get("pbc_cutoff", 0.0))

@@ -94,6 +94,8 @@ def load():
     lib.host_displace_molecule.argtypes = [vp, C.c_int, vp]
     lib.host_get_rdc_flags.argtypes = [vp, vp]
     lib.host_get_rdc_flags.restype = None
+    lib.host_get_rdform_flags.argtypes = [vp, vp]
+    lib.host_get_rdform_flags.restype = None
     lib.host_read_frame.argtypes = [vp, C.c_char_p, C.c_int]
     lib.host_unsupported.argtypes = [vp]
     lib.host_unsupported.restype = C.c_char_p
@@ -119,7 +121,7 @@ def config_text(flags, extra=None):
              "disp_expansion", "damp_dispersion", "extrapolate_disp_coeffs", "schmidt_mixing", "axilrod_teller",
              "midzuno_kihara_approx", "rd_crystal", "read_pqr_box", "calc_pressure", "polarvdw", "cdvdw",
              "cavity_autoreject_absolute", "cavity_bias", "cdvdw_exp_repulsion", "cdvdw_sig_repulsion",
-             "cdvdw_9th_repulsion",
+             "cdvdw_9th_repulsion", "sg", "dreiding", "lj_buffered_14_7", "waldmanhagler", "halgren_mixing", "c6_mixing",
              "polar_iterative", "polarizability_tensor"}
     lines = []
     for k, v in flags.items():

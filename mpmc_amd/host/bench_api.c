@@ -28,6 +28,7 @@ int host_apply_config(system_t *system, const char *text) {
     if (system->ensemble == ENSEMBLE_UVT && !(system->fugacity > 0.0)) return 1;
     if (system->ensemble == ENSEMBLE_NPT && !(system->pressure > 0.0)) return 1; /* check_input.c:673-678 */
     if (system->rd_crystal && system->rd_crystal_order <= 0) return 1;            /* check_input.c:1258-1263 */
+    if (system->waldmanhagler + system->halgren_mixing + system->c6_mixing > 1) return 1; /* check_input.c:1277-1281 */
     if (system->cavity_autoreject_absolute &&                                     /* check_input.c:872-878 */
         ((system->cavity_autoreject_scale <= 0.0) || (system->cavity_autoreject_scale > 1.78)))
         return 1;
@@ -301,6 +302,15 @@ int host_displace_molecule(system_t *system, int index, const double d[3]) {
 void host_get_rdc_flags(system_t *system, int out[2]) {
     out[0] = system->rd_crystal;
     out[1] = system->rd_crystal_order;
+}
+/* sg, dreiding, lj_buffered_14_7, waldmanhagler, halgren_mixing, c6_mixing */
+void host_get_rdform_flags(system_t *system, int out[6]) {
+    out[0] = system->sg;
+    out[1] = system->dreiding;
+    out[2] = system->lj_buffered_14_7;
+    out[3] = system->waldmanhagler;
+    out[4] = system->halgren_mixing;
+    out[5] = system->c6_mixing;
 }
 /* frame `index` (from 0) of the PQR trajectory `path` becomes the system's configuration, read the way
  * replay_trajectory() reads it: every frame in front of it is read (and freed) first, so the box and the cutoff are

@@ -56,6 +56,7 @@ typedef struct shim_state {
     int capacity; /* atoms the context was created for */
     int uploaded; /* a configuration is resident */
     int rdc_order; /* rd_crystal_order as sent with that upload (0: rd_crystal off) */
+    mpmc_hip_rd_form_params rd_form; /* the pair potential and mixing rule as sent with that upload */
     int vdw_on;    /* polarvdw as sent with that upload */
     int exact;     /* the exact dipoles (polarization with polar_iterative off) as sent with that upload */
     double ar_scale; /* cavity_autoreject_scale as sent with that upload (0: cavity_autoreject_absolute off) */
@@ -220,7 +221,7 @@ static void fill_params(const system_t *s, mpmc_hip_params *p) {
     memset(p, 0, sizeof(*p)); /* padding too: the record is compared with memcmp() */
     mpmc_hip_default_params(p);
     p->temperature = s->temperature;
-    p->rd_only = s->rd_only;
+    p->rd_only = s->rd_only || s->sg; /* energy.c:108, :154: no electrostatics and no polarization under sg */
     p->rd_lrc = s->rd_lrc;
     p->feynman_hibbs = s->feynman_hibbs;
     p->feynman_hibbs_order = s->feynman_hibbs_order;
@@ -247,6 +248,25 @@ static void fill_params(const system_t *s, mpmc_hip_params *p) {
     p->wolf = s->wolf;
 }
 
+/* energy.c:132-145: sg, dreiding and lj_buffered_14_7 in the order of its branches; a mixing rule alone puts Lennard-Jones on
+ * the dense path that knows the rule (pairs.c:84-211, in the order of its branches) */
+static void fill_rd_form(const system_t *s, mpmc_hip_rd_form_params *f) {
+    memset(f, 0, sizeof(*f));
+    f->mixing = s->waldmanhagler ? MPMC_HIP_RD_MIX_WALDMAN_HAGLER
+                : s->halgren_mixing ? MPMC_HIP_RD_MIX_HALGREN
+                : s->c6_mixing      ? MPMC_HIP_RD_MIX_C6
+                                    : MPMC_HIP_RD_MIX_LB;
+    if (s->sg)
+        f->form = MPMC_HIP_RD_SG;
+    else if (s->dreiding)
+        f->form = MPMC_HIP_RD_DREIDING;
+    else if (s->lj_buffered_14_7)
+        f->form = MPMC_HIP_RD_BUFFERED_14_7;
+    else if (f->mixing != MPMC_HIP_RD_MIX_LB)
+        f->form = MPMC_HIP_RD_LJ;
+    if (!f->form) f->mixing = 0;
+}
+
 static void fill_disp_params(const system_t *s, mpmc_hip_disp_params *d) {
     memset(d, 0, sizeof(*d));
     d->disp_expansion = s->disp_expansion;
@@ -259,9 +279,9 @@ static void fill_disp_params(const system_t *s, mpmc_hip_disp_params *d) {
  * src/io/check_input.c:325-341, extended to the whole of energy()). */
 static const char *unsupported(const system_t *s) {
 #ifndef MPMC_SHIM_HOST_MIRROR
-    if (s->sg || s->dreiding || s->lj_buffered_14_7 || s->rd_anharmonic || s->gwp || s->spectre)
-        return "only Lennard-Jones or disp_expansion repulsion / dispersion (with or without axilrod_teller) and point "
-               "charges are on the device";
+    if (s->rd_anharmonic) return "rd_anharmonic (the anharmonic bond) is not on the device";
+    if (s->gwp) return "gwp (Gaussian wave packets) is not on the device";
+    if (s->spectre) return "spectre is not on the device";
     /* pairs.c:85-141: these mixing branches come before the disp_expansion one (sg is refused above, the cdvdw_*
      * repulsions below) */
     if (s->disp_expansion && (s->waldmanhagler || s->halgren_mixing))
@@ -269,10 +289,40 @@ static const char *unsupported(const system_t *s) {
     if (s->polarvdw && (s->waldmanhagler || s->halgren_mixing))
         return "polarvdw with waldmanhagler / halgren_mixing is not on the device";
     if (s->polarvdw && s->vdw_fh_2be) return "vdw_fh_2be is not on the device";
+    if (s->ensemble == ENSEMBLE_SURF && (s->sg || s->dreiding || s->lj_buffered_14_7 || s->waldmanhagler || s->halgren_mixing ||
+                                         s->c6_mixing))
+        return "ensemble surf with sg / dreiding / lj_buffered_14_7 or a mixing rule is not on the device";
     if (s->polarization && s->damp_type != DAMPING_EXPONENTIAL) return "exponential Thole damping only";
     if (s->polarization && (s->polar_ewald_full || s->polar_wolf_full)) return "polar_ewald_full / polar_wolf_full are not on the device";
     if (s->ensemble == ENSEMBLE_NVE) return "ensemble nve is not supported";
 #endif
+    /* sg, dreiding, lj_buffered_14_7 and the Lennard-Jones mixing rules are on the device (mpmc_hip_set_rd_form); the
+     * combinations it does not have are refused by name */
+    {
+        mpmc_hip_rd_form_params f;
+        fill_rd_form(s, &f);
+        if (f.form && s->disp_expansion)
+            return "disp_expansion with sg / dreiding / lj_buffered_14_7 / c6_mixing is not on the device";
+        if (f.form && s->rd_crystal)
+            return "rd_crystal with sg / dreiding / lj_buffered_14_7 or a mixing rule is not on the device";
+        if (f.form && s->polarvdw)
+            return "polarvdw with sg / dreiding / lj_buffered_14_7 / c6_mixing is not on the device";
+        if (f.form == MPMC_HIP_RD_SG && f.mixing != MPMC_HIP_RD_MIX_LB)
+            return "sg with waldmanhagler / halgren_mixing / c6_mixing is refused (the reference ignores the mixing rule there)";
+        if (f.form == MPMC_HIP_RD_SG || (f.form && f.mixing == MPMC_HIP_RD_MIX_WALDMAN_HAGLER)) {
+            int nfrozen = 0, negative = 0;
+            for (const molecule_t *m = s->molecules; m; m = m->next)
+                for (const atom_t *a = m->atoms; a; a = a->next) {
+                    nfrozen += (a->frozen != 0);
+                    negative |= (a->sigma < 0.0);
+                }
+            if (f.form == MPMC_HIP_RD_SG && nfrozen >= 2)
+                return "sg with two or more frozen atoms is refused (the reference sums uninitialised distances for "
+                       "frozen-frozen pairs there)";
+            if (f.form != MPMC_HIP_RD_SG && negative)
+                return "waldmanhagler with a negative sigma is refused (the reference never assigns the epsilon of such a pair)";
+        }
+    }
     /* polar_iterative off: the exact dipoles are on the device (mpmc_hip_set_exact_polar); the rest is refused by name */
     if (s->polarization && !s->polar_iterative && s->polar_zodid)
         return "ZODID and matrix inversion cannot both be set! (polar_zodid with polar_iterative off)"; /* check_input.c:349-353 */
@@ -432,6 +482,8 @@ static int full_upload(shim_state *st, system_t *system) {
     if (rc) return hip_fail("upload");
     st->rdc_order = system->rd_crystal ? system->rd_crystal_order : 0;
     if (mpmc_hip_set_rd_crystal(st->ctx, st->rdc_order)) return hip_fail("set_rd_crystal");
+    fill_rd_form(system, &st->rd_form);
+    if (mpmc_hip_set_rd_form(st->ctx, &st->rd_form)) return hip_fail("set_rd_form");
     fill_disp_params(system, &st->disp);
     /* (an upload leaves the context on Lennard-Jones: nothing to say unless the PHAHST potential is asked for) */
     if (st->disp.disp_expansion && mpmc_hip_set_dispersion(st->ctx, &st->disp, n, st->c6, st->c8, st->c10))
@@ -1012,6 +1064,9 @@ int energy_hip_begin(system_t *system) {
         fill_disp_params(system, &dnow);
         if (memcmp(&dnow, &st->disp, sizeof(dnow))) need_upload = 1;
         if ((system->rd_crystal ? system->rd_crystal_order : 0) != st->rdc_order) need_upload = 1;
+        mpmc_hip_rd_form_params fnow;
+        fill_rd_form(system, &fnow);
+        if (memcmp(&fnow, &st->rd_form, sizeof(fnow))) need_upload = 1;
         if ((system->polarvdw != 0) != st->vdw_on) need_upload = 1;
         if ((system->polarization && !system->polar_iterative) != st->exact) need_upload = 1;
         if ((system->cavity_autoreject_absolute ? system->cavity_autoreject_scale : 0.0) != st->ar_scale) need_upload = 1;
@@ -1221,7 +1276,7 @@ int energy_hip_corrtime(system_t *system) {
 #ifndef MPMC_SHIM_HOST_MIRROR
     wrapall(system->molecules, system->pbc); /* pairs.c:334 does this on every step; only the writers read it */
 #endif
-    if (system->polarization && !system->rd_only) return energy_hip_download_dipoles(system);
+    if (system->polarization && !system->rd_only && !system->sg) return energy_hip_download_dipoles(system);
     return 0;
 }
 

@@ -166,6 +166,12 @@ int do_command(system_t *system, char **token) {
     FLAG("axilrod_teller", axilrod_teller); /* input.c:992-1013 */
     FLAG("midzuno_kihara_approx", midzuno_kihara_approx);
     FLAG("rd_crystal", rd_crystal); /* input.c:814-826 */
+    FLAG("sg", sg);                 /* input.c:884-941, :1064-1073 */
+    FLAG("dreiding", dreiding);
+    FLAG("lj_buffered_14_7", lj_buffered_14_7);
+    FLAG("waldmanhagler", waldmanhagler);
+    FLAG("halgren_mixing", halgren_mixing);
+    FLAG("c6_mixing", c6_mixing);
     if (!strcasecmp(k, "polarvdw") || !strcasecmp(k, "cdvdw")) { /* input.c:446-475 */
         if (!strcasecmp(v, "off")) {
             system->polarvdw = 0;
@@ -451,6 +457,18 @@ static int check_system(system_t *system) {
         snprintf(linebuf, MAXLINE, "INPUT: rd crystal order set to %d.\n", system->rd_crystal_order);
         output(linebuf);
     }
+    /* check_input.c:1269-1287 */
+    if (system->sg) output("INPUT: Molecular potential is Silvera-Goldman\n");
+    if (system->waldmanhagler) output("INPUT: Using Waldman-Hagler mixing rules for LJ-interactions.\n");
+    if (system->halgren_mixing) output("INPUT: Using Halgren mixing rules for LJ-interactions.\n");
+    if (system->c6_mixing) output("INPUT: Using C6 mixing rules for LJ-interactions.\n");
+    if ((system->waldmanhagler && system->halgren_mixing) || (system->waldmanhagler && system->c6_mixing) ||
+        (system->halgren_mixing && system->c6_mixing)) {
+        error("INPUT: more than one mixing rule specified\n");
+        return -1;
+    }
+    if (system->dreiding) output("INPUT: Molecular potential is DREIDING\n");
+    if (system->lj_buffered_14_7) output("INPUT: Molecular potential is lj_buffered_14_7\n");
     if (system->polarvdw && !system->cavity_autoreject_absolute && system->ensemble != ENSEMBLE_REPLAY) {
         error("INPUT: cavity_autoreject_absolute must be used with polarvdw + Feynman Hibbs.\n"); /* check_input.c:216-221 */
         return -1;

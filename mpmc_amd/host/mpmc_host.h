@@ -129,6 +129,9 @@ typedef struct _system {
     int axilrod_teller, midzuno_kihara_approx;
     /* Lennard-Jones over lattice images (structs.h, lj.c:109-276): sent with mpmc_hip_set_rd_crystal() */
     int rd_crystal, rd_crystal_order;
+    /* the other pair potentials of energy() (structs.h; sg.c, dreiding.c, lj_buffered_14_7.c) and the Lennard-Jones mixing
+     * rules of pairs.c:84-211: sent with mpmc_hip_set_rd_form() */
+    int sg, dreiding, lj_buffered_14_7, waldmanhagler, halgren_mixing, c6_mixing;
     /* coupled-dipole many-body van der Waals (structs.h; vdw.c): 1 = on; 2 (evects) and 3 (comp) are read so that
      * energy_hip.c can refuse them by name, like the three repulsion variants */
     int polarvdw, cdvdw_exp_repulsion, cdvdw_sig_repulsion, cdvdw_9th_repulsion;
