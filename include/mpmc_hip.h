@@ -415,6 +415,28 @@ int mpmc_hip_set_exact_polar(mpmc_hip_ctx *ctx, int enable);
  * with polarization has completed in it, or when that call's matrix was not positive definite. */
 int mpmc_hip_get_polarizability_tensor(mpmc_hip_ctx *ctx, double out[9]);
 
+/* The dipole tensor of the A matrix (reference thole_amatrix(), thole_matrix.c:90-135): T = c3 I - 3 c5 d d^T with
+ *   damp_type 2 (exponential, the default): c3 = damp1/r^3, c5 = damp2/r^5, damp1 = 1 - e^{-lr}(l^2r^2/2 + lr + 1),
+ *                 damp2 = damp1 - e^{-lr} l^3r^3/6, l = polar_damp;
+ *   damp_type 1 (linear, Thole's original): s = polar_damp (alpha_i alpha_j)^(1/6), v = r/s; for r < s damp1 = (4 - 3v) v^3
+ *                 and damp2 = v^4, otherwise both 1 (a site with alpha = 0 gives s = 0: undamped);
+ *   damp_type 0 (off / none, Applequist): damp1 = damp2 = 1, but 0 for a pair the reference calls es_excluded: two atoms
+ *                 of one molecule, or a pair in which either charge is exactly 0.0 (pairs.c:61-77; the quirk is kept);
+ *                 set_params() then accepts polar_damp <= 0 (check_input.c:406-409);
+ *   wolf_full (polar_wolf_full; damp_type 2 only): c3 = damp1/r^3 - wdamp1/rc^3, c5 = damp2/r^5 - wdamp2/(r^2 rc^3) with
+ *                 wdamp = damp at r = rc = the box cutoff, for EVERY pair (the reference has no r < rc test there), and
+ *                 the static field is the Wolf field whether or not polar_wolf is set (thole_field.c:32).
+ * The values of damp_type are the reference's (DAMPING_OFF / _LINEAR / _EXPONENTIAL).  A setting of the context like
+ * mpmc_hip_set_rd_crystal(): it persists across uploads, the default is {2, 0}, and it is not allowed between
+ * energy_begin() and energy_end().  Changing it drops the coefficient store, the expanded matrix and the chain data.
+ * Refused by name: wolf_full with a damp_type other than 2; at energy(), a non-default model while polarvdw
+ * (mpmc_hip_set_vdw) is on -- the reference's e2body() / calc_e_iso() are written for the exponential form. */
+typedef struct mpmc_hip_thole_model {
+    int damp_type; /* 0 off, 1 linear, 2 exponential */
+    int wolf_full; /* polar_wolf_full */
+} mpmc_hip_thole_model;
+int mpmc_hip_set_thole_model(mpmc_hip_ctx *ctx, const mpmc_hip_thole_model *m);
+
 /* cavity_autoreject_absolute (reference energy.c:48-64): with scale = cavity_autoreject_scale > 0 every energy() also
  * counts the pairs of atoms on DIFFERENT molecules -- frozen-frozen pairs included -- whose minimum-image distance is
  * < scale, the distance and the comparison in the reference's fp64 operation order.  0 = off.  A setting of the context

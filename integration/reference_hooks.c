@@ -36,11 +36,13 @@ int hook_do_command(system_t *system, char **token) {
  * call and fails (never computes something else) when an option it does not implement is on.  `disp_expansion` is no
  * longer among them (default and Schmidt mixing, with or without damp_dispersion / extrapolate_disp_coeffs); the other
  * mixing rules and disp_expansion_mbvdw are refused there, each by name.  Nor is `polar_iterative off`: the engine solves
- * the linear system directly then (mpmc_hip_set_exact_polar) */
+ * the linear system directly then (mpmc_hip_set_exact_polar).  Nor are polar_damp_type linear / off and polar_wolf_full:
+ * the engine has all of thole_amatrix()'s tensors (mpmc_hip_set_thole_model); what stays is the one combination it
+ * refuses */
 int hook_check_system(system_t *system) {
     if (system->hip && system->polarization) {
-        if (system->damp_type != DAMPING_EXPONENTIAL) {
-            error("INPUT: HIP engine available for exponential Thole damping only\n");
+        if (system->polar_wolf_full && system->damp_type != DAMPING_EXPONENTIAL) {
+            error("INPUT: HIP engine: polar_wolf_full needs polar_damp_type exponential\n");
             return -1;
         }
     }

@@ -484,6 +484,9 @@ struct mpmc_hip_ctx {
     // ---- exact dipoles (mpmc_hip_set_exact_polar): blocked Cholesky of view 0's matrix, kernels_exact.h.  A context setting:
     // it persists across uploads.  Nothing below is allocated while the mode is off.
     bool exact_polar = false;
+    // ---- the dipole tensor (mpmc_hip_set_thole_model): a context setting, persists across uploads
+    int thole_damp_type = 2;        // the reference's values: 0 off, 1 linear, 2 exponential
+    bool thole_wolf_full = false;   // polar_wolf_full (exponential only)
     DevBuf<double> d_chol_W;        // [3 nvpad][3 nvpad] the work copy, L in its lower triangle after a call
     DevBuf<double> d_chol_vec;      // b, y, x of the substitutions: [3][3][3 nvpad]
     DevBuf<unsigned> d_chol_flag;   // [0]: a pivot of this call's factorization was not positive
@@ -639,6 +642,40 @@ static DevBox dev_box(const mpmc_hip_ctx *c) {
     b.tie_guard = c->box_ortho ? 0 : 1;
     return b;
 }
+
+// The dipole tensor's model and its parameters (kernels_polar.h).  `idx`: the atom of each slot when the kernel's atom
+// set is a sweep view, nullptr when it is the configuration.  The Wolf constants are those of the current box: every
+// launch forms them anew, so a box change needs no bookkeeping beyond the rebuild it already causes.
+static int thole_model_of(const mpmc_hip_ctx *c) {
+    if (c->thole_damp_type == 0) return kTholeOff;
+    if (c->thole_damp_type == 1) return kTholeLinear;
+    return c->thole_wolf_full ? kTholeExpWolf : kTholeExp;
+}
+static TholeParams thole_params(const mpmc_hip_ctx *c, const int *idx) {
+    TholeParams tp;
+    tp.damp = c->par.polar_damp;
+    tp.rc = c->cutoff;
+    tp.irc3 = tp.wdamp1 = tp.wdamp2 = 0.0;
+    tp.idx = nullptr;
+    const int model = thole_model_of(c);
+    if (model == kTholeOff) tp.idx = idx;
+    if (model == kTholeExpWolf) {  // thole_matrix.c:44-53, :113-114
+        const double l = tp.damp, l2 = l * l, l3 = l2 * l, rc = tp.rc, rc2 = rc * rc, rc3 = rc2 * rc;
+        const double explrcut = std::exp(-l * rc);
+        tp.wdamp1 = 1.0 - explrcut * (0.5 * l2 * rc2 + l * rc + 1.0);
+        tp.wdamp2 = tp.wdamp1 - explrcut * (l3 * rc3 / 6.0);
+        tp.irc3 = 1.0 / rc3;
+    }
+    return tp;
+}
+// KERNEL<MODEL> for the context's model: every model is an instantiation of its own, the exponential one today's code
+#define MPMC_THOLE_DISPATCH(c, ...)                                                   \
+    do switch (thole_model_of(c)) {                                                   \
+        case kTholeLinear: { constexpr int kM = kTholeLinear; __VA_ARGS__; break; }   \
+        case kTholeOff: { constexpr int kM = kTholeOff; __VA_ARGS__; break; }         \
+        case kTholeExpWolf: { constexpr int kM = kTholeExpWolf; __VA_ARGS__; break; } \
+        default: { constexpr int kM = kTholeExp; __VA_ARGS__; break; }                \
+    } while (0)
 
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static int complete_pending_sweep(mpmc_hip_ctx *c);  // engine_polar.inc
@@ -1032,7 +1069,9 @@ extern "C" int mpmc_hip_set_params(mpmc_hip_ctx *c, const mpmc_hip_params *p) {
     if (p->wolf && p->feynman_hibbs && !p->rd_only)
         return fail("MPMC_HIP: COULOMBIC: FH + es_wolf is not implemented");  // coulombic.c:294-298
     if (p->polarization) {
-        if (!(p->polar_damp > 0.0)) return fail("MPMC_HIP: damping factor must be specified (polar_damp > 0)");
+        // (check_input.c:406-409: not under polar_damp_type off, which reads no damping factor; energy() asks again
+        //  should the model be switched back)
+        if (!(p->polar_damp > 0.0) && c->thole_damp_type != 0) return fail("MPMC_HIP: damping factor must be specified (polar_damp > 0)");
         if (p->polar_precision > 0.0 && p->polar_max_iter > 0)
             return fail("MPMC_HIP: cannot specify both polar_precision and polar_max_iter, must pick one");
         if (p->polar_precision < 0.0) return fail("MPMC_HIP: invalid polarization iterative precision specified");
@@ -1398,6 +1437,30 @@ extern "C" int mpmc_hip_set_exact_polar(mpmc_hip_ctx *c, int enable) {
     if (complete_pending_sweep(c)) return -1;
     if (c->have_atoms && flush_moves(c)) return -1;  // keep the order of the caller's operations
     c->exact_polar = enable != 0;
+    c->chol_nv = 0;
+    c->chol_done = c->chol_failed = false;
+    c->all_dirty = true;
+    ++c->config_rev;
+    return 0;
+}
+
+// The dipole tensor's model (thole_matrix.c:90-135; kernels_polar.h).  A setting of the context, like set_rd_crystal().
+// Everything made from the tensor -- the coefficient store, the expanded matrix, the chain data, the Cholesky factor --
+// goes with all_dirty; the static field's mode is part of its partials' key (launch_field()).
+extern "C" int mpmc_hip_set_thole_model(mpmc_hip_ctx *c, const mpmc_hip_thole_model *m) {
+    if (!c || !m) return fail("MPMC_HIP: set_thole_model: null argument");
+    if (c->in_flight) return fail("MPMC_HIP: set_thole_model between energy_begin() and energy_end()");
+    if (m->damp_type < 0 || m->damp_type > 2)
+        return fail("MPMC_HIP: set_thole_model: damp_type %d outside 0 (off), 1 (linear), 2 (exponential)", m->damp_type);
+    if (m->wolf_full && m->damp_type != 2)
+        return fail("MPMC_HIP: set_thole_model: polar_wolf_full needs polar_damp_type exponential (damp_type 2)");
+    const bool wolf_full = m->wolf_full != 0;
+    if (m->damp_type == c->thole_damp_type && wolf_full == c->thole_wolf_full) return 0;  // nothing to change
+    HIPCHK(hipSetDevice(c->device));
+    if (complete_pending_sweep(c)) return -1;
+    if (c->have_atoms && flush_moves(c)) return -1;  // keep the order of the caller's operations
+    c->thole_damp_type = m->damp_type;
+    c->thole_wolf_full = wolf_full;
     c->chol_nv = 0;
     c->chol_done = c->chol_failed = false;
     c->all_dirty = true;
@@ -3061,7 +3124,13 @@ extern "C" int mpmc_hip_energy_begin(mpmc_hip_ctx *c) {
         if (c->rd_form == kRdFormSG && c->rd_mix != kRdMixLB)
             return fail("MPMC_HIP: energy: the sg form takes no mixing rule (the reference ignores it there): set mixing lb");
     }
+    if (c->have_params && c->par.polarization && !c->par.rd_only && c->thole_damp_type != 0 && !(c->par.polar_damp > 0.0))
+        return fail("MPMC_HIP: energy: damping factor must be specified (polar_damp > 0) unless polar_damp_type is off");
     if (c->vdw_on) {
+        if (c->thole_damp_type != 2 || c->thole_wolf_full)
+            return fail("MPMC_HIP: energy: polarvdw with polar_damp_type linear / off or polar_wolf_full "
+                        "(mpmc_hip_set_thole_model) is not implemented (the reference's e2body() / calc_e_iso() are written "
+                        "for the exponential form)");
         if (c->disp_on)
             return fail("MPMC_HIP: energy: polarvdw with disp_expansion (mpmc_hip_set_dispersion) is not implemented");
         if (c->rdc_order)
@@ -3324,8 +3393,8 @@ extern "C" int mpmc_hip_download_amatrix(mpmc_hip_ctx *c, double *A) {
     if (flush_moves(c)) return -1;
     DevBuf<double> dA;
     HIPCHK(dA.alloc(lda * lda));
-    hipLaunchKernelGGL(build_amatrix_kernel, dim3(c->npad / 128, c->npad / kARows), dim3(64), 0, c->stream,
-                       dev_atoms(c), dev_box(c), c->par.polar_damp, dA, (int)lda);
+    MPMC_THOLE_DISPATCH(c, hipLaunchKernelGGL((build_amatrix_kernel<kM>), dim3(c->npad / 128, c->npad / kARows), dim3(64), 0,
+                                              c->stream, dev_atoms(c), dev_box(c), thole_params(c, nullptr), dA, (int)lda));
     hipError_t e = hipMemcpy2DAsync(A, n3 * sizeof(double), dA, lda * sizeof(double), n3 * sizeof(double), n3,
                                     hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);

@@ -13,8 +13,9 @@ static int launch_coef_job(mpmc_hip_ctx *c, const DevBox &bx) {
     if (!c->call.coef_job_valid) return 0;
     c->call.coef_job_valid = false;
     const CoefJob &cj = c->call.coef_job;
-    hipLaunchKernelGGL(update_coef_moves_kernel, dim3(cj.nt, cj.dm.n), dim3(64), 0, c->stream, cj.pa, bx, cj.damp, cj.dm,
-                       cj.ntld, cj.C, cj.m, cj.gx, cj.gy, cj.gz, cj.slot_of_atom, cj.px, cj.py, cj.pz);
+    MPMC_THOLE_DISPATCH(c, hipLaunchKernelGGL((update_coef_moves_kernel<kM>), dim3(cj.nt, cj.dm.n), dim3(64), 0, c->stream, cj.pa,
+                                              bx, cj.tp, cj.dm, cj.ntld, cj.C, cj.m, cj.gx, cj.gy, cj.gz, cj.slot_of_atom, cj.px,
+                                              cj.py, cj.pz));
     if (c->call.coef_job_fork) hipEventRecord(c->ev_fork, c->stream);
     return 0;
 }
@@ -33,7 +34,8 @@ static int launch_field(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx) {
     fp.chunk = chunk;
     // The real-space partials persist between calls: with nothing moved since the last call the kernel is
     // skipped, after a single-molecule move only the tiles of the moved atoms' blocks are recomputed.
-    const int mode = P.polar_ewald ? kFieldEwald : (!P.polar_wolf ? kFieldBare : (P.polar_wolf_alpha == 0.0 ? kFieldWolf0 : kFieldWolfA));
+    const bool wolf = P.polar_wolf || c->thole_wolf_full;  // thole_field.c:32
+    const int mode = P.polar_ewald ? kFieldEwald : (!wolf ? kFieldBare : (P.polar_wolf_alpha == 0.0 ? kFieldWolf0 : kFieldWolfA));
     const int key = mode * 1000003 + chunk;
     DirtyBlocks sel = c->call.dirty_blocks;
     const bool resident = c->field_part_valid && c->field_key == key;
@@ -72,19 +74,22 @@ static int launch_field(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx) {
     if (fused) {
         const CoefJob &cj = c->call.coef_job;
         c->call.coef_job_valid = false;
-        if (!P.polar_wolf) {
-            hipLaunchKernelGGL(field_coef_kernel<kFieldBare>, grid, block, 0, c->stream, a, bx, fp, sel, c->d_fieldpart, cj);
+        if (!wolf) {
+            MPMC_THOLE_DISPATCH(c, hipLaunchKernelGGL((field_coef_kernel<kFieldBare, kM>), grid, block, 0, c->stream, a, bx, fp, sel,
+                                                      c->d_fieldpart, cj));
         } else if (P.polar_wolf_alpha == 0.0) {
-            hipLaunchKernelGGL(field_coef_kernel<kFieldWolf0>, grid, block, 0, c->stream, a, bx, fp, sel, c->d_fieldpart, cj);
+            MPMC_THOLE_DISPATCH(c, hipLaunchKernelGGL((field_coef_kernel<kFieldWolf0, kM>), grid, block, 0, c->stream, a, bx, fp, sel,
+                                                      c->d_fieldpart, cj));
         } else {
             const double al = P.polar_wolf_alpha, R = c->cutoff, rR = 1.0 / R;
             fp.cutoffterm = std::erfc(al * R) * rR * rR + 2.0 * al * kOneOverSqrtPi * std::exp(-al * al * R * R) * rR;
-            hipLaunchKernelGGL(field_coef_kernel<kFieldWolfA>, grid, block, 0, c->stream, a, bx, fp, sel, c->d_fieldpart, cj);
+            MPMC_THOLE_DISPATCH(c, hipLaunchKernelGGL((field_coef_kernel<kFieldWolfA, kM>), grid, block, 0, c->stream, a, bx, fp, sel,
+                                                      c->d_fieldpart, cj));
         }
         HIPCHK(hipGetLastError());
         if (c->call.coef_job_fork) hipEventRecord(c->ev_fork, c->stream);
     } else if (!skip) {
-        if (!P.polar_wolf) {
+        if (!wolf) {
             HIPCHK(launch_slot(c, GS_FIELD, static_field_kernel<kFieldBare>, grid, block, c->stream, a, bx, fp, sel, c->d_fieldpart));
         } else if (P.polar_wolf_alpha == 0.0) {
             HIPCHK(launch_slot(c, GS_FIELD, static_field_kernel<kFieldWolf0>, grid, block, c->stream, a, bx, fp, sel, c->d_fieldpart));
@@ -156,6 +161,7 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
     pa.flags = v.pflags;
     pa.n = v.nv;
     pa.npad = v.nvpad;
+    const TholeParams tp = thole_params(c, v.d_idx);  // (q and mol stay in atom order: the undamped model reads them through d_idx)
     ScopedTimer t(c, T_AMAT, st);
     // The tensor data stays resident between calls: after a single-molecule move only the entries of pairs
     // that involve a moved atom are rewritten (bit-identical to a full rebuild).
@@ -178,11 +184,11 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
         if (ensure_view_coef(c, v, nt, st)) return -1;
         if (can_update && v.C_valid) {
             if (tail >= 0)
-                hipLaunchKernelGGL(build_coef_kernel, dim3(nt, nt), dim3(64 * kCoefWaves), 0, st, pa, bx, c->par.polar_damp,
-                                   v.ntld, v.C, tail);
+                MPMC_THOLE_DISPATCH(c, hipLaunchKernelGGL((build_coef_kernel<kM>), dim3(nt, nt), dim3(64 * kCoefWaves), 0, st, pa,
+                                                          bx, tp, v.ntld, v.C, tail));
             if (nd > 0 && side)
-                hipLaunchKernelGGL(update_coef_kernel, dim3(nt, nd), dim3(64), 0, st, pa, bx, c->par.polar_damp, dl, v.ntld,
-                                   v.C);
+                MPMC_THOLE_DISPATCH(c, hipLaunchKernelGGL((update_coef_kernel<kM>), dim3(nt, nd), dim3(64), 0, st, pa, bx, tp, dl,
+                                                          v.ntld, v.C));
             else if (nd > 0 && fuse_moves && nd <= kMaxDirtyMoves) {
                 // the move and the coefficient update in one launch (kernels_coef.h)
                 DirtyMoves dm;
@@ -210,7 +216,7 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
                     // grid (field_coef_kernel) or, when it cannot, launches update_coef_moves_kernel in front of it
                     CoefJob &cj = c->call.coef_job;
                     cj.pa = pa;
-                    cj.damp = c->par.polar_damp;
+                    cj.tp = tp;
                     cj.dm = dm;
                     cj.nt = nt;
                     cj.ntld = v.ntld;
@@ -235,20 +241,20 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
                     if (want_chain && launch_coef_job(c, bx)) return -1;
                 } else {  // a dirty slot whose coordinates are already on the device (staged copy): the plain way
                     if (apply_deferred_moves(c)) return -1;
-                    HIPCHK(launch_slot(c, GS_COEF, update_coef_kernel, dim3(nt, nd), dim3(64), c->stream, pa, bx,
-                                       c->par.polar_damp, dl, v.ntld, v.C));
+                    MPMC_THOLE_DISPATCH(c, HIPCHK(launch_slot(c, GS_COEF, update_coef_kernel<kM>, dim3(nt, nd), dim3(64), c->stream,
+                                                              pa, bx, tp, dl, v.ntld, v.C)));
                 }
             } else if (nd > 0) {
                 if (c->call.moves_deferred && &v == &c->view[0] && apply_deferred_moves(c)) return -1;
-                HIPCHK(launch_slot(c, GS_COEF, update_coef_kernel, dim3(nt, nd), dim3(64), c->stream, pa, bx,
-                                   c->par.polar_damp, dl, v.ntld, v.C));
+                MPMC_THOLE_DISPATCH(c, HIPCHK(launch_slot(c, GS_COEF, update_coef_kernel<kM>, dim3(nt, nd), dim3(64), c->stream, pa,
+                                                          bx, tp, dl, v.ntld, v.C)));
             }
             if (c->call.moves_deferred && &v == &c->view[0] && apply_deferred_moves(c)) return -1;  // (nd == 0: nothing fused)
             coef_updated = true;
         } else {
             if (c->call.moves_deferred && &v == &c->view[0] && apply_deferred_moves(c)) return -1;
-            hipLaunchKernelGGL(build_coef_kernel, dim3(nt, nt), dim3(64 * kCoefWaves), 0, st, pa, bx,
-                               c->par.polar_damp, v.ntld, v.C, 0);
+            MPMC_THOLE_DISPATCH(c, hipLaunchKernelGGL((build_coef_kernel<kM>), dim3(nt, nt), dim3(64 * kCoefWaves), 0, st, pa, bx,
+                                                      tp, v.ntld, v.C, 0));
             v.C_valid = true;
             ++v.C_epoch;
         }
@@ -422,11 +428,11 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
         if (ensure_view_matrix(v)) return -1;
         if (can_update && v.A_valid) {
             if (nd > 0)
-                hipLaunchKernelGGL(update_amatrix_kernel, dim3(v.nvpad / 128, nd), dim3(64), 0, st, pa, bx,
-                                   c->par.polar_damp, dl, v.A, 3 * v.nvpad);
+                MPMC_THOLE_DISPATCH(c, hipLaunchKernelGGL((update_amatrix_kernel<kM>), dim3(v.nvpad / 128, nd), dim3(64), 0, st, pa,
+                                                          bx, tp, dl, v.A, 3 * v.nvpad));
         } else {
-            hipLaunchKernelGGL(build_amatrix_kernel, dim3(v.nvpad / 128, v.nvpad / kARows), dim3(64), 0, st, pa, bx,
-                               c->par.polar_damp, v.A, 3 * v.nvpad);
+            MPMC_THOLE_DISPATCH(c, hipLaunchKernelGGL((build_amatrix_kernel<kM>), dim3(v.nvpad / 128, v.nvpad / kARows), dim3(64), 0,
+                                                      st, pa, bx, tp, v.A, 3 * v.nvpad));
             v.A_valid = true;
         }
     } else {

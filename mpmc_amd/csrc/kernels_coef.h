@@ -96,7 +96,8 @@ __device__ __forceinline__ double2 stream_load_coef(const double2 *p) {
 // ---------------------------------------------------------------------------------------------
 // (tj_min > 0: only the tiles whose column block is >= tj_min -- the tail of a view whose order changed from that
 // block on; the tiles in front of it involve unchanged atoms only)
-__global__ __launch_bounds__(64 * kCoefWaves) void build_coef_kernel(DevAtoms a, DevBox bx, double damp, int ntld,
+template <int MODEL>
+__global__ __launch_bounds__(64 * kCoefWaves) void build_coef_kernel(DevAtoms a, DevBox bx, TholeParams tp, int ntld,
                                                                        double2 *__restrict__ C, int tj_min) {
     const int tj = blockIdx.x, ti = blockIdx.y;
     if (tj < ti || tj < tj_min) return;
@@ -116,8 +117,12 @@ __global__ __launch_bounds__(64 * kCoefWaves) void build_coef_kernel(DevAtoms a,
     for (int s = kCoefSteps * w; s < kCoefSteps * (w + 1); ++s) {
         const int jj = (l + s) & 63;
         double c3 = 0.0, c5 = 0.0, dx, dy, dz;
-        if (vi && sv[jj] && !(ti == tj && s == 0))
-            thole_coef(bx, damp, xi - sx[jj], yi - sy[jj], zi - sz[jj], c3, c5, dx, dy, dz);
+        if (vi && sv[jj] && !(ti == tj && s == 0)) {
+            double aa;
+            bool excl;
+            thole_pair<MODEL>(a, tp, 64 * ti + l, 64 * tj + jj, aa, excl);
+            thole_coef<MODEL>(bx, tp, aa, excl, xi - sx[jj], yi - sy[jj], zi - sz[jj], c3, c5, dx, dy, dz);
+        }
         tile[s * 64 + l] = make_double2(c3, c5);
     }
 }
@@ -126,7 +131,8 @@ __global__ __launch_bounds__(64 * kCoefWaves) void build_coef_kernel(DevAtoms a,
 // grid = (nt, ndirty); block = 64: thread = partner k of dirty slot a.  A pair of two moved atoms is
 // written by both (same value).  Same function of the same coordinates as the full build, hence
 // bit-identical to it.
-__global__ __launch_bounds__(64) void update_coef_kernel(DevAtoms a, DevBox bx, double damp, DirtyList dirty, int ntld,
+template <int MODEL>
+__global__ __launch_bounds__(64) void update_coef_kernel(DevAtoms a, DevBox bx, TholeParams tp, DirtyList dirty, int ntld,
                                                           double2 *__restrict__ C) {
     const int sa = dirty.slot[blockIdx.y];
     const int k = blockIdx.x * 64 + threadIdx.x;
@@ -137,8 +143,12 @@ __global__ __launch_bounds__(64) void update_coef_kernel(DevAtoms a, DevBox bx, 
     const bool a_is_row = (ta < tk) || (ta == tk);
     const int i = a_is_row ? sa : k, j = a_is_row ? k : sa;
     double c3 = 0.0, c5 = 0.0, dx, dy, dz;
-    if ((a.flags[i] & kValid) && (a.flags[j] & kValid))
-        thole_coef(bx, damp, a.x[i] - a.x[j], a.y[i] - a.y[j], a.z[i] - a.z[j], c3, c5, dx, dy, dz);
+    if ((a.flags[i] & kValid) && (a.flags[j] & kValid)) {
+        double aa;
+        bool excl;
+        thole_pair<MODEL>(a, tp, i, j, aa, excl);
+        thole_coef<MODEL>(bx, tp, aa, excl, a.x[i] - a.x[j], a.y[i] - a.y[j], a.z[i] - a.z[j], c3, c5, dx, dy, dz);
+    }
     const double2 v = make_double2(c3, c5);
     const size_t tsz = kCoefTile * kCoefTile;
     if (ta < tk) {
@@ -165,8 +175,9 @@ struct DirtyMoves {
 };
 // (bxi, byi: what blockIdx.x / blockIdx.y are in update_coef_moves_kernel's own grid (nt, dm.n); t64: the thread within
 //  its 64; writer: the one unit that stores the moved coordinates)
+template <int MODEL>
 __device__ __forceinline__ void update_coef_moves_body(int bxi, int byi, int t64, bool writer, const DevAtoms &a,
-                                                       const DevBox &bx, double damp, const DirtyMoves &dm, int ntld,
+                                                       const DevBox &bx, const TholeParams &tp, const DirtyMoves &dm, int ntld,
                                                        double2 *__restrict__ C, const MoveList &m, double *__restrict__ gx,
                                                        double *__restrict__ gy, double *__restrict__ gz,
                                                        const int *__restrict__ slot_of_atom, double *px, double *py,
@@ -200,8 +211,11 @@ __device__ __forceinline__ void update_coef_moves_body(int bxi, int byi, int t64
     const int i = a_is_row ? sa : k, j = a_is_row ? k : sa;
     double c3 = 0.0, c5 = 0.0, dx, dy, dz;
     if ((a.flags[i] & kValid) && (a.flags[j] & kValid)) {
-        if (a_is_row) thole_coef(bx, damp, xa - xk, ya - yk, za - zk, c3, c5, dx, dy, dz);
-        else thole_coef(bx, damp, xk - xa, yk - ya, zk - za, c3, c5, dx, dy, dz);
+        double aa;
+        bool excl;
+        thole_pair<MODEL>(a, tp, i, j, aa, excl);
+        if (a_is_row) thole_coef<MODEL>(bx, tp, aa, excl, xa - xk, ya - yk, za - zk, c3, c5, dx, dy, dz);
+        else thole_coef<MODEL>(bx, tp, aa, excl, xk - xa, yk - ya, zk - za, c3, c5, dx, dy, dz);
     }
     const double2 v = make_double2(c3, c5);
     const size_t tsz = kCoefTile * kCoefTile;
@@ -216,14 +230,15 @@ __device__ __forceinline__ void update_coef_moves_body(int bxi, int byi, int t64
     }
 }
 
-__global__ __launch_bounds__(64) void update_coef_moves_kernel(DevAtoms a, DevBox bx, double damp, DirtyMoves dm, int ntld,
+template <int MODEL>
+__global__ __launch_bounds__(64) void update_coef_moves_kernel(DevAtoms a, DevBox bx, TholeParams tp, DirtyMoves dm, int ntld,
                                                                 double2 *__restrict__ C, MoveList m,
                                                                 double *__restrict__ gx, double *__restrict__ gy,
                                                                 double *__restrict__ gz,
                                                                 const int *__restrict__ slot_of_atom, double *px, double *py,
                                                                 double *pz) {
-    update_coef_moves_body(blockIdx.x, blockIdx.y, threadIdx.x, blockIdx.x == 0 && blockIdx.y == 0, a, bx, damp, dm, ntld, C,
-                           m, gx, gy, gz, slot_of_atom, px, py, pz);
+    update_coef_moves_body<MODEL>(blockIdx.x, blockIdx.y, threadIdx.x, blockIdx.x == 0 && blockIdx.y == 0, a, bx, tp, dm, ntld,
+                                  C, m, gx, gy, gz, slot_of_atom, px, py, pz);
 }
 
 // The move, the coefficient update AND the incremental static-field pass of a steady-state step as ONE launch: the two
@@ -235,7 +250,7 @@ __global__ __launch_bounds__(64) void update_coef_moves_kernel(DevAtoms a, DevBo
 // functions of the same coordinates => same bits as the two launches.
 struct CoefJob {
     DevAtoms pa;   // the view's atoms (update_coef_moves_kernel's `a`)
-    double damp;
+    TholeParams tp;
     DirtyMoves dm;
     int nt, ntld;
     double2 *C;
@@ -244,15 +259,15 @@ struct CoefJob {
     const int *slot_of_atom;
     double *px, *py, *pz;
 };
-template <int MODE>
+template <int MODE, int MODEL>
 __global__ __launch_bounds__(64 * kFieldWaves) void field_coef_kernel(DevAtoms a, DevBox bx, FieldParams fp, DirtyBlocks sel,
                                                                        double *__restrict__ part, CoefJob cj) {
     if (blockIdx.z == 2) {
         const int u = ((int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x) * kFieldWaves + ((int)threadIdx.x >> 6);
         const int bxi = u % cj.nt, byi = u / cj.nt;
         if (byi < cj.dm.n)
-            update_coef_moves_body(bxi, byi, threadIdx.x & 63, u == 0, cj.pa, bx, cj.damp, cj.dm, cj.ntld, cj.C, cj.m, cj.gx,
-                                   cj.gy, cj.gz, cj.slot_of_atom, cj.px, cj.py, cj.pz);
+            update_coef_moves_body<MODEL>(bxi, byi, threadIdx.x & 63, u == 0, cj.pa, bx, cj.tp, cj.dm, cj.ntld, cj.C, cj.m, cj.gx,
+                                          cj.gy, cj.gz, cj.slot_of_atom, cj.px, cj.py, cj.pz);
         return;
     }
     static_field_body<MODE>(a, bx, fp, sel, part, cj.m);

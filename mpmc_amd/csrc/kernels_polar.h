@@ -278,34 +278,95 @@ __global__ __launch_bounds__(64 * kFieldGroups) void field_reduce_kernel(const d
 // ---------------------------------------------------------------------------------------------
 constexpr int kARows = 16;
 
+// The dipole tensors of the reference's thole_amatrix() (thole_matrix.c:90-135).  All have the shape
+// T = c3 I - 3 c5 d d^T; the model decides c3 and c5:
+//   kTholeExp      polar_damp_type exponential: damp1 = 1 - e^{-lr}(l^2r^2/2 + lr + 1), damp2 = damp1 - e^{-lr} l^3r^3/6
+//   kTholeLinear   polar_damp_type linear (Thole's original): s = l (alpha_i alpha_j)^{1/6}, v = r/s; r < s: damp1 =
+//                  (4 - 3v) v^3, damp2 = v^4; else both 1 (alpha = 0 gives s = 0: no damping)
+//   kTholeOff      polar_damp_type off / none (Applequist): both 1, but 0 for an es_excluded pair (pairs.c:61-77: same
+//                  molecule, or either charge exactly 0.0 -- the reference's quirk, kept)
+//   kTholeExpWolf  exponential + polar_wolf_full: c3 = damp1/r^3 - wdamp1/rc^3, c5 = damp2/r^5 - wdamp2/(r^2 rc^3) for EVERY
+//                  pair (the reference has no r < rc test and the A matrix no cutoff); wdamp = damp at r = rc
+enum TholeModel { kTholeExp = 0, kTholeLinear = 1, kTholeOff = 2, kTholeExpWolf = 3 };
+
+struct TholeParams {
+    double damp;            // polar_damp
+    double rc;              // the box cutoff
+    double irc3;            // rc^-3
+    double wdamp1, wdamp2;  // the Wolf constants, formed once per box on the host (0 outside kTholeExpWolf)
+    const int *idx;         // kTholeOff: atom of slot k when the kernel's atom set is a sweep view (q and mol stay in
+                            // atom order); nullptr = the slots are the atoms
+};
+
+// What the models beside the exponential ones read of a pair's two atoms (slots i, j of the kernel's atom set):
+// aa = alpha_i alpha_j (linear), excl = es_excluded (off).
+template <int MODEL>
+__device__ __forceinline__ void thole_pair(const DevAtoms &a, const TholeParams &tp, int i, int j, double &aa, bool &excl) {
+    aa = 0.0;
+    excl = false;
+    if (MODEL == kTholeLinear) aa = a.alpha[i] * a.alpha[j];
+    if (MODEL == kTholeOff) {
+        const int ai = tp.idx ? tp.idx[i] : i, aj = tp.idx ? tp.idx[j] : j;
+        excl = (a.mol[ai] == a.mol[aj]) || (a.q[ai] == 0.0) || (a.q[aj] == 0.0);
+    }
+}
+
 // Radial coefficients of the damped dipole tensor T = c3 I - 3 c5 d d^T (thole_matrix.c:72-137) and the
 // minimum-image displacement d they belong to.
-__device__ __forceinline__ void thole_coef(const DevBox &bx, double damp, double dx0, double dy0, double dz0,
-                                           double &c3, double &c5, double &dx, double &dy, double &dz) {
+template <int MODEL>
+__device__ __forceinline__ void thole_coef(const DevBox &bx, const TholeParams &tp, double aa, bool excl, double dx0,
+                                           double dy0, double dz0, double &c3, double &c5, double &dx, double &dy,
+                                           double &dz) {
     double r, rimg;
     minimum_image(bx, dx0, dy0, dz0, r, rimg, dx, dy, dz);
-    double ir3, ir5;
+    double ir3, ir5, ir2 = 0.0;
     if (rimg == 0.0) {
         ir3 = ir5 = kMAXVALUE;  // thole_matrix.c:81-82
     } else {
         const double ir = 1.0 / rimg;
         ir3 = ir * ir * ir;
         ir5 = ir3 * ir * ir;
+        if (MODEL == kTholeExpWolf) ir2 = ir * ir;
     }
-    const double l = damp, l2 = l * l, l3 = l2 * l;
-    const double r2 = rimg * rimg;
-    const double explr = exp(-l * rimg);
-    const double damp1 = 1.0 - explr * (0.5 * l2 * r2 + l * rimg + 1.0);
-    const double damp2 = damp1 - explr * (l3 * r2 * rimg / 6.0);
-    c5 = damp2 * ir5;
-    c3 = damp1 * ir3;
+    if (MODEL == kTholeExp || MODEL == kTholeExpWolf) {
+        const double l = tp.damp, l2 = l * l, l3 = l2 * l;
+        const double r2 = rimg * rimg;
+        const double explr = exp(-l * rimg);
+        const double damp1 = 1.0 - explr * (0.5 * l2 * r2 + l * rimg + 1.0);
+        const double damp2 = damp1 - explr * (l3 * r2 * rimg / 6.0);
+        c5 = damp2 * ir5;
+        c3 = damp1 * ir3;
+        if (MODEL == kTholeExpWolf) {
+            // (rimg = 0: d = 0, so the dyad term is 0 whatever c5 is; the reference reads a stale 1/r there, times 0 --
+            //  the Wolf part of c5 is taken as 0)
+            c5 -= (tp.wdamp2 * ir2) * tp.irc3;
+            c3 -= tp.wdamp1 * tp.irc3;
+        }
+    } else if (MODEL == kTholeLinear) {
+        // Both factors are continuous at r = s ((4 - 3) 1 = 1, 1^4 = 1): where this pow() and the reference's libm
+        // round s to different sides of r, the branch taken differs but the coefficients differ by rounding only.
+        const double s = tp.damp * pow(aa, 1.0 / 6.0);
+        const double v = rimg / s;
+        double damp1 = 1.0, damp2 = 1.0;
+        if (rimg < s) {
+            damp1 = (4.0 - 3.0 * v) * v * v * v;
+            damp2 = v * v * v * v;
+        }
+        c5 = damp2 * ir5;
+        c3 = damp1 * ir3;
+    } else {
+        const double damp = excl ? 0.0 : 1.0;
+        c5 = damp * ir5;
+        c3 = damp * ir3;
+    }
 }
 
-__device__ __forceinline__ void thole_tensor(const DevBox &bx, double damp, double dx0, double dy0, double dz0,
-                                             double &xx, double &xy, double &xz, double &yy, double &yz,
-                                             double &zz) {
+template <int MODEL>
+__device__ __forceinline__ void thole_tensor(const DevBox &bx, const TholeParams &tp, double aa, bool excl, double dx0,
+                                             double dy0, double dz0, double &xx, double &xy, double &xz, double &yy,
+                                             double &yz, double &zz) {
     double c3, c5, dx, dy, dz;
-    thole_coef(bx, damp, dx0, dy0, dz0, c3, c5, dx, dy, dz);
+    thole_coef<MODEL>(bx, tp, aa, excl, dx0, dy0, dz0, c3, c5, dx, dy, dz);
     xx = -3.0 * dx * dx * c5 + c3;
     xy = -3.0 * dx * dy * c5;
     xz = -3.0 * dx * dz * c5;
@@ -314,7 +375,19 @@ __device__ __forceinline__ void thole_tensor(const DevBox &bx, double damp, doub
     zz = -3.0 * dz * dz * c5 + c3;
 }
 
-__global__ __launch_bounds__(64) void build_amatrix_kernel(DevAtoms a, DevBox bx, double damp,
+// the exponential tensor from polar_damp alone (kernels_vdw.h: e2body() / calc_e_iso() are written for that form)
+__device__ __forceinline__ void thole_tensor(const DevBox &bx, double damp, double dx0, double dy0, double dz0,
+                                             double &xx, double &xy, double &xz, double &yy, double &yz,
+                                             double &zz) {
+    TholeParams tp;
+    tp.damp = damp;
+    tp.rc = tp.irc3 = tp.wdamp1 = tp.wdamp2 = 0.0;
+    tp.idx = nullptr;
+    thole_tensor<kTholeExp>(bx, tp, 0.0, false, dx0, dy0, dz0, xx, xy, xz, yy, yz, zz);
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(64) void build_amatrix_kernel(DevAtoms a, DevBox bx, TholeParams tp,
                                                             double *__restrict__ A, int lda) {
     const int lane = threadIdx.x;
     const int j0 = blockIdx.x * 128 + 2 * lane;
@@ -345,16 +418,22 @@ __global__ __launch_bounds__(64) void build_amatrix_kernel(DevAtoms a, DevBox bx
             if (j0 == i) {
                 t0[0] = t0[3] = t0[5] = dg;
             } else {
-                thole_tensor(bx, damp, sx[k] - xj.x, sy[k] - yj.x, sz[k] - zj.x, t0[0], t0[1], t0[2], t0[3], t0[4],
-                             t0[5]);
+                double aa;
+                bool excl;
+                thole_pair<MODEL>(a, tp, i, j0, aa, excl);
+                thole_tensor<MODEL>(bx, tp, aa, excl, sx[k] - xj.x, sy[k] - yj.x, sz[k] - zj.x, t0[0], t0[1], t0[2], t0[3],
+                                    t0[4], t0[5]);
             }
         }
         if (vi && (flj.y & kValid)) {
             if (j0 + 1 == i) {
                 t1[0] = t1[3] = t1[5] = dg;
             } else {
-                thole_tensor(bx, damp, sx[k] - xj.y, sy[k] - yj.y, sz[k] - zj.y, t1[0], t1[1], t1[2], t1[3], t1[4],
-                             t1[5]);
+                double aa;
+                bool excl;
+                thole_pair<MODEL>(a, tp, i, j0 + 1, aa, excl);
+                thole_tensor<MODEL>(bx, tp, aa, excl, sx[k] - xj.y, sy[k] - yj.y, sz[k] - zj.y, t1[0], t1[1], t1[2], t1[3],
+                                    t1[4], t1[5]);
             }
         }
         // t = {xx, xy, xz, yy, yz, zz}
@@ -460,7 +539,8 @@ struct DirtyList {  // passed by value in the kernel arguments: no H2D copy on t
     int slot[64];
 };
 
-__global__ __launch_bounds__(64) void update_amatrix_kernel(DevAtoms a, DevBox bx, double damp, DirtyList dirty,
+template <int MODEL>
+__global__ __launch_bounds__(64) void update_amatrix_kernel(DevAtoms a, DevBox bx, TholeParams tp, DirtyList dirty,
                                                              double *__restrict__ A, int lda) {
     const int lane = threadIdx.x;
     const int j0 = blockIdx.x * 128 + 2 * lane;
@@ -478,14 +558,22 @@ __global__ __launch_bounds__(64) void update_amatrix_kernel(DevAtoms a, DevBox b
     if (vi && (flj.x & kValid)) {
         if (j0 == i)
             t0[0] = t0[3] = t0[5] = dg;
-        else
-            thole_tensor(bx, damp, xi - xj.x, yi - yj.x, zi - zj.x, t0[0], t0[1], t0[2], t0[3], t0[4], t0[5]);
+        else {
+            double aa;
+            bool excl;
+            thole_pair<MODEL>(a, tp, i, j0, aa, excl);
+            thole_tensor<MODEL>(bx, tp, aa, excl, xi - xj.x, yi - yj.x, zi - zj.x, t0[0], t0[1], t0[2], t0[3], t0[4], t0[5]);
+        }
     }
     if (vi && (flj.y & kValid)) {
         if (j0 + 1 == i)
             t1[0] = t1[3] = t1[5] = dg;
-        else
-            thole_tensor(bx, damp, xi - xj.y, yi - yj.y, zi - zj.y, t1[0], t1[1], t1[2], t1[3], t1[4], t1[5]);
+        else {
+            double aa;
+            bool excl;
+            thole_pair<MODEL>(a, tp, i, j0 + 1, aa, excl);
+            thole_tensor<MODEL>(bx, tp, aa, excl, xi - xj.y, yi - yj.y, zi - zj.y, t1[0], t1[1], t1[2], t1[3], t1[4], t1[5]);
+        }
     }
     // block-row i (coalesced 16-byte stores, as in the full build)
     double *r0 = A + (size_t)(3 * i) * lda + 3 * (size_t)j0;

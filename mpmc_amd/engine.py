@@ -21,7 +21,7 @@ EXPORTS = [
     "mpmc_hip_set_autoreject", "mpmc_hip_get_close_contacts",
     "mpmc_hip_set_cavity_grid", "mpmc_hip_cavity_bin", "mpmc_hip_cavity_update", "mpmc_hip_cavity_point",
     "mpmc_hip_download_cavity_grid",
-    "mpmc_hip_set_exact_polar", "mpmc_hip_get_polarizability_tensor",
+    "mpmc_hip_set_exact_polar", "mpmc_hip_get_polarizability_tensor", "mpmc_hip_set_thole_model",
     "mpmc_hip_update_atoms", "mpmc_hip_insert_molecule", "mpmc_hip_remove_molecule",
     "mpmc_hip_slot_count", "mpmc_hip_set_sweep_order", "mpmc_hip_energy", "mpmc_hip_energy_begin", "mpmc_hip_energy_end",
     "mpmc_hip_download_dipoles",
@@ -124,6 +124,15 @@ class RdFormParams(C.Structure):
     ]
 
 
+class TholeModel(C.Structure):
+    """mpmc_hip_thole_model: the dipole tensor of the A matrix (mpmc_hip_set_thole_model)."""
+    _fields_ = [
+        ("damp_type", C.c_int),
+        ("wolf_full", C.c_int),
+    ]
+
+
+THOLE_DAMPINGS = {"off": 0, "none": 0, "linear": 1, "exponential": 2}  # the reference's DAMPING_* values
 RD_FORMS = {"off": 0, "lj": 1, "sg": 2, "dreiding": 3, "lj_buffered_14_7": 4}  # MPMC_HIP_RD_*
 RD_MIXINGS = {"lb": 0, "waldmanhagler": 1, "halgren_mixing": 2, "c6_mixing": 3}  # MPMC_HIP_RD_MIX_*
 PARAM_NAMES = [f[0] for f in Params._fields_]
@@ -134,10 +143,12 @@ RDFORM_NAMES = ["sg", "dreiding", "lj_buffered_14_7", "waldmanhagler", "halgren_
 VDW_NAMES = ["polarvdw", "cdvdw"]  # mpmc_hip_set_vdw (reference keywords)
 AUTOREJECT_NAMES = ["cavity_autoreject_absolute", "cavity_autoreject_scale"]  # mpmc_hip_set_autoreject (reference keywords)
 EXACT_NAMES = ["polar_iterative"]  # mpmc_hip_set_exact_polar (reference keyword; 0 = the exact dipoles)
+THOLE_NAMES = ["polar_damp_type", "polar_wolf_full"]  # mpmc_hip_set_thole_model (reference keywords)
 VDW_TERMS = ["e_total", "e_iso", "lr_corr", "repulsion", "repulsion_lrc"]  # mpmc_hip_get_vdw_terms, in its order
 # flags that make_params() leaves to others: pbc_cutoff is a box property at this boundary (set_box), the rest are the
 # arguments of the calls above (Engine.load_system)
-NOT_PARAMS = frozenset(["pbc_cutoff"] + DISP_NAMES + AT_NAMES + RDC_NAMES + RDFORM_NAMES + VDW_NAMES + AUTOREJECT_NAMES + EXACT_NAMES)
+NOT_PARAMS = frozenset(["pbc_cutoff"] + DISP_NAMES + AT_NAMES + RDC_NAMES + RDFORM_NAMES + VDW_NAMES + AUTOREJECT_NAMES + EXACT_NAMES
+                       + THOLE_NAMES)
 AT_ALPHA_AU = 6.7483345  # A^3 -> Bohr^3, as the reference writes it (axilrod_teller.cpp:115)
 
 _lib = None
@@ -178,6 +189,7 @@ def load():
     lib.mpmc_hip_get_vdw_terms.argtypes = [vp, dp]
     lib.mpmc_hip_set_exact_polar.argtypes = [vp, C.c_int]
     lib.mpmc_hip_get_polarizability_tensor.argtypes = [vp, dp]
+    lib.mpmc_hip_set_thole_model.argtypes = [vp, C.POINTER(TholeModel)]
     lib.mpmc_hip_set_autoreject.argtypes = [vp, C.c_double]
     lib.mpmc_hip_get_close_contacts.argtypes = [vp, C.POINTER(C.c_longlong)]
     ip = C.POINTER(C.c_int)
@@ -380,6 +392,18 @@ class Engine:
         uploads."""
         _chk(self.lib.mpmc_hip_set_exact_polar(self.ctx, int(bool(enable))))
 
+    def set_thole_model(self, damping="exponential", wolf_full=False):
+        """The dipole tensor of the A matrix (mpmc_hip_set_thole_model): damping "exponential" (the default), "linear"
+        (Thole's original model) or "off" / "none" (undamped; es_excluded pairs do not couple), as the reference's
+        polar_damp_type; wolf_full = its polar_wolf_full (exponential only).  A context setting: it persists across
+        uploads."""
+        if isinstance(damping, str):
+            if damping.lower() not in THOLE_DAMPINGS:
+                raise ValueError("set_thole_model: damping %r is none of %s" % (damping, sorted(THOLE_DAMPINGS)))
+            damping = THOLE_DAMPINGS[damping.lower()]
+        m = TholeModel(int(damping), int(bool(wolf_full)))
+        _chk(self.lib.mpmc_hip_set_thole_model(self.ctx, C.byref(m)))
+
     def polarizability_tensor(self):
         """The 3 x 3 molecular polarizability tensor (A^3) of the last completed energy() in the exact mode
         (mpmc_hip_get_polarizability_tensor; the reference's polarizability_tensor on)."""
@@ -457,7 +481,9 @@ class Engine:
         polar_iterative = 0 together with polarization switches the exact dipoles on; anything else switches them off.
         sg / dreiding / lj_buffered_14_7 switch that pair potential on (set_rd_form), waldmanhagler / halgren_mixing /
         c6_mixing name its mixing rule and, without another form, switch the dense Lennard-Jones form on; without any of
-        the six the standard path is restored."""
+        the six the standard path is restored.  polar_damp_type ("exponential" | "linear" | "off" | "none") and
+        polar_wolf_full name the dipole tensor (set_thole_model); without them the default, exponential, is restored."""
+        self.set_thole_model(params.get("polar_damp_type", "exponential"), bool(params.get("polar_wolf_full")))
         self.set_exact_polar("polar_iterative" in params and not params["polar_iterative"]
                              and bool(params.get("polarization")))
         self.set_params(**params)

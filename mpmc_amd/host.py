@@ -96,6 +96,8 @@ def load():
     lib.host_get_rdc_flags.restype = None
     lib.host_get_rdform_flags.argtypes = [vp, vp]
     lib.host_get_rdform_flags.restype = None
+    lib.host_get_thole_flags.argtypes = [vp, vp]
+    lib.host_get_thole_flags.restype = None
     lib.host_read_frame.argtypes = [vp, C.c_char_p, C.c_int]
     lib.host_unsupported.argtypes = [vp]
     lib.host_unsupported.restype = C.c_char_p
@@ -122,11 +124,13 @@ def config_text(flags, extra=None):
              "midzuno_kihara_approx", "rd_crystal", "read_pqr_box", "calc_pressure", "polarvdw", "cdvdw",
              "cavity_autoreject_absolute", "cavity_bias", "cdvdw_exp_repulsion", "cdvdw_sig_repulsion",
              "cdvdw_9th_repulsion", "sg", "dreiding", "lj_buffered_14_7", "waldmanhagler", "halgren_mixing", "c6_mixing",
-             "polar_iterative", "polarizability_tensor"}
+             "polar_iterative", "polarizability_tensor", "polar_wolf_full"}
     lines = []
     for k, v in flags.items():
         if k in ("polarvdw", "cdvdw") and isinstance(v, str):
             lines.append("%s %s" % (k, v))  # evects / comp
+        elif k == "polar_damp_type":
+            lines.append("%s %s" % (k, v))  # a bare word: exponential | linear | off | none
         elif k in onoff:
             lines.append("%s %s" % (k, "on" if v else "off"))
         elif k in ("ewald_alpha_set", "polar_ewald_alpha_set"):
@@ -134,7 +138,8 @@ def config_text(flags, extra=None):
         else:
             lines.append("%s %r" % (k, v))
     if flags.get("polarization"):
-        lines.append("polar_damp_type exponential")
+        if "polar_damp_type" not in flags:
+            lines.append("polar_damp_type exponential")
         if "polar_iterative" not in flags:  # (polar_iterative=0: the exact dipoles)
             lines.append("polar_iterative on")
     for k, v in (extra or {}).items():

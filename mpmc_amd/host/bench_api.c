@@ -11,6 +11,7 @@ int host_apply_config(system_t *system, const char *text) {
     char line[MAXLINE], tok[10][MAXLINE], *token[10];
     for (int i = 0; i < 10; i++) token[i] = tok[i];
     system->polar_iterative = 1; /* a system built from arrays iterates unless the text says `polar_iterative off` */
+    system->damp_type = DAMPING_EXPONENTIAL; /* ... and has the exponential tensor unless the text names another */
     const char *p = text;
     while (*p) {
         size_t len = strcspn(p, "\n");
@@ -311,6 +312,12 @@ void host_get_rdform_flags(system_t *system, int out[6]) {
     out[3] = system->waldmanhagler;
     out[4] = system->halgren_mixing;
     out[5] = system->c6_mixing;
+}
+/* the dipole tensor's keywords as read: damp_type (DAMPING_OFF / _LINEAR / _EXPONENTIAL), polar_wolf_full, polar_ewald_full */
+void host_get_thole_flags(system_t *system, int out[3]) {
+    out[0] = system->damp_type;
+    out[1] = system->polar_wolf_full;
+    out[2] = system->polar_ewald_full;
 }
 /* frame `index` (from 0) of the PQR trajectory `path` becomes the system's configuration, read the way
  * replay_trajectory() reads it: every frame in front of it is read (and freed) first, so the box and the cutoff are

@@ -58,6 +58,7 @@ typedef struct shim_state {
     int rdc_order; /* rd_crystal_order as sent with that upload (0: rd_crystal off) */
     mpmc_hip_rd_form_params rd_form; /* the pair potential and mixing rule as sent with that upload */
     int vdw_on;    /* polarvdw as sent with that upload */
+    mpmc_hip_thole_model thole; /* the dipole tensor (polar_damp_type, polar_wolf_full) as sent with that upload */
     int exact;     /* the exact dipoles (polarization with polar_iterative off) as sent with that upload */
     double ar_scale; /* cavity_autoreject_scale as sent with that upload (0: cavity_autoreject_absolute off) */
     int failed;   /* device / ABI failure of the last call */
@@ -267,6 +268,14 @@ static void fill_rd_form(const system_t *s, mpmc_hip_rd_form_params *f) {
     if (!f->form) f->mixing = 0;
 }
 
+/* thole_matrix.c:90-135: the tensor of the A matrix.  Without polarization the engine keeps its default (the matrix of
+ * polarvdw is the exponential one: unsupported() refuses the others there). */
+static void fill_thole_model(const system_t *s, mpmc_hip_thole_model *m) {
+    memset(m, 0, sizeof(*m));
+    m->damp_type = s->polarization ? s->damp_type : DAMPING_EXPONENTIAL;
+    m->wolf_full = (s->polarization && s->polar_wolf_full) ? 1 : 0;
+}
+
 static void fill_disp_params(const system_t *s, mpmc_hip_disp_params *d) {
     memset(d, 0, sizeof(*d));
     d->disp_expansion = s->disp_expansion;
@@ -292,10 +301,15 @@ static const char *unsupported(const system_t *s) {
     if (s->ensemble == ENSEMBLE_SURF && (s->sg || s->dreiding || s->lj_buffered_14_7 || s->waldmanhagler || s->halgren_mixing ||
                                          s->c6_mixing))
         return "ensemble surf with sg / dreiding / lj_buffered_14_7 or a mixing rule is not on the device";
-    if (s->polarization && s->damp_type != DAMPING_EXPONENTIAL) return "exponential Thole damping only";
-    if (s->polarization && (s->polar_ewald_full || s->polar_wolf_full)) return "polar_ewald_full / polar_wolf_full are not on the device";
     if (s->ensemble == ENSEMBLE_NVE) return "ensemble nve is not supported";
 #endif
+    /* the linear and the undamped tensor and polar_wolf_full are on the device (mpmc_hip_set_thole_model); the reference's
+     * polar_ewald_full applies one k-component to all three field components (polar_ewald.c:267-268): nothing to match */
+    if (s->polarization && s->polar_ewald_full) return "polar_ewald_full is not on the device";
+    if (s->polarization && s->polar_wolf_full && s->damp_type != DAMPING_EXPONENTIAL)
+        return "polar_wolf_full needs polar_damp_type exponential";
+    if (s->polarvdw && (s->damp_type != DAMPING_EXPONENTIAL || s->polar_wolf_full))
+        return "polarvdw with polar_damp_type linear / off or polar_wolf_full is not on the device";
     /* sg, dreiding, lj_buffered_14_7 and the Lennard-Jones mixing rules are on the device (mpmc_hip_set_rd_form); the
      * combinations it does not have are refused by name */
     {
@@ -475,6 +489,9 @@ static int full_upload(shim_state *st, system_t *system) {
     /* (in front of the parameters: the exact mode takes a set with neither polar_max_iter nor polar_precision) */
     st->exact = (system->polarization && !system->polar_iterative);
     if (mpmc_hip_set_exact_polar(st->ctx, st->exact)) return hip_fail("set_exact_polar");
+    /* (likewise: under polar_damp_type off the engine takes a set without polar_damp) */
+    fill_thole_model(system, &st->thole);
+    if (mpmc_hip_set_thole_model(st->ctx, &st->thole)) return hip_fail("set_thole_model");
     int rc = mpmc_hip_set_params(st->ctx, &st->params);
     if (!rc) rc = mpmc_hip_set_box(st->ctx, basis, system->pbc->cutoff);
     if (!rc) rc = mpmc_hip_upload(st->ctx, n, st->x, st->y, st->z, st->q, st->alpha, st->eps, st->sig, st->mass, mol, fz);
@@ -1069,6 +1086,9 @@ int energy_hip_begin(system_t *system) {
         if (memcmp(&fnow, &st->rd_form, sizeof(fnow))) need_upload = 1;
         if ((system->polarvdw != 0) != st->vdw_on) need_upload = 1;
         if ((system->polarization && !system->polar_iterative) != st->exact) need_upload = 1;
+        mpmc_hip_thole_model tnow;
+        fill_thole_model(system, &tnow);
+        if (memcmp(&tnow, &st->thole, sizeof(tnow))) need_upload = 1;
         if ((system->cavity_autoreject_absolute ? system->cavity_autoreject_scale : 0.0) != st->ar_scale) need_upload = 1;
     }
     if (!need_upload && scale_box) {

@@ -236,13 +236,19 @@ int do_command(system_t *system, char **token) {
     REAL("polar_precision", polar_precision);
     INT("polar_max_iter", polar_max_iter);
     if (!strcasecmp(k, "polar_damp_type")) {
-        if (!strcasecmp(v, "exponential")) {
-            system->damp_type = 2; /* DAMPING_EXPONENTIAL */
-            return 0;
-        }
-        error("INPUT: the HIP engine implements exponential Thole damping only\n"); /* cf. check_input.c:329-332 */
-        return 1;
+        /* input.c:1217-1232; an absent keyword leaves DAMPING_OFF, as there */
+        if (!strcasecmp(v, "none") || !strcasecmp(v, "off"))
+            system->damp_type = DAMPING_OFF;
+        else if (!strcasecmp(v, "linear"))
+            system->damp_type = DAMPING_LINEAR;
+        else if (!strcasecmp(v, "exponential"))
+            system->damp_type = DAMPING_EXPONENTIAL;
+        else
+            return 1;
+        return 0;
     }
+    FLAG("polar_wolf_full", polar_wolf_full);   /* input.c:530-538 */
+    FLAG("polar_ewald_full", polar_ewald_full); /* input.c:508-516; refused by energy_hip.c, by name */
     FLAG("cuda", cuda);
     FLAG("hip", hip);
     TEXT("job_name", job_name);
@@ -504,8 +510,18 @@ static int check_system(system_t *system) {
             output("INPUT: Matrix polarization activated\n");
             if (system->polarizability_tensor) output("INPUT: Polarizability tensor calculation activated\n");
         }
-        if (system->damp_type != 2) {
-            error("INPUT: Thole damping method not specified (exponential only)\n");
+        if (system->polar_wolf_full) output("INPUT: Full polar wolf treatment activated.\n"); /* check_input.c:359-361 */
+        /* check_input.c:391-409 */
+        if (system->damp_type == DAMPING_LINEAR)
+            output("INPUT: Thole linear damping activated\n");
+        else if (system->damp_type == DAMPING_OFF)
+            output("INPUT: Thole linear damping is OFF\n");
+        else if (system->damp_type != DAMPING_EXPONENTIAL) {
+            error("INPUT: Thole damping method not specified\n");
+            return -1;
+        }
+        if (system->polar_damp <= 0.0 && system->damp_type != DAMPING_OFF) {
+            error("INPUT: damping factor must be specified\n");
             return -1;
         }
         if ((system->polar_precision > 0.0) && (system->polar_max_iter > 0)) { /* check_input.c:424-428 */

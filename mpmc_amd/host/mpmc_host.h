@@ -30,6 +30,7 @@ extern "C" {
 enum { ENSEMBLE_UVT, ENSEMBLE_NVT, ENSEMBLE_SURF, ENSEMBLE_SURF_FIT, ENSEMBLE_NVE, ENSEMBLE_TE, ENSEMBLE_NPT,
        ENSEMBLE_REPLAY };
 enum { MOVETYPE_INSERT, MOVETYPE_REMOVE, MOVETYPE_DISPLACE, MOVETYPE_VOLUME };
+enum { DAMPING_OFF, DAMPING_LINEAR, DAMPING_EXPONENTIAL }; /* defines.h:91-93 */
 
 typedef struct _atom {
     int id, bond_id;
@@ -120,6 +121,9 @@ typedef struct _system {
     int polarizability_tensor; /* structs.h:429: print the molecular tensor after the first energy() and leave (exact dipoles only) */
     int polarization, polar_iterative, polar_ewald, polar_zodid, polar_palmo, polar_gs, polar_gs_ranked, polar_sor,
         polar_esor, polar_max_iter, polar_wolf, polar_rrms, damp_type;
+    /* the dipole tensor beside damp_type (structs.h:432-433): polar_wolf_full is sent with mpmc_hip_set_thole_model(),
+     * polar_ewald_full is read so that energy_hip.c can refuse it by name */
+    int polar_wolf_full, polar_ewald_full;
     double polar_gamma, polar_damp, polar_precision, polar_wolf_alpha;
     /* the PHAHST family (structs.h:420-421): exp repulsion + C6 / C8 / C10 dispersion instead of Lennard-Jones; the last
      * four are read so that energy_hip.c can refuse them by name */
