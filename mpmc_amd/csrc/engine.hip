@@ -613,6 +613,12 @@ static DevAtoms dev_atoms(const mpmc_hip_ctx *c) {
     a.npad = c->npad;
     return a;
 }
+// `a` with the real epsilon / sigma whatever the mode: what the kernels of rd_crystal, set_rd_form and polarvdw read
+static DevAtoms lj_atoms(const mpmc_hip_ctx *c, DevAtoms a) {
+    a.eps = c->d_eps;
+    a.sig = c->d_sig;
+    return a;
+}
 
 static DevBox dev_box(const mpmc_hip_ctx *c) {
     DevBox b;
@@ -1268,23 +1274,31 @@ static int alloc_zero_params(mpmc_hip_ctx *c) {
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
+// What the setters of per-atom data refuse before anything else (`name`: the setter's, as its messages spell it).
+static int per_atom_setter_refused(const mpmc_hip_ctx *c, const char *name) {
+    if (c->in_flight) return fail("MPMC_HIP: %s between energy_begin() and energy_end()", name);
+    if (!c->have_atoms) return fail("MPMC_HIP: %s: no configuration uploaded", name);
+    if (c->edited) return fail("MPMC_HIP: %s: molecules were inserted or removed since the upload", name);
+    return 0;
+}
+// The Lennard-Jones kernels change between real and zero parameters: how set_dispersion() and set_vdw() end.
+static void lj_kernels_switched(mpmc_hip_ctx *c) {
+    c->pair_part_valid = c->lrc.valid = false;
+    c->all_dirty = true;
+    ++c->config_rev;
+}
 // disp_expansion (PHAHST): the resident epsilon / sigma become the exponent b and the range rho of the exponential
 // repulsion, and c6 / c8 / c10 (atomic units, upload order) arrive here.  Until the next upload the LJ kernels see zero
 // parameters and the dense kernels of kernels_disp.h form rd_energy.
 extern "C" int mpmc_hip_set_dispersion(mpmc_hip_ctx *c, const mpmc_hip_disp_params *p, int n, const double *c6,
                                        const double *c8, const double *c10) {
     if (!c || !p) return fail("MPMC_HIP: set_dispersion: null argument");
-    if (c->in_flight) return fail("MPMC_HIP: set_dispersion between energy_begin() and energy_end()");
-    if (!c->have_atoms) return fail("MPMC_HIP: set_dispersion: no configuration uploaded");
-    if (c->edited) return fail("MPMC_HIP: set_dispersion: molecules were inserted or removed since the upload");
+    if (per_atom_setter_refused(c, "set_dispersion")) return -1;
     if (n != c->n) return fail("MPMC_HIP: set_dispersion: %d coefficients for the %d atoms of the upload", n, c->n);
     HIPCHK(hipSetDevice(c->device));
     if (flush_moves(c)) return -1;  // keep the order of the caller's operations
     c->disp.valid = c->disp_lrc.valid = false;
-    c->pair_part_valid = false;  // the Lennard-Jones kernels change between real and zero parameters
-    c->lrc.valid = false;
-    c->all_dirty = true;
-    ++c->config_rev;
+    lj_kernels_switched(c);
     if (!p->disp_expansion) {
         c->disp_on = false;
         return 0;
@@ -1319,9 +1333,7 @@ extern "C" int mpmc_hip_set_dispersion(mpmc_hip_ctx *c, const mpmc_hip_disp_para
 // midzuno_kihara_approx the caller has already replaced it by 3/4 alpha 6.7483345 c6.  The polarizabilities are the upload's.
 extern "C" int mpmc_hip_set_axilrod_teller(mpmc_hip_ctx *c, int enable, int n, const double *c9) {
     if (!c) return fail("MPMC_HIP: set_axilrod_teller: null context");
-    if (c->in_flight) return fail("MPMC_HIP: set_axilrod_teller between energy_begin() and energy_end()");
-    if (!c->have_atoms) return fail("MPMC_HIP: set_axilrod_teller: no configuration uploaded");
-    if (c->edited) return fail("MPMC_HIP: set_axilrod_teller: molecules were inserted or removed since the upload");
+    if (per_atom_setter_refused(c, "set_axilrod_teller")) return -1;
     HIPCHK(hipSetDevice(c->device));
     if (!enable) {
         if (flush_moves(c)) return -1;
@@ -1503,9 +1515,7 @@ extern "C" int mpmc_hip_get_three_body_energy(mpmc_hip_ctx *c, double *out) {
 // molecules are the upload's.  Until the next upload the LJ kernels see zero parameters.
 extern "C" int mpmc_hip_set_vdw(mpmc_hip_ctx *c, int enable, int n, const double *omega, const int *mol_type) {
     if (!c) return fail("MPMC_HIP: set_vdw: null context");
-    if (c->in_flight) return fail("MPMC_HIP: set_vdw between energy_begin() and energy_end()");
-    if (!c->have_atoms) return fail("MPMC_HIP: set_vdw: no configuration uploaded");
-    if (c->edited) return fail("MPMC_HIP: set_vdw: molecules were inserted or removed since the upload");
+    if (per_atom_setter_refused(c, "set_vdw")) return -1;
     HIPCHK(hipSetDevice(c->device));
     if (!enable) {
         c->vdw_iso.clear();
@@ -1513,10 +1523,7 @@ extern "C" int mpmc_hip_set_vdw(mpmc_hip_ctx *c, int enable, int n, const double
         if (flush_moves(c)) return -1;
         c->vdw_on = false;
         c->rep.valid = c->rep_lrc.valid = c->vdw.valid = c->vdw_lrc.valid = false;
-        c->pair_part_valid = false;  // the Lennard-Jones kernels change between real and zero parameters
-        c->lrc.valid = false;
-        c->all_dirty = true;
-        ++c->config_rev;
+        lj_kernels_switched(c);
         return 0;
     }
     if (n != c->n) return fail("MPMC_HIP: set_vdw: %d frequencies for the %d atoms of the upload", n, c->n);
@@ -1569,13 +1576,11 @@ extern "C" int mpmc_hip_set_vdw(mpmc_hip_ctx *c, int enable, int n, const double
     c->vdw_mols = std::move(mols);
     c->vdw_iso_summed = false;
     c->rep.valid = c->rep_lrc.valid = c->vdw.valid = c->vdw_lrc.valid = false;
-    if (!c->vdw_on) {
-        c->pair_part_valid = false;  // the Lennard-Jones kernels change between real and zero parameters
-        c->lrc.valid = false;
-        c->all_dirty = true;
-    }
+    if (c->vdw_on)
+        ++c->config_rev;  // (new frequencies in a mode that was on: the Lennard-Jones kernels keep their zero parameters)
+    else
+        lj_kernels_switched(c);
     c->vdw_on = true;
-    ++c->config_rev;
     return 0;
 }
 
@@ -2510,20 +2515,25 @@ static int static_pass(mpmc_hip_ctx *c, TileSum &ts, bool stale, int nparts, Res
     return 0;
 }
 
+// A mode's long-range correction, a static sum that exists only while `wanted` (rd_lrc): otherwise the publish kernel writes
+// its slot as zero, and the sum is dropped so that switching rd_lrc back on makes it again.
+template <typename Enqueue>
+static int lrc_pass(mpmc_hip_ctx *c, TileSum &ts, bool wanted, int nparts, ResSlot slot, hipStream_t sb, Enqueue &&enqueue) {
+    if (wanted) return static_pass(c, ts, !ts.valid, nparts, slot, sb, enqueue);
+    c->call.res_zero_mask |= 1u << slot;
+    ts.valid = false;
+    return 0;
+}
+
 // disp_expansion: the dense pair sum, and its long-range correction when the parameters, the cutoff or the volume changed.
 static int launch_disp(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipStream_t sb) {
     const int ntile = c->npad / 64;
     const DispAtoms da = {c->d_eps, c->d_sig, c->d_c6, c->d_c8, c->d_c10};
-    if (c->par.rd_lrc) {
-        if (static_pass(c, c->disp_lrc, !c->disp_lrc.valid, ntile * ntile, R_DISP_LRC, sb, [&] {
-                hipLaunchKernelGGL(disp_lrc_kernel, dim3(ntile, ntile), dim3(64 * kDispLrcWaves), 0, sb, a, da, bx, c->disp_par,
-                                   c->disp_lrc.part);
-            }))
-            return -1;
-    } else {
-        c->call.res_zero_mask |= 1u << R_DISP_LRC;
-        c->disp_lrc.valid = false;
-    }
+    if (lrc_pass(c, c->disp_lrc, c->par.rd_lrc, ntile * ntile, R_DISP_LRC, sb, [&] {
+            hipLaunchKernelGGL(disp_lrc_kernel, dim3(ntile, ntile), dim3(64 * kDispLrcWaves), 0, sb, a, da, bx, c->disp_par,
+                               c->disp_lrc.part);
+        }))
+        return -1;
     return tile_pass(c, c->disp, ntile * ntile, R_DISP, sb, [&](const DirtyBlocks &sel) {
         hipLaunchKernelGGL(disp_tile_kernel, dim3(ntile, sel.n > 0 ? sel.n : ntile), dim3(64 * kDispWaves), 0, sb, a, da, bx,
                            c->disp_par, sel, c->disp.part, c->call.pair_moves);
@@ -2548,9 +2558,7 @@ static RdcParams rdc_params(const mpmc_hip_ctx *c) {
 // changed.  `a` carries zero epsilon / sigma in this mode: these kernels get the real ones.
 static int launch_rdc(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipStream_t sb) {
     const int ntile = c->npad / 64;
-    DevAtoms lj = a;
-    lj.eps = c->d_eps;
-    lj.sig = c->d_sig;
+    const DevAtoms lj = lj_atoms(c, a);
     const RdcParams rp = rdc_params(c);
     const int want_lrc = c->par.rd_lrc ? 1 : 0;
     const bool stale = !c->rdc_static.valid || c->rdc_static_lrc != want_lrc;
@@ -2576,25 +2584,17 @@ static int launch_rdc(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipS
 // ones.
 static int launch_rdform(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipStream_t sb) {
     const int ntile = c->npad / 64;
-    DevAtoms lj = a;
-    lj.eps = c->d_eps;
-    lj.sig = c->d_sig;
+    const DevAtoms lj = lj_atoms(c, a);
     RdFormParams fp;
     fp.mixing = c->rd_mix;
     fp.fh = c->par.feynman_hibbs ? 1 : 0;
     fp.fh_order = c->par.feynman_hibbs_order;
     fp.temperature = c->par.temperature;
-    if (c->rd_form == kRdFormLJ && c->par.rd_lrc) {
-        const int mix = c->rd_mix;
-        if (static_pass(c, c->rdf_lrc, !c->rdf_lrc.valid, ntile * ntile, R_DISP_LRC, sb, [&] {
-                hipLaunchKernelGGL(rdform_lrc_kernel, dim3(ntile, ntile), dim3(64 * kRdFormLrcWaves), 0, sb, lj, bx, mix,
-                                   c->rdf_lrc.part);
-            }))
-            return -1;
-    } else {
-        c->call.res_zero_mask |= 1u << R_DISP_LRC;
-        c->rdf_lrc.valid = false;
-    }
+    if (lrc_pass(c, c->rdf_lrc, c->rd_form == kRdFormLJ && c->par.rd_lrc, ntile * ntile, R_DISP_LRC, sb, [&] {
+            hipLaunchKernelGGL(rdform_lrc_kernel, dim3(ntile, ntile), dim3(64 * kRdFormLrcWaves), 0, sb, lj, bx, c->rd_mix,
+                               c->rdf_lrc.part);
+        }))
+        return -1;
     return tile_pass(c, c->rdf, ntile * ntile, R_DISP, sb, [&](const DirtyBlocks &sel) {
         const dim3 grid(ntile, sel.n > 0 ? sel.n : ntile), block(64 * kRdFormWaves);
         double *part = c->rdf.part;
@@ -2684,19 +2684,12 @@ static int vdw_ensure_iso(mpmc_hip_ctx *c) {
 // mode: the repulsion kernels get the real ones.
 static int launch_vdw(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipStream_t sb) {
     const int ntile = c->npad / 64;
-    DevAtoms lj = a;
-    lj.eps = c->d_eps;
-    lj.sig = c->d_sig;
+    const DevAtoms lj = lj_atoms(c, a);
     const DirtyBlocks all = {};
-    if (c->par.rd_lrc) {
-        if (static_pass(c, c->rep_lrc, !c->rep_lrc.valid, ntile * ntile, R_DISP_LRC, sb, [&] {
-                hipLaunchKernelGGL(rep_lrc_kernel, dim3(ntile, ntile), dim3(64 * kVdwLrcWaves), 0, sb, lj, bx, all, c->rep_lrc.part);
-            }))
-            return -1;
-    } else {
-        c->call.res_zero_mask |= 1u << R_DISP_LRC;
-        c->rep_lrc.valid = false;
-    }
+    if (lrc_pass(c, c->rep_lrc, c->par.rd_lrc, ntile * ntile, R_DISP_LRC, sb, [&] {
+            hipLaunchKernelGGL(rep_lrc_kernel, dim3(ntile, ntile), dim3(64 * kVdwLrcWaves), 0, sb, lj, bx, all, c->rep_lrc.part);
+        }))
+        return -1;
     if (tile_pass(c, c->rep, ntile * ntile, R_DISP, sb, [&](const DirtyBlocks &sel) {
             hipLaunchKernelGGL(rep_tile_kernel, dim3(ntile, sel.n > 0 ? sel.n : ntile), dim3(64 * kRepWaves), 0, sb, lj, bx, sel,
                                c->rep.part, c->call.pair_moves);
@@ -2707,16 +2700,11 @@ static int launch_vdw(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipS
         c->vdw.valid = c->vdw_lrc.valid = false;
         return 0;
     }
-    if (c->par.rd_lrc) {
-        if (static_pass(c, c->vdw_lrc, !c->vdw_lrc.valid, ntile * ntile, R_VDW_LRC, sb, [&] {
-                hipLaunchKernelGGL(vdw_lrc_kernel, dim3(ntile, ntile), dim3(64 * kVdwLrcWaves), 0, sb, a,
-                                   (const double *)c->d_vdw_w, bx, all, c->vdw_lrc.part);
-            }))
-            return -1;
-    } else {
-        c->call.res_zero_mask |= 1u << R_VDW_LRC;
-        c->vdw_lrc.valid = false;
-    }
+    if (lrc_pass(c, c->vdw_lrc, c->par.rd_lrc, ntile * ntile, R_VDW_LRC, sb, [&] {
+            hipLaunchKernelGGL(vdw_lrc_kernel, dim3(ntile, ntile), dim3(64 * kVdwLrcWaves), 0, sb, a, (const double *)c->d_vdw_w,
+                               bx, all, c->vdw_lrc.part);
+        }))
+        return -1;
     if (c->vdw.valid && c->dirty_atoms.empty()) return 0;  // nothing moved: d_res[R_VDW] is still that sum
     ScopedTimer t(c, T_OTHER, sb);
     if (vdw_eigen_sum(c, a, bx, 0, c->vdw_na, c->call.pair_moves, c->d_res + R_VDW, sb)) return -1;

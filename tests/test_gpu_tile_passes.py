@@ -1,7 +1,9 @@
 """GPU tests of the tile-pass scheme the dense terms share (mpmc_amd/csrc/kernels_tile.h; tile_pass() in engine.hip):
 disp_tile_kernel, rdc_tile_kernel and at_triple_kernel after ONE evaluation's worth of moves that dirty several 64-atom
 blocks in descending order (tests/tile_pass_cases.py says why that order), and every dense kernel against the bits of the
-commit before the scheme was shared (tests/golden/dense_terms_guard.npz).
+commit before the scheme was shared (tests/golden/dense_terms_guard.npz); and the host half's table of what drops which
+cached sum (positions_unknown() and its three siblings in engine.hip, and the mode setters): every
+mode through every event, against a fresh context.
 
 No tolerance is introduced here: the bit comparisons have none, and the comparisons with the CPU references use
 phahst_cases.RD_TOL, rdc_cases.RD_TOL and at_cases.TOLERANCE (1e-12 of sum |terms| each) as the tests of those terms do.
@@ -72,6 +74,55 @@ def test_several_dirty_blocks_in_descending_order(name):
         got, want, tol = live["three_body"], u.total, ac.TOLERANCE * u.sum_abs
     print("%s: %.15g reference %.15g |diff| %.3g tol %.3g" % (name, got, want, abs(got - want), tol))
     assert abs(got - want) <= tol, (name, got, want, tol)
+
+
+def _fresh_snapshot(s, flags):
+    e = engine.Engine(len(s["charge"]))
+    e.load_system(s, flags)
+    r = tp.snapshot(e)
+    e.close()
+    return r
+
+
+@pytest.mark.parametrize("mode,event", tp.EVENT_CELLS)
+def test_an_event_leaves_the_bits_of_a_fresh_context(mode, event):
+    """The table of what drops which cached sum, from outside: a live context that went through the
+    event gives, field for field with ==, what a fresh context gives on the final state -- and again after one more
+    single-molecule move, whose incremental passes start from the sums the event left valid.  A sum the event should have
+    dropped and did not shows as the stale value; the event itself must show in the fields it is about, so that no cell
+    passes by doing nothing."""
+    m = tp.EVENT_MODES[mode]()
+    s, f = m["system"], m["flags"]
+    e = engine.Engine(len(s["charge"]))
+    e.load_system(s, f)
+    before = tp.snapshot(e)
+    assert before["status"] == 0 and before[m["term"]] != 0.0
+    s, f, probe, fields = tp.EVENTS[event](e, m, s, f, before)
+    got = tp.snapshot(e)
+    kept = tp.E_ISO_FIELDS if mode == "polarvdw" and event in tp.E_ISO_KEPT_BY else ()
+
+    def same(live, fresh, what):
+        diff = {k: (live[k], fresh[k]) for k in fresh if live[k] != fresh[k] and k not in kept}
+        print(mode, event, what, "fields compared", len(fresh) - len(kept), "differing", diff)
+        assert sorted(live) == sorted(fresh) and not diff, (what, diff)
+        if kept:  # the kept e_iso, and the two sums made with it
+            assert live["e_iso"] == before["e_iso"]
+            assert live["vdw_energy"] == (live["e_total"] - live["e_iso"]) + live["lr_corr"]
+            assert live["energy"] == ((live["rd_energy"] + live["coulombic_energy"]) + live["polarization_energy"]) + live["vdw_energy"]
+
+    same(got, _fresh_snapshot(s, f), "behind the event")
+    probe = got if probe is None else probe
+    for k in fields:
+        assert probe[k] != before[k], (k, probe[k])
+    if not fields:  # (rd_lrc under the sg form: no term reads it)
+        assert got == before
+
+    mv = tp.moves(s, seed=37)[-1:]
+    e.update_atoms(*mv[0])
+    after = tp.snapshot(e)
+    e.close()
+    same(after, _fresh_snapshot(tp.moved(s, mv), f), "behind the move")
+    assert after["energy"] != got["energy"] and after["status"] == 0
 
 
 def test_dense_terms_give_the_bits_of_the_parent_commit():

@@ -1,6 +1,7 @@
 """Inputs of tests/test_gpu_tile_passes.py and tests/golden/make_dense_terms_guard.py: the smallest committed case of each
 dense-term mode, a move of several molecules whose 64-atom blocks arrive at the engine in DESCENDING order, and the
-sequence of evaluations both files record.
+sequence of evaluations both files record; and the modes and events of the test that pins what drops which cached sum
+(EVENT_MODES, EVENTS).
 
 Why descending.  A step of the existing incremental tests moves one molecule: one dirty block, or two in ascending order.
 The rule "the tile of two dirty blocks belongs to the earlier entry of the list" (kernels_tile.h, owned_tile) decides
@@ -12,7 +13,11 @@ import numpy as np
 import at_cases as ac
 import phahst_cases as pc
 import rdc_cases as rc
+import rdforms_cases as rf
+import vdw_cases as vc
 from mpmc_amd import synth
+from mpmc_amd.engine import DISP_NAMES
+from pair_reference import _molecule_index
 
 MAX_MOVED = 32  # kMaxMoves: the moves ride in the MoveList of the pair kernel's launch
 RDC_ORDER = 2
@@ -110,6 +115,120 @@ def run_edit_case(engine):
     out.append(dict(e.energy()))
     e.close()
     return out
+
+
+# ---- What drops which cached sum, pinned from outside: a live context that went through an event
+# against a fresh one on the final state.  One entry per mode that owns rd_energy, plus Axilrod-Teller: the smallest
+# committed case of each (2 to 5 blocks of 64 atoms: full and incremental passes differ).
+#   term          the field the mode's own term shows in
+#   leave / back  leave the mode and come back to it, on a live context (plain Lennard-Jones leaves by entering rd_crystal)
+#   fh4           the mode's existing tests run feynman_hibbs order 4
+#   lrc           rd_lrc changes something in the mode (the sg form has no long-range correction: kernels_rdforms.h)
+def _event_mode(system, flags, term, leave, back, fh4=False, lrc=True):
+    return dict(system=system, flags=dict(flags), term=term, leave=leave, back=back, fh4=fh4, lrc=lrc)
+
+
+def _rd_form_mode(form, mixing, base):
+    return _event_mode(rf.system("t130", form, mixing), rf.flags("t130", base, form, mixing), "rd_energy",
+                       lambda e, s, f: e.set_rd_form("off"), lambda e, s, f: e.set_rd_form(form, mixing), fh4=form == "lj",
+                       lrc=form == "lj")
+
+
+EVENT_MODES = {
+    "lj": lambda: _event_mode(synth.s_pol(320), synth.FLAGS_ES, "rd_energy", lambda e, s, f: e.set_rd_crystal(RDC_ORDER),
+                              lambda e, s, f: e.set_rd_crystal(0), fh4=True),
+    "phahst": lambda: _event_mode(pc.system("c320"), pc.VARIANTS["polarizable"], "rd_energy",
+                                  lambda e, s, f: e.set_dispersion(s),
+                                  lambda e, s, f: e.set_dispersion(s, **{k: f[k] for k in DISP_NAMES if k in f})),
+    "rd_crystal": lambda: _event_mode(rc.system("t150"), rc.flags("lrc", RDC_ORDER), "rd_energy",
+                                      lambda e, s, f: e.set_rd_crystal(0), lambda e, s, f: e.set_rd_crystal(RDC_ORDER),
+                                      fh4=True),
+    "lj-waldmanhagler": lambda: _rd_form_mode("lj", "waldmanhagler", rf.POLAR),
+    "sg": lambda: _rd_form_mode("sg", "lb", rf.BASE),
+    "polarvdw": lambda: _event_mode(vc.system("box70"), vc.FLAGS, "vdw_energy", lambda e, s, f: e.set_vdw(s, enable=False),
+                                    lambda e, s, f: e.set_vdw(s)),
+    "axilrod_teller": lambda: _event_mode(ac.case("n320"), synth.FLAGS_AT, "three_body",
+                                          lambda e, s, f: e.set_axilrod_teller(s, enable=False),
+                                          lambda e, s, f: e.set_axilrod_teller(s)),
+}
+
+
+def snapshot(e):
+    """every Result field of an energy() and every mode's getters behind it (zeros outside their mode)"""
+    return dict(e.energy(), three_body=e.three_body_energy(), vdw_energy=e.vdw_energy(), **e.vdw_terms())
+
+
+def _per_molecule(s):
+    """(molecule index of every atom in upload order, first atom of every molecule)"""
+    mol = _molecule_index(s["molecule"])
+    return mol, np.array([np.flatnonzero(mol == m)[0] for m in range(mol.max() + 1)])
+
+
+# An event: (live context, mode entry, system, flags, snapshot before) -> (system, flags of the final state, the snapshot
+# that must differ from `before` or None for the one behind the event, the fields it must differ in).
+def _ev_rd_lrc(e, m, s, f, before):
+    f2 = dict(f, rd_lrc=0 if f.get("rd_lrc", 1) else 1)
+    e.set_params(**f2)
+    return s, f2, None, ("rd_energy",) if m["lrc"] else ()
+
+
+def _ev_fh4(e, m, s, f, before):
+    f2 = dict(f, feynman_hibbs=1, feynman_hibbs_order=4)
+    e.set_params(**f2)
+    return s, f2, None, ("rd_energy",)
+
+
+def _ev_set_box(e, m, s, f, before):
+    f2 = dict(f, pbc_cutoff=0.95 * before["cutoff"])
+    e.set_box(s["basis"], f2["pbc_cutoff"])
+    return s, f2, None, ("cutoff", "rd_energy")
+
+
+def _ev_scale_box(e, m, s, f, before):
+    mol, first = _per_molecule(s)
+    basis, delta = np.asarray(s["basis"]) * 1.01, 0.01 * s["pos"][first]
+    assert e.scale_box(basis, delta, f.get("pbc_cutoff", 0.0))
+    return dict(s, basis=basis, pos=s["pos"] + delta[mol]), f, None, ("volume", "rd_energy")
+
+
+def _ev_load_system(e, m, s, f, before):
+    mol, first = _per_molecule(s)
+    shift = np.random.default_rng(5).uniform(-0.05, 0.05, (len(first), 3))
+    s2 = dict(s, pos=s["pos"] + shift[mol], epsilon=1.02 * s["epsilon"], sigma=1.01 * s["sigma"])
+    e.load_system(s2, f)
+    return s2, f, None, ("rd_energy", m["term"])
+
+
+def _ev_full_passes(e, m, s, f, before):
+    e.set_option("incremental_pairs", 0)
+    mv = moves(s, seed=31)[:1]
+    e.update_atoms(*mv[0])
+    return moved(s, mv), f, None, ("energy",)
+
+
+def _ev_leave_and_back(e, m, s, f, before):
+    m["leave"](e, s, f)
+    outside = snapshot(e)
+    m["back"](e, s, f)
+    return s, f, outside, (m["term"],)
+
+
+EVENTS = {
+    "rd_lrc": _ev_rd_lrc,
+    "fh4": _ev_fh4,
+    "set_box": _ev_set_box,
+    "scale_box": _ev_scale_box,
+    "load_system": _ev_load_system,
+    "full_passes": _ev_full_passes,
+    "leave_and_back": _ev_leave_and_back,
+}
+FH4_MODES = ("lj", "rd_crystal", "lj-waldmanhagler")  # (polarvdw refuses feynman_hibbs)
+EVENT_CELLS = [(mode, ev) for mode in EVENT_MODES for ev in EVENTS if ev != "fh4" or mode in FH4_MODES]
+# polarvdw keeps e_iso per molecule type for as long as the mode stays on, through a box change and an upload (vdw.c:262-320;
+# tests/test_gpu_vdw.py::test_scale_box_leaves_the_bits_of_a_fresh_context): behind these events it is the value from before,
+# not the one a fresh context makes, and so are the two sums it enters
+E_ISO_KEPT_BY = ("set_box", "scale_box", "load_system")
+E_ISO_FIELDS = ("e_iso", "vdw_energy", "energy")
 
 
 def guard_entries(engine):
