@@ -493,11 +493,44 @@ int mpmc_hip_update_atoms(mpmc_hip_ctx *ctx, int first, int count, const double 
  * `mass` = atomic masses (the molecular mass is their sum), `frozen` applies to the whole molecule.
  * Return 0 = done; 1 = cannot be done incrementally (context full, more than 16 atoms, Gauss-Seidel on the
  * expanded matrix (persistent_gs = 0), incremental options off): upload the whole configuration again; < 0 = error.
- * In Gauss-Seidel modes follow up with mpmc_hip_set_sweep_order(). */
+ * In Gauss-Seidel modes follow up with mpmc_hip_set_sweep_order().
+ * These two entries cannot carry the per-atom data of the dense energy modes, so they answer 1 while
+ * mpmc_hip_set_dispersion(), mpmc_hip_set_axilrod_teller(), mpmc_hip_set_rd_crystal() or mpmc_hip_set_rd_form() is on,
+ * and keep doing so: mpmc_hip_edit_molecules() below is the entry that edits in those modes. */
 int mpmc_hip_insert_molecule(mpmc_hip_ctx *ctx, int count, const double *x, const double *y, const double *z,
                              const double *charge, const double *polarizability, const double *epsilon,
                              const double *sigma, const double *mass, int frozen, int *first_slot);
 int mpmc_hip_remove_molecule(mpmc_hip_ctx *ctx, int first_slot, int count);
+
+/* Several molecules leave and enter in one call, in every mode that has device-side edits.
+ *   Removals are carried out first, in the order given (remove_first_slot[k], remove_count[k]); insertions follow, in the
+ *   order given, insert_first_slot[k] receiving the first slot of insert[k].  The slot rules, the sweep-view slots and the
+ *   Gauss-Seidel protocol (mpmc_hip_set_sweep_order) are those of the two entries above: called with the same molecules
+ *   this entry leaves what the sequence of those calls leaves, bit for bit.
+ *   A molecule brings what insert_molecule takes, and the per-atom data of the modes that are on: c6 / c8 / c10 while
+ *   mpmc_hip_set_dispersion() is on (epsilon / sigma are then the exponent b and the range rho, as at the upload), and c9
+ *   while mpmc_hip_set_axilrod_teller() is on -- the EFFECTIVE coefficient, as that call takes it.  Arrays of a mode that
+ *   is off are not read and may be NULL.
+ *   It works on the standard path, and while set_dispersion, set_axilrod_teller (beside Lennard-Jones or beside
+ *   disp_expansion), set_rd_crystal or set_rd_form is on.
+ * Return 0 = done; 1 = upload the whole configuration again: more than 8 removals or 8 insertions, a molecule above 16
+ * atoms, no room in the context or in the sweep view, mpmc_hip_set_vdw() or mpmc_hip_set_exact_polar() on, "pair_coefficients",
+ * "incremental_amatrix" or "incremental_pairs" at 0, Gauss-Seidel without the chain kernel; < 0 = error (a bad slot
+ * range, a NULL array the active mode reads, a negative polarizability under axilrod_teller, a call between
+ * energy_begin() and energy_end()).
+ * All or nothing: whatever makes the call answer 1 or fail is decided before anything changes, and the next energy()
+ * then returns what it would have returned without the call. */
+typedef struct {
+    int count;                 /* atoms of the molecule, 1 .. 16 */
+    int frozen;
+    const double *x, *y, *z, *charge, *polarizability, *epsilon, *sigma, *mass;
+    const double *c6, *c8, *c10;   /* read while mpmc_hip_set_dispersion() is on, else may be NULL */
+    const double *c9;              /* read while mpmc_hip_set_axilrod_teller() is on: the EFFECTIVE c9, as that call takes it */
+} mpmc_hip_molecule;
+
+int mpmc_hip_edit_molecules(mpmc_hip_ctx *ctx,
+                            int nremove, const int *remove_first_slot, const int *remove_count,
+                            int ninsert, const mpmc_hip_molecule *insert, int *insert_first_slot);
 /* Gauss-Seidel modes (polar_gs / polar_gs_ranked) only: their result depends on the ORDER in which the atoms are
  * swept -- the order of the reference's atom_array (the molecule lists), which thole_iterative.c walks and
  * update_ranking() re-sorts stably -- and after insert / remove the engine's slot order is no longer that order.

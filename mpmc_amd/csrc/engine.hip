@@ -334,6 +334,8 @@ struct CallState {
     bool two_streams = false;     // the LJ / Ewald kernels run on the side stream beside it
     bool plain_launches = false;  // neither captured into a step graph nor eligible to be ("step_graph" off)
     DirtyBlocks dirty_blocks;             // 64-atom blocks of the atoms moved since the last call
+    DirtyBlocks lrc_blocks;               // ... and of lrc_dirty_atoms (n = 0: none, or more than the list holds), which every
+    bool lrc_edited = false;              //     long-range correction of the call consumes: lrc_edited = that list is not empty
     bool pair_part_valid_before = false;  // pair_part_valid when the call started (after collect_dirty_blocks)
     bool moves_deferred = false;  // pending moves not yet applied: they ride in view 0's coefficient update ...
     bool moves_in_pair = false;   // ... or inside the pair kernel's launch (steps without polarization)
@@ -552,7 +554,8 @@ struct mpmc_hip_ctx {
     std::vector<char> slot_valid;        // per atom slot
     std::vector<char> slot_polar;        // per atom slot: polarizability != 0 (what a stated sweep order must cover exactly)
     std::vector<std::pair<int, int>> holes;  // (first, count) of removed molecules, reusable by an insert of that size
-    std::vector<int> lrc_dirty_atoms;    // atoms inserted / removed since the long-range correction was summed
+    std::vector<int> lrc_dirty_atoms;    // atoms inserted / removed since the static sums (the long-range corrections, rd_crystal's
+                                         // self part) were made: ONE list, read by every such sum of a call, cleared once behind them
     int n_mol_uploaded = 0;         // molecules of the last upload (their ids are 0 .. n_mol_uploaded - 1)
     bool edited = false;            // insert_molecule / remove_molecule since the last upload: ids no longer in upload order
     // Gauss-Seidel + grand-canonical edits: the sweep ORDER is part of the result, and after insert / remove the
@@ -1044,12 +1047,18 @@ static void positions_unknown(mpmc_hip_ctx *c) {
     c->pair_part_valid = c->field_part_valid = c->disp.valid = c->rdc.valid = c->at.valid = false;
     c->rep.valid = c->vdw.valid = c->rdf.valid = false;
 }
-// set_params(), or insert_molecule() grew the tile grid.  Not c->at: no parameter enters the three-body term, and the grid
-// cannot grow in its mode (edits_supported()); a full triple pass after every set_params() would be wasted.
+// set_params(), or an insertion grew the tile grid (grid_grew()).  Not c->at: no parameter enters the three-body term; a
+// full triple pass after every set_params() would be wasted.
 static void params_or_grid_changed(mpmc_hip_ctx *c) {
     c->pair_part_valid = c->field_part_valid = c->disp.valid = c->rdc.valid = false;
     c->rep.valid = c->vdw.valid = false;  // (polar_damp enters the matrix)
     c->rdf.valid = false;
+}
+// An appended molecule changed npad: a tile's slot in every partial array is I * ntile + J and the count of three-body units
+// follows ntile, so every tile sum, static ones included, is made from scratch.
+static void grid_grew(mpmc_hip_ctx *c) {
+    params_or_grid_changed(c);
+    c->lrc.valid = c->disp_lrc.valid = c->rdf_lrc.valid = c->rdc_static.valid = c->at.valid = false;
 }
 // apply_box(): the sums of parameters, cutoff and volume (those over positions go with all_dirty)
 static void box_changed(mpmc_hip_ctx *c) {
@@ -1329,6 +1338,14 @@ extern "C" int mpmc_hip_set_dispersion(mpmc_hip_ctx *c, const mpmc_hip_disp_para
     return 0;
 }
 
+// The two three-body values of one site (AtAtoms): what set_axilrod_teller() stores for an uploaded atom and
+// edit_molecules() for an inserted one.
+static void at_site_values(double alpha, double c9, double &a, double &g) {
+    a = alpha * kAtAlpha;
+    // 1 / (c / p) with the reference's own p = pow(alpha * 6.7483345, 3) (axilrod_teller.cpp:121-122); c = 0 gives inf
+    g = (a != 0.0) ? 1.0 / (c9 / std::pow(a, 3)) : 1.0;
+}
+
 // axilrod_teller: the triple-dipole term.  c9 (atomic units, upload order) is the EFFECTIVE per-atom coefficient: under
 // midzuno_kihara_approx the caller has already replaced it by 3/4 alpha 6.7483345 c6.  The polarizabilities are the upload's.
 extern "C" int mpmc_hip_set_axilrod_teller(mpmc_hip_ctx *c, int enable, int n, const double *c9) {
@@ -1352,10 +1369,7 @@ extern "C" int mpmc_hip_set_axilrod_teller(mpmc_hip_ctx *c, int enable, int n, c
     for (int i = 0; i < n; ++i) {
         const double alpha = ha[i];
         if (alpha < 0.0) return fail("MPMC_HIP: set_axilrod_teller: negative polarizability %g of atom %d", alpha, i);
-        const double ai = alpha * kAtAlpha;
-        ha[i] = ai;
-        // 1 / (c / p) with the reference's own p = pow(alpha * 6.7483345, 3) (axilrod_teller.cpp:121-122); c = 0 gives inf
-        hg[i] = (ai != 0.0) ? 1.0 / (c9[i] / std::pow(ai, 3)) : 1.0;
+        at_site_values(alpha, c9[i], ha[i], hg[i]);
     }
     if (!c->d_at_a) {
         HIPCHK(c->d_at_a.alloc(nall));
@@ -1821,14 +1835,18 @@ static bool gs_order_mode(const mpmc_hip_ctx *c) {  // Gauss-Seidel on the chain
            c->opt.persistent_gs != 0 && !c->exact_polar;  // (the exact dipoles ignore the solver flags)
 }
 
-static bool edits_supported(const mpmc_hip_ctx *c) {
+// dense: the caller brings the per-atom data of the dense modes (mpmc_hip_edit_molecules).  insert_molecule() and
+// remove_molecule() cannot, and answer 1 in those modes.
+static bool edits_supported(const mpmc_hip_ctx *c, bool dense = false) {
     const mpmc_hip_params &P = c->par;
     if (!c->have_atoms || c->all_dirty || !c->opt.incremental || !c->opt.incremental_pairs || !c->opt.pair_coef) return false;
-    if (c->disp_on) return false;  // disp_expansion: no device-side insert / remove (the caller uploads again)
-    if (c->at_on) return false;    // axilrod_teller: the same
-    if (c->rdc_order) return false;  // rd_crystal: the same
-    if (c->rd_form) return false;    // set_rd_form: the same
-    if (c->vdw_on) return false;     // polarvdw: the same
+    if (!dense) {
+        if (c->disp_on) return false;  // disp_expansion: c6 / c8 / c10 of the new atoms are missing (the caller uploads again)
+        if (c->at_on) return false;    // axilrod_teller: c9 is
+        if (c->rdc_order) return false;  // rd_crystal and set_rd_form: pinned to the same answer
+        if (c->rd_form) return false;
+    }
+    if (c->vdw_on) return false;     // polarvdw: the coupled-dipole matrix is not patched by edits
     if (c->exact_polar) return false;  // exact dipoles: the expanded matrix is not patched by edits (as on its Gauss-Seidel path)
     // Gauss-Seidel: only with the chain kernel, whose view is rebuilt from the order the caller states afterwards
     if (!P.rd_only && P.polarization && (P.polar_gs || P.polar_gs_ranked) && !gs_order_mode(c)) return false;
@@ -1855,6 +1873,11 @@ static int launch_edits(mpmc_hip_ctx *c, const EditList &ed) {
     t.pz = v0.pz;
     t.palpha = v0.palpha;
     t.pflags = v0.pflags;
+    t.c6 = c->disp_on ? c->d_c6.get() : nullptr;
+    t.c8 = c->disp_on ? c->d_c8.get() : nullptr;
+    t.c10 = c->disp_on ? c->d_c10.get() : nullptr;
+    t.at_a = c->at_on ? c->d_at_a.get() : nullptr;
+    t.at_g = c->at_on ? c->d_at_g.get() : nullptr;
     drop_polar_result(c);  // (mark_edited(): the result of the configuration before the edit cannot be asked for any more)
     if (flush_moves(c)) return -1;  // keep the order of the caller's operations
     c->main_writes = true;
@@ -1878,6 +1901,43 @@ static void mark_edited(mpmc_hip_ctx *c, int first, int count) {
 
 extern "C" int mpmc_hip_slot_count(mpmc_hip_ctx *c) { return c ? c->n : 0; }
 
+// What an inserted molecule brings beyond the arguments of insert_molecule(): null outside the mode that reads it.
+struct DenseAtomData {
+    const double *c6 = nullptr, *c8 = nullptr, *c10 = nullptr;  // disp_expansion
+    const double *c9 = nullptr;                                  // axilrod_teller (effective)
+};
+static int remove_checked(mpmc_hip_ctx *c, int first, int count);
+static int insert_checked(mpmc_hip_ctx *c, int count, const double *x, const double *y, const double *z, const double *charge,
+                          const double *polarizability, const double *epsilon, const double *sigma, const double *mass,
+                          int frozen, const DenseAtomData &dd, int *first_slot);
+
+// Where a molecule of `count` atoms goes: the most recent hole of exactly that size, else new slots at the end.  hole: its
+// index in `holes`, or -1.  false: the context is full.
+static bool place_molecule(const std::vector<std::pair<int, int>> &holes, int n, int max_atoms, int count, int &first,
+                           int &hole) {
+    first = hole = -1;
+    for (int h = (int)holes.size() - 1; h >= 0; --h)
+        if (holes[h].second == count) {
+            hole = h;
+            first = holes[h].first;
+            return true;
+        }
+    if (n + count > max_atoms) return false;
+    first = n;
+    return true;
+}
+// View slots an insertion at `first` appends: a polarizable site takes the atom slot's old view slot if it has one.
+static int new_view_slots(const mpmc_hip_ctx *c, int first, int count, const double *polarizability) {
+    const SweepView &v0 = c->view[0];
+    const bool gs_mode = gs_order_mode(c);
+    int new_view = 0;
+    for (int i = 0; i < count; ++i) {
+        const bool had = !gs_mode && first + i < (int)v0.slot_of_atom.size() && v0.slot_of_atom[first + i] >= 0;
+        if (polarizability[i] != 0.0 && !had) ++new_view;
+    }
+    return new_view;
+}
+
 extern "C" int mpmc_hip_remove_molecule(mpmc_hip_ctx *c, int first, int count) {
     if (!c || !c->have_atoms) return fail("MPMC_HIP: remove_molecule: no configuration uploaded");
     if (c->in_flight) return fail("MPMC_HIP: remove_molecule between energy_begin() and energy_end()");
@@ -1886,6 +1946,11 @@ extern "C" int mpmc_hip_remove_molecule(mpmc_hip_ctx *c, int first, int count) {
     for (int i = 0; i < count; ++i)
         if (!c->slot_valid[first + i]) return fail("MPMC_HIP: remove_molecule: slot %d holds no atom", first + i);
     if (count > kMaxEdit || !edits_supported(c)) return 1;
+    return remove_checked(c, first, count);
+}
+
+// The removal itself, every condition checked by the caller.
+static int remove_checked(mpmc_hip_ctx *c, int first, int count) {
     HIPCHK(hipSetDevice(c->device));
     SweepView &v0 = c->view[0];
     EditList ed;
@@ -1893,6 +1958,7 @@ extern "C" int mpmc_hip_remove_molecule(mpmc_hip_ctx *c, int first, int count) {
     ed.n = count;
     for (int i = 0; i < count; ++i) {
         ed.idx[i] = first + i;
+        ed.at_g[i] = 1.0;  // (the pad value of set_axilrod_teller)
         // the view slot stays with the atom slot, as a hole -- except in Gauss-Seidel modes, where the view is rebuilt
         // from the caller's order (mpmc_hip_set_sweep_order) and is not patched here
         ed.vslot[i] = gs_order_mode(c) ? -1 : v0.slot_of_atom[first + i];
@@ -1922,27 +1988,20 @@ extern "C" int mpmc_hip_insert_molecule(mpmc_hip_ctx *c, int count, const double
     if (count > kMaxEdit || !edits_supported(c)) return 1;
     HIPCHK(hipSetDevice(c->device));
     note_coords(c, x, y, z, count);
+    int first, hole;
+    if (!place_molecule(c->holes, c->n, c->max_atoms, count, first, hole)) return 1;
+    if (c->view[0].nv + new_view_slots(c, first, count, polarizability) > c->view[0].cap) return 1;
+    return insert_checked(c, count, x, y, z, charge, polarizability, epsilon, sigma, mass, frozen, DenseAtomData(), first_slot);
+}
+
+// The insertion itself: room in the context and in the view checked by the caller, which has also noted the coordinates.
+static int insert_checked(mpmc_hip_ctx *c, int count, const double *x, const double *y, const double *z, const double *charge,
+                          const double *polarizability, const double *epsilon, const double *sigma, const double *mass,
+                          int frozen, const DenseAtomData &dd, int *first_slot) {
     SweepView &v0 = c->view[0];
-    // a hole of exactly this size (most recent first), else new slots at the end
-    int first = -1, hole = -1;
-    for (int h = (int)c->holes.size() - 1; h >= 0; --h)
-        if (c->holes[h].second == count) {
-            hole = h;
-            first = c->holes[h].first;
-            break;
-        }
-    if (first < 0) {
-        if (c->n + count > c->max_atoms) return 1;
-        first = c->n;
-    }
-    // view slots for the polarizable sites: the atom slot's old one if it has one, else appended
+    int first, hole;
+    place_molecule(c->holes, c->n, c->max_atoms, count, first, hole);
     const bool gs_mode = gs_order_mode(c);
-    int new_view = 0;
-    for (int i = 0; i < count; ++i) {
-        const bool had = !gs_mode && first + i < (int)v0.slot_of_atom.size() && v0.slot_of_atom[first + i] >= 0;
-        if (polarizability[i] != 0.0 && !had) ++new_view;
-    }
-    if (v0.nv + new_view > v0.cap) return 1;
     if (hole >= 0)
         c->holes.erase(c->holes.begin() + hole);
     else {
@@ -1953,8 +2012,7 @@ extern "C" int mpmc_hip_insert_molecule(mpmc_hip_ctx *c, int count, const double
         const int npad = round_up(c->n, 128);
         if (npad != c->npad) {  // the tile grids of the pair / field / LRC partials change shape
             c->npad = npad;
-            params_or_grid_changed(c);
-            c->lrc.valid = false;
+            grid_grew(c);
         }
     }
     double mm = 0.0;
@@ -1984,6 +2042,13 @@ extern "C" int mpmc_hip_insert_molecule(mpmc_hip_ctx *c, int count, const double
         ed.eps[i] = epsilon[i];
         ed.sig[i] = sigma[i];
         ed.molmass[i] = mm;
+        if (dd.c6) {
+            ed.c6[i] = dd.c6[i];
+            ed.c8[i] = dd.c8[i];
+            ed.c10[i] = dd.c10[i];
+        }
+        ed.at_g[i] = 1.0;
+        if (dd.c9) at_site_values(polarizability[i], dd.c9[i], ed.at_a[i], ed.at_g[i]);
         c->slot_valid[a] = 1;
         c->slot_polar[a] = (polarizability[i] != 0.0);
     }
@@ -2000,6 +2065,92 @@ extern "C" int mpmc_hip_insert_molecule(mpmc_hip_ctx *c, int count, const double
         v0.pos_valid = false;
     }
     *first_slot = first;
+    return 0;
+}
+
+// Several removals and insertions in one call, with the per-atom data of the dense modes (mpmc_hip.h).  Two halves: the
+// first decides every answer other than 0 on copies of the hole list and the slot count and changes nothing; the second
+// is the sequence of remove_checked() / insert_checked() the two old entries would run.
+constexpr int kMaxEditMolecules = 8;
+extern "C" int mpmc_hip_edit_molecules(mpmc_hip_ctx *c, int nremove, const int *remove_first_slot, const int *remove_count,
+                                       int ninsert, const mpmc_hip_molecule *insert, int *insert_first_slot) {
+    if (!c || !c->have_atoms) return fail("MPMC_HIP: edit_molecules: no configuration uploaded");
+    if (c->in_flight) return fail("MPMC_HIP: edit_molecules between energy_begin() and energy_end()");
+    if (nremove < 0 || ninsert < 0 || (nremove > 0 && (!remove_first_slot || !remove_count)) ||
+        (ninsert > 0 && (!insert || !insert_first_slot)))
+        return fail("MPMC_HIP: edit_molecules: bad arguments");
+    if (nremove > kMaxEditMolecules || ninsert > kMaxEditMolecules) return 1;
+    // ---- errors
+    std::vector<char> leaving(c->n, 0);
+    size_t atoms = 0;
+    bool too_large = false;
+    for (int r = 0; r < nremove; ++r) {
+        const int first = remove_first_slot[r], count = remove_count[r];
+        if (first < 0 || count <= 0 || count > c->n || first > c->n - count)
+            return fail("MPMC_HIP: edit_molecules: removal %d: range [%d, %d + %d) outside [0, %d)", r, first, first, count, c->n);
+        for (int i = 0; i < count; ++i) {
+            if (!c->slot_valid[first + i] || leaving[first + i])
+                return fail("MPMC_HIP: edit_molecules: removal %d: slot %d holds no atom", r, first + i);
+            leaving[first + i] = 1;
+        }
+        too_large = too_large || count > kMaxEdit;
+        atoms += count;
+    }
+    for (int m = 0; m < ninsert; ++m) {
+        const mpmc_hip_molecule &M = insert[m];
+        if (M.count <= 0 || !M.x || !M.y || !M.z || !M.charge || !M.polarizability || !M.epsilon || !M.sigma || !M.mass)
+            return fail("MPMC_HIP: edit_molecules: insertion %d: bad arguments", m);
+        if (c->disp_on && (!M.c6 || !M.c8 || !M.c10))
+            return fail("MPMC_HIP: edit_molecules: c6 / c8 / c10 missing while disp_expansion is on (insertion %d)", m);
+        if (c->at_on && !M.c9) return fail("MPMC_HIP: edit_molecules: c9 missing while axilrod_teller is on (insertion %d)", m);
+        too_large = too_large || M.count > kMaxEdit;
+        if (M.count > kMaxEdit) continue;
+        if (c->at_on)
+            for (int i = 0; i < M.count; ++i)
+                if (M.polarizability[i] < 0.0)
+                    return fail("MPMC_HIP: edit_molecules: negative polarizability %g under axilrod_teller (insertion %d, atom %d)",
+                                M.polarizability[i], m, i);
+        atoms += M.count;
+    }
+    // ---- "upload again"
+    if (too_large || !edits_supported(c, true)) return 1;
+    // (more dirty atoms than the incremental passes list would set all_dirty half way, where the old entries start answering 1)
+    if (c->dirty_atoms.size() + atoms > 4 * (size_t)kMaxDirty) return 1;
+    {
+        std::vector<std::pair<int, int>> holes = c->holes;
+        int n = c->n, new_view = 0;
+        for (int r = 0; r < nremove; ++r) holes.push_back(std::make_pair(remove_first_slot[r], remove_count[r]));
+        for (int m = 0; m < ninsert; ++m) {
+            int first, hole;
+            if (!place_molecule(holes, n, c->max_atoms, insert[m].count, first, hole)) return 1;
+            if (hole >= 0)
+                holes.erase(holes.begin() + hole);
+            else
+                n += insert[m].count;
+            new_view += new_view_slots(c, first, insert[m].count, insert[m].polarizability);
+        }
+        if (c->view[0].nv + new_view > c->view[0].cap) return 1;
+    }
+    // ---- the edits
+    HIPCHK(hipSetDevice(c->device));
+    for (int r = 0; r < nremove; ++r)
+        if (remove_checked(c, remove_first_slot[r], remove_count[r])) return -1;
+    for (int m = 0; m < ninsert; ++m) {
+        const mpmc_hip_molecule &M = insert[m];
+        note_coords(c, M.x, M.y, M.z, M.count);
+        for (int i = 0; i < M.count; ++i)
+            if (M.sigma[i] < 0.0) c->negative_sigma = true;  // (as an upload that holds one: Waldman-Hagler is then refused)
+        DenseAtomData dd;
+        if (c->disp_on) {
+            dd.c6 = M.c6;
+            dd.c8 = M.c8;
+            dd.c10 = M.c10;
+        }
+        if (c->at_on) dd.c9 = M.c9;
+        if (insert_checked(c, M.count, M.x, M.y, M.z, M.charge, M.polarizability, M.epsilon, M.sigma, M.mass, M.frozen, dd,
+                           &insert_first_slot[m]))
+            return -1;
+    }
     return 0;
 }
 
@@ -2518,20 +2669,32 @@ static int static_pass(mpmc_hip_ctx *c, TileSum &ts, bool stale, int nparts, Res
 // A mode's long-range correction, a static sum that exists only while `wanted` (rd_lrc): otherwise the publish kernel writes
 // its slot as zero, and the sum is dropped so that switching rd_lrc back on makes it again.
 template <typename Enqueue>
-static int lrc_pass(mpmc_hip_ctx *c, TileSum &ts, bool wanted, int nparts, ResSlot slot, hipStream_t sb, Enqueue &&enqueue) {
-    if (wanted) return static_pass(c, ts, !ts.valid, nparts, slot, sb, enqueue);
+static int lrc_pass(mpmc_hip_ctx *c, TileSum &ts, bool wanted, bool stale, int nparts, ResSlot slot, hipStream_t sb,
+                    Enqueue &&enqueue) {
+    if (wanted) return static_pass(c, ts, stale, nparts, slot, sb, enqueue);
     c->call.res_zero_mask |= 1u << slot;
     ts.valid = false;
     return 0;
+}
+
+// Which tiles the pass of a static sum redoes after insertions / removals: sel = the blocks of lrc_dirty_atoms, or all of
+// them (sel.n == 0) when the sum has to be made from scratch (`scratch`: it is not valid, or the list held more blocks than
+// a selection does).  Returns "stale": the sum is not that of the atoms that exist now.
+static bool lrc_selection(const mpmc_hip_ctx *c, bool scratch, DirtyBlocks &sel) {
+    sel = c->call.lrc_blocks;  // (n = 0 after an overflow)
+    if (scratch) sel.n = 0;
+    return scratch || c->call.lrc_edited;
 }
 
 // disp_expansion: the dense pair sum, and its long-range correction when the parameters, the cutoff or the volume changed.
 static int launch_disp(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipStream_t sb) {
     const int ntile = c->npad / 64;
     const DispAtoms da = {c->d_eps, c->d_sig, c->d_c6, c->d_c8, c->d_c10};
-    if (lrc_pass(c, c->disp_lrc, c->par.rd_lrc, ntile * ntile, R_DISP_LRC, sb, [&] {
-            hipLaunchKernelGGL(disp_lrc_kernel, dim3(ntile, ntile), dim3(64 * kDispLrcWaves), 0, sb, a, da, bx, c->disp_par,
-                               c->disp_lrc.part);
+    DirtyBlocks lsel;
+    const bool stale = lrc_selection(c, !c->disp_lrc.valid, lsel);
+    if (lrc_pass(c, c->disp_lrc, c->par.rd_lrc, stale, ntile * ntile, R_DISP_LRC, sb, [&] {
+            hipLaunchKernelGGL(disp_lrc_kernel, dim3(ntile, lsel.n > 0 ? lsel.n : ntile), dim3(64 * kDispLrcWaves), 0, sb, a, da,
+                               bx, c->disp_par, lsel, c->disp_lrc.part);
         }))
         return -1;
     return tile_pass(c, c->disp, ntile * ntile, R_DISP, sb, [&](const DirtyBlocks &sel) {
@@ -2561,14 +2724,16 @@ static int launch_rdc(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipS
     const DevAtoms lj = lj_atoms(c, a);
     const RdcParams rp = rdc_params(c);
     const int want_lrc = c->par.rd_lrc ? 1 : 0;
-    const bool stale = !c->rdc_static.valid || c->rdc_static_lrc != want_lrc;
+    // (after an edit the self part, a sum over the atoms that exist, is made again whole; the correction by edited blocks)
+    DirtyBlocks lsel;
+    const bool stale = lrc_selection(c, !c->rdc_static.valid || c->rdc_static_lrc != want_lrc, lsel);
     if (static_pass(c, c->rdc_static, stale, want_lrc ? ntile * ntile : 0, R_DISP_LRC, sb, [&] {
             hipLaunchKernelGGL(rdc_self_kernel, dim3(1), dim3(kRdcSelfThreads), 0, sb, lj, bx, rp, c->d_res + R_RDC_SELF);
             if (!want_lrc) return;
             DevBox bc = bx;
             bc.cutoff = rp.cutoff_c;  // lj_lrc_corr / lj_lrc_self at the crystal cutoff (lj.c:188, :273)
-            const DirtyBlocks all = {};
-            hipLaunchKernelGGL(lj_lrc_kernel, dim3(ntile, ntile), dim3(64 * kLrcWaves), 0, sb, lj, bc, all, c->rdc_static.part);
+            hipLaunchKernelGGL(lj_lrc_kernel, dim3(ntile, lsel.n > 0 ? lsel.n : ntile), dim3(64 * kLrcWaves), 0, sb, lj, bc, lsel,
+                               c->rdc_static.part);
         }))
         return -1;
     c->rdc_static_lrc = want_lrc;
@@ -2590,9 +2755,11 @@ static int launch_rdform(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, h
     fp.fh = c->par.feynman_hibbs ? 1 : 0;
     fp.fh_order = c->par.feynman_hibbs_order;
     fp.temperature = c->par.temperature;
-    if (lrc_pass(c, c->rdf_lrc, c->rd_form == kRdFormLJ && c->par.rd_lrc, ntile * ntile, R_DISP_LRC, sb, [&] {
-            hipLaunchKernelGGL(rdform_lrc_kernel, dim3(ntile, ntile), dim3(64 * kRdFormLrcWaves), 0, sb, lj, bx, c->rd_mix,
-                               c->rdf_lrc.part);
+    DirtyBlocks lsel;
+    const bool stale = lrc_selection(c, !c->rdf_lrc.valid, lsel);
+    if (lrc_pass(c, c->rdf_lrc, c->rd_form == kRdFormLJ && c->par.rd_lrc, stale, ntile * ntile, R_DISP_LRC, sb, [&] {
+            hipLaunchKernelGGL(rdform_lrc_kernel, dim3(ntile, lsel.n > 0 ? lsel.n : ntile), dim3(64 * kRdFormLrcWaves), 0, sb, lj,
+                               bx, c->rd_mix, lsel, c->rdf_lrc.part);
         }))
         return -1;
     return tile_pass(c, c->rdf, ntile * ntile, R_DISP, sb, [&](const DirtyBlocks &sel) {
@@ -2686,7 +2853,7 @@ static int launch_vdw(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipS
     const int ntile = c->npad / 64;
     const DevAtoms lj = lj_atoms(c, a);
     const DirtyBlocks all = {};
-    if (lrc_pass(c, c->rep_lrc, c->par.rd_lrc, ntile * ntile, R_DISP_LRC, sb, [&] {
+    if (lrc_pass(c, c->rep_lrc, c->par.rd_lrc, !c->rep_lrc.valid, ntile * ntile, R_DISP_LRC, sb, [&] {
             hipLaunchKernelGGL(rep_lrc_kernel, dim3(ntile, ntile), dim3(64 * kVdwLrcWaves), 0, sb, lj, bx, all, c->rep_lrc.part);
         }))
         return -1;
@@ -2700,7 +2867,7 @@ static int launch_vdw(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, hipS
         c->vdw.valid = c->vdw_lrc.valid = false;
         return 0;
     }
-    if (lrc_pass(c, c->vdw_lrc, c->par.rd_lrc, ntile * ntile, R_VDW_LRC, sb, [&] {
+    if (lrc_pass(c, c->vdw_lrc, c->par.rd_lrc, !c->vdw_lrc.valid, ntile * ntile, R_VDW_LRC, sb, [&] {
             hipLaunchKernelGGL(vdw_lrc_kernel, dim3(ntile, ntile), dim3(64 * kVdwLrcWaves), 0, sb, a, (const double *)c->d_vdw_w,
                                bx, all, c->vdw_lrc.part);
         }))
@@ -2830,19 +2997,21 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
         side_rc = [&]() -> int {
         // after apply_moves: the new coordinates are in place (unless this stream's pair kernel brings the move itself)
         if (two_streams && !(k.side_carry && k.side_moves.n > 0)) side_wait_for_moves(c, sb);
-        // ---- LJ long-range correction: parameters + volume only => cached (lj.c:56-107)
+        // ---- the static sums depend on parameters, the volume and WHICH atoms exist -- not on coordinates: summed once,
+        // their tile partials kept, and only the tiles of inserted / removed atoms' blocks redone afterwards.  The list of
+        // those atoms is read here, by every static sum of the call (this one, launch_disp / launch_rdc / launch_rdform),
+        // and cleared behind the last of them.
+        const bool lrc_overflow = !blocks_of(c->lrc_dirty_atoms, k.lrc_blocks);
+        k.lrc_edited = !c->lrc_dirty_atoms.empty();
+        // ---- LJ long-range correction (lj.c:56-107)
         if (P.rd_lrc) {
-            // depends on parameters, the volume and WHICH atoms exist -- not on coordinates: summed once, its
-            // tile partials kept, and only the tiles of inserted / removed atoms' blocks redone afterwards
             DirtyBlocks lsel;
-            const bool overflow = !blocks_of(c->lrc_dirty_atoms, lsel);
-            if (!c->lrc.valid) lsel.n = 0;
-            if (static_pass(c, c->lrc, !c->lrc.valid || overflow || lsel.n > 0, ntile * ntile, R_LRC, sb, [&] {
+            const bool stale = lrc_selection(c, !c->lrc.valid || lrc_overflow, lsel);
+            if (static_pass(c, c->lrc, stale, ntile * ntile, R_LRC, sb, [&] {
                     hipLaunchKernelGGL(lj_lrc_kernel, dim3(ntile, lsel.n > 0 ? lsel.n : ntile), dim3(64 * kLrcWaves), 0, sb, a, bx,
                                        lsel, c->lrc.part);
                 }))
                 return -1;
-            c->lrc_dirty_atoms.clear();
         } else {
             k.res_zero_mask |= 1u << R_LRC;  // (zeroed by the publish kernel: a memset is a launch of its own)
             c->lrc.valid = false;
@@ -2895,6 +3064,7 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
         } else if (!c->vdw_on) {
             k.res_zero_mask |= 1u << R_AT;
         }
+        c->lrc_dirty_atoms.clear();  // (every static sum of the call has consumed it)
 
         // ---- reciprocal + self (absent under Wolf summation, coulombic.c:27-28)
         if (!P.rd_only && !P.wolf) {

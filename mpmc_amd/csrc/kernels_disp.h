@@ -152,18 +152,20 @@ __global__ __launch_bounds__(64 * kDispWaves) void disp_tile_kernel(DevAtoms a, 
     block_sum_store<kDispWaves>(acc, red, out);
 }
 
-// Long-range correction (disp_expansion.c:5-38, :50-53, :92-100): parameters, the cutoff and the volume only, so it is
-// evaluated at upload / set_dispersion and at box change, like lj_lrc_kernel's result.  Always a full pass: the mode has
-// no device-side insert / remove.  grid = (npad/64 [J], npad/64 [I]), tile partials [I][J], summed by reduce_rows_kernel.
+// Long-range correction (disp_expansion.c:5-38, :50-53, :92-100): parameters, the cutoff, the volume and which atoms
+// exist, no coordinate.  A full pass at upload / set_dispersion and at box change; after mpmc_hip_edit_molecules only the
+// tiles of the edited atoms' blocks are redone, like lj_lrc_kernel's.  Grids: owned_tile(); tile partials [I][J], summed by
+// reduce_rows_kernel.
 constexpr int kDispLrcWaves = 8;
 __device__ __forceinline__ double disp_lrc_term(double c6, double c8, double c10, double rc, double volume) {
     return -4.0 * kPI * (c6 / (3.0 * rc * rc * rc) + c8 / (5.0 * rc * rc * rc * rc * rc) +
                          c10 / (7.0 * rc * rc * rc * rc * rc * rc * rc)) / volume;
 }
 __global__ __launch_bounds__(64 * kDispLrcWaves) void disp_lrc_kernel(DevAtoms a, DispAtoms d, DevBox bx, DispParams dp,
-                                                                      double *__restrict__ partials) {
-    const int I = blockIdx.y, J = blockIdx.x;
+                                                                      DirtyBlocks sel, double *__restrict__ partials) {
+    int I, J;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (!owned_tile(sel, I, J)) return;
     double *out = partials + (size_t)I * gridDim.x + J;
     if (J < I) {
         if (threadIdx.x == 0) out[0] = 0.0;

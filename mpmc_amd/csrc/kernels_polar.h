@@ -487,7 +487,9 @@ __global__ __launch_bounds__(64) void apply_moves_kernel(MoveList m, double *__r
 
 // Insertion / removal of one molecule (grand-canonical moves), by value in the kernel arguments like a
 // MoveList: every per-atom array of the configuration and of sweep view 0 is patched in place.  A removed
-// atom keeps its coordinates and becomes a hole (flags = 0, q = alpha = eps = sigma = 0).
+// atom keeps its coordinates and becomes a hole (flags = 0, q = alpha = eps = sigma = 0).  The per-atom data of the dense
+// modes ride along: c6 / c8 / c10 of disp_expansion and the two three-body values of axilrod_teller (a hole gets the pad
+// values their setters write: zeros, and at_g = 1); a target pointer of a mode that is off is null and nothing is written.
 constexpr int kMaxEdit = 16;
 struct EditList {
     int n;
@@ -496,6 +498,8 @@ struct EditList {
     int mol[kMaxEdit], flags[kMaxEdit];
     double x[kMaxEdit], y[kMaxEdit], z[kMaxEdit], q[kMaxEdit], alpha[kMaxEdit], eps[kMaxEdit], sig[kMaxEdit],
         molmass[kMaxEdit];
+    double c6[kMaxEdit], c8[kMaxEdit], c10[kMaxEdit];  // disp_expansion (atomic units, as read)
+    double at_a[kMaxEdit], at_g[kMaxEdit];              // axilrod_teller: alpha * 6.7483345 and 1 / (c9 / a^3)
 };
 struct EditTargets {
     double *x, *y, *z, *q, *alpha, *eps, *sig, *molmass;
@@ -503,6 +507,8 @@ struct EditTargets {
     int *slot_of_atom, *idx_of_slot;
     double *px, *py, *pz, *palpha;
     int *pflags;
+    double *c6, *c8, *c10;  // null outside disp_expansion
+    double *at_a, *at_g;    // null outside axilrod_teller
 };
 
 __global__ __launch_bounds__(64) void apply_edits_kernel(EditList e, EditTargets t) {
@@ -522,6 +528,15 @@ __global__ __launch_bounds__(64) void apply_edits_kernel(EditList e, EditTargets
     t.molmass[a] = e.molmass[k];
     t.mol[a] = e.mol[k];
     t.flags[a] = e.flags[k];
+    if (t.c6) {
+        t.c6[a] = e.c6[k];
+        t.c8[a] = e.c8[k];
+        t.c10[a] = e.c10[k];
+    }
+    if (t.at_a) {
+        t.at_a[a] = e.at_a[k];
+        t.at_g[a] = e.at_g[k];
+    }
     t.slot_of_atom[a] = s;
     if (s >= 0) {
         t.idx_of_slot[s] = a;

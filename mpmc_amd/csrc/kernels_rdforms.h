@@ -281,8 +281,9 @@ __global__ __launch_bounds__(64 * kRdFormWaves) void rdform_tile_kernel(DevAtoms
 
 // Long-range correction of the LJ form (lj_lrc_corr / lj_lrc_self, lj.c:56-107): every pair that is not frozen-frozen,
 // same-molecule pairs included, whose MIXED eps_ij and sigma_ij are both non-zero, plus every non-frozen atom with its own
-// non-zero values.  Parameters, the cutoff and the volume only: made again at upload, set_rd_form and box change.  Always a
-// full pass (the mode has no device-side insert / remove).  grid = (npad/64 [J], npad/64 [I]), tile partials [I][J].
+// non-zero values.  Parameters, the cutoff, the volume and which atoms exist: a full pass at upload, set_rd_form and box
+// change; after mpmc_hip_edit_molecules only the tiles of the edited atoms' blocks are redone, like lj_lrc_kernel's.
+// Grids: owned_tile(); tile partials [I][J].
 constexpr int kRdFormLrcWaves = 8;
 __device__ __forceinline__ double rdform_lrc_term(double eps, double sig, double rc, double volume) {
     const double sc = fabs(sig) / rc;
@@ -292,9 +293,10 @@ __device__ __forceinline__ double rdform_lrc_term(double eps, double sig, double
     return ((16.0 / 3.0) * kPI * eps * s3) * ((1.0 / 3.0) * sc9 - sc3) / volume;
 }
 __global__ __launch_bounds__(64 * kRdFormLrcWaves) void rdform_lrc_kernel(DevAtoms a, DevBox bx, int mixing,
-                                                                           double *__restrict__ partials) {
-    const int I = blockIdx.y, J = blockIdx.x;
+                                                                           DirtyBlocks sel, double *__restrict__ partials) {
+    int I, J;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (!owned_tile(sel, I, J)) return;
     double *out = partials + (size_t)I * gridDim.x + J;
     if (J < I) {
         if (threadIdx.x == 0) out[0] = 0.0;

@@ -22,7 +22,7 @@ EXPORTS = [
     "mpmc_hip_set_cavity_grid", "mpmc_hip_cavity_bin", "mpmc_hip_cavity_update", "mpmc_hip_cavity_point",
     "mpmc_hip_download_cavity_grid",
     "mpmc_hip_set_exact_polar", "mpmc_hip_get_polarizability_tensor", "mpmc_hip_set_thole_model",
-    "mpmc_hip_update_atoms", "mpmc_hip_insert_molecule", "mpmc_hip_remove_molecule",
+    "mpmc_hip_update_atoms", "mpmc_hip_insert_molecule", "mpmc_hip_remove_molecule", "mpmc_hip_edit_molecules",
     "mpmc_hip_slot_count", "mpmc_hip_set_sweep_order", "mpmc_hip_energy", "mpmc_hip_energy_begin", "mpmc_hip_energy_end",
     "mpmc_hip_download_dipoles",
     "mpmc_hip_download_amatrix", "mpmc_hip_download_ranking", "mpmc_hip_get_timings",
@@ -132,6 +132,13 @@ class TholeModel(C.Structure):
     ]
 
 
+class Molecule(C.Structure):
+    """mpmc_hip_molecule: one molecule of mpmc_hip_edit_molecules()."""
+    _fields_ = [("count", C.c_int), ("frozen", C.c_int)] + [
+        (k, C.c_void_p) for k in ("x", "y", "z", "charge", "polarizability", "epsilon", "sigma", "mass",
+                                  "c6", "c8", "c10", "c9")]
+
+
 THOLE_DAMPINGS = {"off": 0, "none": 0, "linear": 1, "exponential": 2}  # the reference's DAMPING_* values
 RD_FORMS = {"off": 0, "lj": 1, "sg": 2, "dreiding": 3, "lj_buffered_14_7": 4}  # MPMC_HIP_RD_*
 RD_MIXINGS = {"lb": 0, "waldmanhagler": 1, "halgren_mixing": 2, "c6_mixing": 3}  # MPMC_HIP_RD_MIX_*
@@ -201,6 +208,7 @@ def load():
     lib.mpmc_hip_update_atoms.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     lib.mpmc_hip_insert_molecule.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
     lib.mpmc_hip_remove_molecule.argtypes = [vp, C.c_int, C.c_int]
+    lib.mpmc_hip_edit_molecules.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.POINTER(Molecule), vp]
     lib.mpmc_hip_slot_count.argtypes = [vp]
     lib.mpmc_hip_set_sweep_order.argtypes = [vp, C.c_int, vp]
     lib.mpmc_hip_energy.argtypes = [vp, C.POINTER(Result)]
@@ -527,6 +535,43 @@ class Engine:
         if rc < 0:
             _chk(rc)
         return rc == 0
+
+    def edit_molecules(self, remove=(), insert=()):
+        """Several molecules leave and enter in one call (mpmc_hip_edit_molecules), in every mode with device-side edits.
+        remove: (first, count) pairs, carried out first; insert: dicts with pos [k, 3], charge, alpha, epsilon, sigma,
+        mass and optionally frozen, c6, c8, c10 (read under disp_expansion) and c9 (the EFFECTIVE coefficient, read under
+        axilrod_teller).  Returns the list of the inserted molecules' first slots, or None when the engine asks for a
+        full upload instead (nothing has changed then)."""
+        remove = [(int(f), int(k)) for f, k in remove]
+        rf = np.ascontiguousarray([f for f, _ in remove], dtype=np.int32)
+        rk = np.ascontiguousarray([k for _, k in remove], dtype=np.int32)
+        mols = (Molecule * max(1, len(insert)))()
+        keep = []  # the arrays the structs point into
+        for m, d in zip(mols, insert):
+            pos = np.ascontiguousarray(d["pos"], dtype=np.float64).reshape(-1, 3)
+            m.count, m.frozen = pos.shape[0], int(bool(d.get("frozen", False)))
+            for k, name in enumerate("xyz"):
+                keep.append(np.ascontiguousarray(pos[:, k]))
+                setattr(m, name, keep[-1].ctypes.data)
+            for field, key in (("charge", "charge"), ("polarizability", "alpha"), ("epsilon", "epsilon"),
+                               ("sigma", "sigma"), ("mass", "mass"), ("c6", "c6"), ("c8", "c8"), ("c10", "c10"), ("c9", "c9")):
+                if d.get(key) is None:
+                    continue  # (a NULL pointer: the engine names a missing array its mode reads)
+                a = np.ascontiguousarray(d[key], dtype=np.float64)
+                if a.shape != (pos.shape[0],):
+                    raise ValueError("edit_molecules: %s must have one entry per atom of the molecule" % key)
+                keep.append(a)
+                setattr(m, field, a.ctypes.data)
+        first = np.full(max(1, len(insert)), -1, dtype=np.int32)
+        rc = self.lib.mpmc_hip_edit_molecules(self.ctx, len(remove), rf.ctypes.data if remove else None,
+                                              rk.ctypes.data if remove else None, len(insert),
+                                              mols if len(insert) else None, first.ctypes.data if len(insert) else None)
+        if rc < 0:
+            _chk(rc)
+        if rc > 0:
+            return None
+        self.n = int(self.lib.mpmc_hip_slot_count(self.ctx))
+        return [int(f) for f in first[:len(insert)]]
 
     def set_sweep_order(self, slots):
         """Gauss-Seidel modes after insert / remove: device slots of the polarizable atoms in the caller's atom order."""

@@ -108,6 +108,10 @@ def load():
     lib.host_get_cavity.restype = C.c_int
     lib.host_get_cavity_darts.argtypes = [vp, vp]
     lib.host_get_cavity_darts.restype = None
+    lib.host_get_sync_counts.argtypes = [vp, C.POINTER(C.c_long)]
+    lib.host_get_sync_counts.restype = None
+    lib.host_effective_c9.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double]
+    lib.host_effective_c9.restype = C.c_double
     lib.volume_change.argtypes = [vp]
     lib.volume_change.restype = None
     lib.revert_volume_change.argtypes = [vp]
@@ -285,6 +289,13 @@ class HostSystem:
     def force_volume_move(self, new_volume, revert=False):
         """One volume move to `new_volume` outside Metropolis and, on request, its revert (no energy evaluated)."""
         self.lib.host_force_volume_move(self.ptr, float(new_volume), int(bool(revert)))
+
+    def sync_counts(self):
+        """How the binding has kept the device in line so far (host_get_sync_counts): full uploads, edit calls that were
+        carried out (mpmc_hip_edit_molecules), molecules those calls removed + inserted."""
+        out = (C.c_long * 3)()
+        self.lib.host_get_sync_counts(self.ptr, out)
+        return dict(full_uploads=int(out[0]), edit_calls=int(out[1]), molecules_edited=int(out[2]))
 
     def mc_steps(self, nsteps):
         r = self.lib.host_mc_steps(self.ptr, int(nsteps))

@@ -352,6 +352,12 @@ void host_get_npt(system_t *system, double out[5]) {
 }
 /* 0 = energy_hip() ignores volume-move notes: every volume step uploads the whole configuration (A/B, tests) */
 void host_set_volume_notes(system_t *system, int on) { energy_hip_set_volume_notes(system, on); }
+/* full uploads, edit calls carried out, molecules they removed + inserted (energy_hip_sync_counts) */
+void host_get_sync_counts(system_t *system, long out[3]) { energy_hip_sync_counts(system, out); }
+/* the per-atom c9 the binding sends (energy_hip_effective_c9) */
+double host_effective_c9(int midzuno_kihara_approx, double alpha, double c6, double c9) {
+    return energy_hip_effective_c9(midzuno_kihara_approx, alpha, c6, c9);
+}
 /* One volume move to a stated new volume, outside Metropolis, so that tests reach both branches: exactly what
  * make_move() does for MOVETYPE_VOLUME except that the new volume is given instead of drawn (as the reference's
  * ENSEMBLE_REPLAY branch, mc_moves.c:176-178), and on request exactly what restore() does to take it back.  The

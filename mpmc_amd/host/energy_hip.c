@@ -99,6 +99,7 @@ typedef struct shim_state {
     double *cav_darts; /* [cav_ndarts][3]: the last call's dart positions */
     int cav_ndarts, cav_darts_cap, cav_hits;
     int cav_failed; /* a device / ABI failure in a cavity call: the next energy_hip() reports it (sticky) */
+    long sync_counts[3]; /* full uploads, mpmc_hip_edit_molecules calls that answered 0, molecules they removed + inserted */
     int timing;
     mpmc_hip_timings tsum;
     int walker_rank, walker_nranks;
@@ -451,6 +452,12 @@ static int same_type(const char *a, const char *b) {
     return 1;
 }
 
+/* The per-atom coefficient mpmc_hip_set_axilrod_teller() and mpmc_hip_edit_molecules() take: c9 as read, or the
+ * Midzuno-Kihara replacement (axilrod_teller.cpp:114-118, the same expression left to right). */
+double energy_hip_effective_c9(int midzuno_kihara_approx, double alpha, double c6, double c9) {
+    return midzuno_kihara_approx ? 3.0 / 4.0 * alpha * 6.7483345 * c6 : c9;
+}
+
 /* whole configuration, slots = list order */
 static int full_upload(shim_state *st, system_t *system) {
     const int n = system->natoms;
@@ -506,15 +513,14 @@ static int full_upload(shim_state *st, system_t *system) {
     if (st->disp.disp_expansion && mpmc_hip_set_dispersion(st->ctx, &st->disp, n, st->c6, st->c8, st->c10))
         return hip_fail("set_dispersion");
     if (system->axilrod_teller) {
-        /* the engine takes the EFFECTIVE per-atom coefficient: c9 as read, or the Midzuno-Kihara replacement
-         * (axilrod_teller.cpp:114-118, the same expression left to right) */
+        /* the engine takes the EFFECTIVE per-atom coefficient */
         double *eff = malloc((n > 0 ? n : 1) * sizeof(double));
         if (!eff) {
             error("ENERGY: HIP engine: out of host memory\n");
             return -1;
         }
         for (int k = 0; k < n; k++)
-            eff[k] = system->midzuno_kihara_approx ? 3.0 / 4.0 * st->alpha[k] * 6.7483345 * st->c6[k] : st->c9[k];
+            eff[k] = energy_hip_effective_c9(system->midzuno_kihara_approx, st->alpha[k], st->c6[k], st->c9[k]);
         rc = mpmc_hip_set_axilrod_teller(st->ctx, 1, n, eff);
         free(eff);
         if (rc) return hip_fail("set_axilrod_teller");
@@ -547,6 +553,7 @@ static int full_upload(shim_state *st, system_t *system) {
     st->uploaded = 1;
     st->in_sync = 1;
     st->nnotes = 0;
+    st->sync_counts[0]++;
     drop_volume_notes(st);
     return 0;
 }
@@ -581,6 +588,12 @@ void energy_hip_note_volume_change(system_t *system, const double *delta_per_mol
     }
     memcpy(copy, delta_per_molecule, (size_t)st->nres * 3 * sizeof(double));
     st->vol_delta[st->nvol++] = copy;
+}
+/* how energy_hip() has kept the device in line so far: full uploads, edit calls that were carried out, molecules they
+ * removed + inserted (zeros before the first call) */
+void energy_hip_sync_counts(system_t *system, long out[3]) {
+    shim_state *st = state_of(system, 0);
+    for (int k = 0; k < 3; k++) out[k] = st ? st->sync_counts[k] : 0;
 }
 void energy_hip_set_volume_notes(system_t *system, int on) {
     shim_state *st = state_of(system, 1);
@@ -694,7 +707,10 @@ static int sync_noted(shim_state *st) {
  * back: a node that holds exactly what a resident's slots hold is that resident; otherwise the node is NEW if the
  * node behind it is the resident (a grand-canonical insertion goes in front of the molecule it was copied from,
  * mc_moves.c:626-637), the resident is GONE if the node is the next resident (a removal, or restore() taking an
- * insertion back), and else the node is the resident DISPLACED if it is the same species site by site.  Only what
+ * insertion back), in the dense modes the same two one place further on (restore() undoing one trial and make_move()
+ * making the next can leave two new nodes or two gone residents side by side, and read as displacements they would shift
+ * every molecule behind them by one until the walk gives up), and else the node is the resident DISPLACED if it is the same species
+ * site by site.  Only what
  * the device holds matters -- which atoms at which coordinates, and for the Gauss-Seidel solvers in which order --
  * so "the rejected insertion was taken out and its neighbour displaced" may legitimately be carried out as "the
  * rejected insertion's slots get the neighbour's new coordinates and the neighbour's slots are freed".
@@ -707,6 +723,10 @@ static int sync_walk(shim_state *st, system_t *system) {
     resident_t *res = st->res, *out = st->res2;
     int gone[8], ngone = 0, fresh[8], nfresh = 0, moved[16], nmoved = 0;
     int i = 0, j = 0, n2 = 0, natoms = 0;
+    /* The look two places ahead (above) is taken in the dense modes only, where every change of N used to be an upload.
+     * On the standard path the walk stays as it was: where it gives up and uploads decides the slot order, the slot order
+     * the rounding of the sums, and the bits of such chains are on record (tests/golden). */
+    const int two_ahead = st->disp.disp_expansion || system->axilrod_teller || st->rdc_order || st->rd_form.form;
     while (i < nm || j < st->nres) {
         if (i < nm && j < st->nres && same_place(st, mols[i], &res[j])) {
             out[n2] = res[j++];
@@ -716,6 +736,17 @@ static int sync_walk(shim_state *st, system_t *system) {
             if (ngone == 8) return 1;
             gone[ngone++] = j++;
         } else if (i + 1 < nm && j < st->nres && same_place(st, mols[i + 1], &res[j])) {
+            if (nfresh == 8) return 1;
+            fresh[nfresh++] = n2;
+            out[n2].mol = mols[i++]; out[n2].atoms = out[n2].mol->atoms; out[n2].slot = -1; out[n2].natoms = natoms_of(out[n2].mol);
+            out[n2].frozen = (out[n2].mol->frozen != 0);
+            n2++;
+        } else if (two_ahead && i < nm && j + 2 < st->nres && same_place(st, mols[i], &res[j + 2])) {
+            /* two residents in a row are gone: a rejected insertion taken back and the molecule beside it removed */
+            if (ngone == 8) return 1;
+            gone[ngone++] = j++;
+        } else if (two_ahead && i + 2 < nm && j < st->nres && same_place(st, mols[i + 2], &res[j])) {
+            /* two new nodes in a row: a rejected removal put back and an insertion beside it */
             if (nfresh == 8) return 1;
             fresh[nfresh++] = n2;
             out[n2].mol = mols[i++]; out[n2].atoms = out[n2].mol->atoms; out[n2].slot = -1; out[n2].natoms = natoms_of(out[n2].mol);
@@ -739,34 +770,60 @@ static int sync_walk(shim_state *st, system_t *system) {
         } else
             return 1;
     }
-    /* removals first, so that an insertion of the same size can take the slots */
-    for (int f = 0; f < ngone; f++) {
-        const int rc = mpmc_hip_remove_molecule(st->ctx, res[gone[f]].slot, res[gone[f]].natoms);
-        if (rc < 0) return hip_fail("remove_molecule");
+    /* one call for both lists: the engine removes first, so that an insertion of the same size can take the slots, and
+     * answers 1 before it has changed anything */
+    if (ngone || nfresh) {
+        enum { kMol = 8, kAt = 16 }; /* the engine's limits: beyond them it would answer 1 */
+        double buf[13][kMol][kAt]; /* x y z q alpha eps sig mass c6 c8 c10 c9(effective) c9(as read) */
+        double dw[kMol][kAt];
+        mpmc_hip_molecule ins[kMol];
+        int rfirst[kMol], rcount[kMol], slot[kMol];
+        for (int f = 0; f < ngone; f++) {
+            rfirst[f] = res[gone[f]].slot;
+            rcount[f] = res[gone[f]].natoms;
+        }
+        for (int f = 0; f < nfresh; f++) {
+            resident_t *r = &out[fresh[f]];
+            int k = 0;
+            for (atom_t *a = r->mol->atoms; a; a = a->next, k++) {
+                if (k == kAt) return 1;
+                buf[0][f][k] = a->pos[0]; buf[1][f][k] = a->pos[1]; buf[2][f][k] = a->pos[2];
+                buf[3][f][k] = a->charge; buf[4][f][k] = a->polarizability; buf[5][f][k] = a->epsilon;
+                buf[6][f][k] = a->sigma; buf[7][f][k] = a->mass;
+                buf[8][f][k] = a->c6; buf[9][f][k] = a->c8; buf[10][f][k] = a->c10;
+                buf[11][f][k] = energy_hip_effective_c9(system->midzuno_kihara_approx, a->polarizability, a->c6, a->c9);
+                buf[12][f][k] = a->c9;
+                dw[f][k] = a->omega;
+            }
+            mpmc_hip_molecule *m = &ins[f];
+            m->count = k; m->frozen = r->frozen;
+            m->x = buf[0][f]; m->y = buf[1][f]; m->z = buf[2][f]; m->charge = buf[3][f]; m->polarizability = buf[4][f];
+            m->epsilon = buf[5][f]; m->sigma = buf[6][f]; m->mass = buf[7][f];
+            m->c6 = buf[8][f]; m->c8 = buf[9][f]; m->c10 = buf[10][f]; m->c9 = buf[11][f];
+            slot[f] = -1;
+        }
+        const int rc = mpmc_hip_edit_molecules(st->ctx, ngone, rfirst, rcount, nfresh, ins, slot);
+        if (rc < 0) return hip_fail("edit_molecules");
         if (rc > 0) return 1;
-    }
-    for (int f = 0; f < nfresh; f++) {
-        resident_t *r = &out[fresh[f]];
-        double tx[64], ty[64], tz[64], q[64], al[64], ep[64], sg[64], ms[64];
-        double d6[64], d8[64], d10[64], d9[64], dw[64]; /* not sent (Lennard-Jones mode), but part of the image same_species() reads */
-        int k = 0;
-        for (atom_t *a = r->mol->atoms; a; a = a->next, k++) {
-            if (k == 64) return 1;
-            tx[k] = a->pos[0]; ty[k] = a->pos[1]; tz[k] = a->pos[2];
-            q[k] = a->charge; al[k] = a->polarizability; ep[k] = a->epsilon; sg[k] = a->sigma; ms[k] = a->mass;
-            d6[k] = a->c6; d8[k] = a->c8; d10[k] = a->c10; d9[k] = a->c9; dw[k] = a->omega;
+        st->sync_counts[1]++;
+        st->sync_counts[2] += ngone + nfresh;
+        for (int f = 0; f < nfresh; f++) {
+            resident_t *r = &out[fresh[f]];
+            const int s = slot[f], k = ins[f].count;
+            if (s < 0 || s + k > st->cap) {
+                st->uploaded = 0; /* (cannot happen: the image was reserved for the context's capacity) */
+                return 1;
+            }
+            for (int a = 0; a < k; a++) {
+                st->x[s + a] = buf[0][f][a]; st->y[s + a] = buf[1][f][a]; st->z[s + a] = buf[2][f][a];
+                st->q[s + a] = buf[3][f][a]; st->alpha[s + a] = buf[4][f][a]; st->eps[s + a] = buf[5][f][a];
+                st->sig[s + a] = buf[6][f][a]; st->mass[s + a] = buf[7][f][a];
+                st->c6[s + a] = buf[8][f][a]; st->c8[s + a] = buf[9][f][a]; st->c10[s + a] = buf[10][f][a];
+                st->c9[s + a] = buf[12][f][a];
+                st->omega[s + a] = dw[f][a];
+            }
+            r->slot = s;
         }
-        int s = -1;
-        const int rc = mpmc_hip_insert_molecule(st->ctx, k, tx, ty, tz, q, al, ep, sg, ms, r->frozen, &s);
-        if (rc < 0) return hip_fail("insert_molecule");
-        if (rc > 0 || s < 0 || s + k > st->cap) return 1;
-        for (int a = 0; a < k; a++) {
-            st->x[s + a] = tx[a]; st->y[s + a] = ty[a]; st->z[s + a] = tz[a];
-            st->q[s + a] = q[a]; st->alpha[s + a] = al[a]; st->eps[s + a] = ep[a]; st->sig[s + a] = sg[a]; st->mass[s + a] = ms[a];
-            st->c6[s + a] = d6[a]; st->c8[s + a] = d8[a]; st->c10[s + a] = d10[a]; st->c9[s + a] = d9[a];
-            st->omega[s + a] = dw[a];
-        }
-        r->slot = s;
     }
     for (int f = 0; f < nmoved; f++) {
         const int rc = sync_coordinates(st, out[moved[f]].mol, &out[moved[f]]);

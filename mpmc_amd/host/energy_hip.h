@@ -51,6 +51,13 @@ void energy_hip_note_volume_change(system_t *system, const double *delta_per_mol
 /* on = 0: volume notes are ignored (the full upload of an un-hooked caller; for A/B measurement and tests) */
 void energy_hip_set_volume_notes(system_t *system, int on);
 
+/* How energy_hip() has kept the device in line with the lists since the first call: out[0] full uploads, out[1] calls of
+ * mpmc_hip_edit_molecules() that were carried out (grand-canonical insertions / removals without a re-upload), out[2]
+ * molecules those calls removed + inserted. */
+void energy_hip_sync_counts(system_t *system, long out[3]);
+/* the per-atom c9 the engine is given: as read, or 3/4 alpha 6.7483345 c6 under midzuno_kihara_approx */
+double energy_hip_effective_c9(int midzuno_kihara_approx, double alpha, double c6, double c9);
+
 /* atom->mu / ef_static / ef_induced / ef_induced_change as polar() leaves them; called where the reference
  * reads them (write_dipole() / write_field() at corrtime, src/mc/mc.c:398-414) instead of on every step */
 int energy_hip_download_dipoles(system_t *system);
