@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "step_pods.h"  // DirtyBlocks, SweepParams, BlockList, GsBuild: kernel arguments the host's plans fill in
+
 namespace mpmc {
 
 // reference src/include/defines.h:7-61
@@ -23,16 +25,6 @@ constexpr double kOneOverSqrtPi = 0.56418958354;  // reference src/polarization/
 constexpr int kWave = 64;
 
 enum AtomFlag : int { kFrozen = 1, kValid = 2 };
-
-// 64-atom blocks (atom order) that hold an atom moved since the last energy(); carried in the kernel
-// arguments.  n == 0 means "everything": the tiled pair/field kernels then cover their whole grid,
-// otherwise only the tiles that touch one of these blocks (their partial sums persist in HBM, and a
-// tile's partial is a function of its two blocks' atoms only, so the result is bit-identical).
-constexpr int kMaxDirtyBlocks = 16;
-struct DirtyBlocks {
-    int n;
-    int blk[kMaxDirtyBlocks];
-};
 
 // Periodic cell, passed by value (lands in SGPRs / kernarg).
 struct DevBox {

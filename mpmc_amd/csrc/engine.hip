@@ -24,7 +24,6 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <memory>
 #include <tuple>
@@ -36,6 +35,7 @@
 #include <vector>
 
 #include "device_common.h"
+#include "step_plan.h"
 #include "kernels_pair.h"
 #include "kernels_disp.h"
 #include "kernels_rdforms.h"
@@ -351,9 +351,13 @@ struct CallState {
     bool rank_on_side = false;        // ranking metric computed and copied to the host on the side stream
     int gs_sweeps = 0;                // Gauss-Seidel sweeps enqueued so far
     bool gs_used[2] = {false, false};  // the persistent kernel ran on view 0 / 1: its error word travels with the record
-    std::function<void()> enqueue_side;  // set while run_polarization() may feed the side stream (see enqueue_direct)
-    std::function<void()> publish_early;  // set while run_polarization() may launch the publish kernel itself, behind the
-    bool published = false;               //   finish that completes U_pol (see enqueue_direct); published: it did
+    bool polar_first = false;     // the chain is enqueued up to its first sweep before the side stream is fed (plan_call)
+    bool side_open = false;       // run_polarization() may feed the side stream now (feed_side_stream; see enqueue_direct)
+    bool side_done = false;       // enqueue_side_stream() has run in this call ...
+    int side_rc = 0;              //   ... and returned this
+    bool may_publish_early = false;  // this call may publish behind the finish of sweep m = ceil(n / 2), the finish that
+    bool published = false;          //   completes U_pol (publish_early; see enqueue_direct); published: it did ...
+    int publish_rc = 0;              //   ... and launch_publish() returned this
     bool recip_fused = false;     // the reciprocal-space partials rode in the pair kernel's launch
     int recip_chunks = 0;         // chunk sums the publish kernel folds (0: R_RECIP was written directly)
     int pair_rows_to_sum = 0;     // tile partials of the pair kernel the publish kernel has to add up
@@ -686,7 +690,6 @@ static TholeParams thole_params(const mpmc_hip_ctx *c, const int *idx) {
         default: { constexpr int kM = kTholeExp; __VA_ARGS__; break; }                \
     } while (0)
 
-static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static int complete_pending_sweep(mpmc_hip_ctx *c);  // engine_polar.inc
 template <int NRHS>
 static int exact_substitute(mpmc_hip_ctx *c, int nv, int nvpad, const double *es);  // engine_polar.inc
@@ -1641,6 +1644,10 @@ extern "C" int mpmc_hip_get_close_contacts(mpmc_hip_ctx *c, long long *count) {
 // a moved coordinate before its own writer) -- or, when the move reached the device another way (edits, staged copies),
 // wait for the event the main stream recorded behind it.
 static void side_wait_for_moves(mpmc_hip_ctx *c, hipStream_t s);
+// What the polarization chain (engine_polar.inc) calls at the points where the device has work queued: both do nothing
+// outside the window enqueue_direct() opens for them, and nothing the second time.
+static void feed_side_stream(mpmc_hip_ctx *c);  // the LJ / Ewald launches of the call (enqueue_side_stream)
+static void publish_early(mpmc_hip_ctx *c);     // the publish launch, behind the finish that completes U_pol
 static int flush_moves(mpmc_hip_ctx *c) {
     if (c->pending.n > 0) {
         // (outside an evaluation: a pending sweep reads the view's coordinates; energy_begin() has dropped it by now)
@@ -1911,31 +1918,10 @@ static int insert_checked(mpmc_hip_ctx *c, int count, const double *x, const dou
                           const double *polarizability, const double *epsilon, const double *sigma, const double *mass,
                           int frozen, const DenseAtomData &dd, int *first_slot);
 
-// Where a molecule of `count` atoms goes: the most recent hole of exactly that size, else new slots at the end.  hole: its
-// index in `holes`, or -1.  false: the context is full.
-static bool place_molecule(const std::vector<std::pair<int, int>> &holes, int n, int max_atoms, int count, int &first,
-                           int &hole) {
-    first = hole = -1;
-    for (int h = (int)holes.size() - 1; h >= 0; --h)
-        if (holes[h].second == count) {
-            hole = h;
-            first = holes[h].first;
-            return true;
-        }
-    if (n + count > max_atoms) return false;
-    first = n;
-    return true;
-}
+// (where a molecule goes: place_molecule(), step_plan.h)
 // View slots an insertion at `first` appends: a polarizable site takes the atom slot's old view slot if it has one.
 static int new_view_slots(const mpmc_hip_ctx *c, int first, int count, const double *polarizability) {
-    const SweepView &v0 = c->view[0];
-    const bool gs_mode = gs_order_mode(c);
-    int new_view = 0;
-    for (int i = 0; i < count; ++i) {
-        const bool had = !gs_mode && first + i < (int)v0.slot_of_atom.size() && v0.slot_of_atom[first + i] >= 0;
-        if (polarizability[i] != 0.0 && !had) ++new_view;
-    }
-    return new_view;
+    return count_new_view_slots(c->view[0].slot_of_atom, gs_order_mode(c), first, count, polarizability);
 }
 
 extern "C" int mpmc_hip_remove_molecule(mpmc_hip_ctx *c, int first, int count) {
@@ -2893,23 +2879,6 @@ static int launch_publish(mpmc_hip_ctx *c) {
     return 0;
 }
 
-// atoms -> the 64-atom blocks they are in, each once (unused entries zero); false: more blocks than the list holds
-static bool blocks_of(const std::vector<int> &atoms, DirtyBlocks &out) {
-    memset(&out, 0, sizeof(out));
-    for (int atom : atoms) {
-        const int b = atom / 64;
-        bool seen = false;
-        for (int k = 0; k < out.n; ++k) seen |= (out.blk[k] == b);
-        if (seen) continue;
-        if (out.n == kMaxDirtyBlocks) {
-            memset(&out, 0, sizeof(out));
-            return false;
-        }
-        out.blk[out.n++] = b;
-    }
-    return true;
-}
-
 // 64-atom blocks touched by the moves since the last call (n = 0: recompute every tile)
 static void collect_dirty_blocks(mpmc_hip_ctx *c) {
     DirtyBlocks &d = c->call.dirty_blocks;
@@ -2930,8 +2899,9 @@ static void begin_call(mpmc_hip_ctx *c) {
     collect_dirty_blocks(c);
 }
 
-// One evaluation, launch by launch (also what stream capture records for the step graph).
-static int enqueue_direct(mpmc_hip_ctx *c) {
+// The predicates of the call, from the parameters, the options and what is pending: launches nothing, changes nothing but
+// c->call.
+static void plan_call(mpmc_hip_ctx *c) {
     const mpmc_hip_params &P = c->par;
     CallState &k = c->call;
     k.do_polar = !P.rd_only && P.polarization;
@@ -2959,145 +2929,19 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
     // (The long-range-correction and self-term kernels in front of it read parameters only.)
     k.moves_in_pair = !k.moves_deferred && c->opt.fuse_moves && c->pending.n > 0 && k.plain_launches && !do_polar &&
                       !c->dirty_atoms.empty();
-    if (!k.moves_deferred && !k.moves_in_pair) {
-        if (c->opt.side_moves && !c->main_writes && c->pending.n > 0 && two_streams && k.plain_launches)
-            k.side_apply = c->pending;  // (the side stream applies it too: no fork event, see side_wait_for_moves)
-        if (flush_moves(c)) return -1;
-    } else if (k.moves_deferred && k.gs_mode) {
-        if (c->opt.side_moves && !c->main_writes) k.side_apply = c->pending;  // (else: the fork event behind the coefficient job)
-    }
     // (the pair kernel is launched whenever an atom moved; the long-range-correction kernels in front of it read
     //  parameters only)
     k.side_carry = k.moves_deferred && !k.gs_mode && c->opt.side_moves && !c->main_writes && !c->dirty_atoms.empty() &&
                    c->pending.n <= kMaxMoves;
-    if (is_timed_call(c)) hipEventRecord(c->ev_first, c->stream);
-
-    const DevAtoms a = dev_atoms(c);
-    const DevBox bx = dev_box(c);
-    const int ntile = c->npad / 64;
-    int polar_iterations = 0, iter_success = 0;
-
-    hipStream_t sb = two_streams ? c->stream2 : c->stream;
     // The side stream publishes its own slots of the record (no join event) in the Jacobi-type modes; the Gauss-Seidel
     // modes keep the join (their ranking kernels share slots and streams with the chain), and so does graph capture.
     k.split = two_streams && c->opt.split_record && !k.gs_mode && k.plain_launches;
-    if (two_streams && !k.moves_deferred && k.side_apply.n == 0)
-        hipEventRecord(c->ev_fork, c->stream);  // (the side stream's wait is issued when it is fed)
     // Enqueue order: the host needs ~3 us per launch and the polarization chain is the critical path, so
     // with a fixed iteration count the chain is enqueued up to its first sweep (by then the device has
     // ~40 us of work queued), then the side-stream kernels, then the remaining sweeps (option "side_after":
     // after 1, 2 and 3 sweeps measured 5 910 / 5 820 / 5 750 steps/s, within box noise); in precision mode
     // the chain synchronises with the host every iteration, so the side stream is fed first.
-    const bool polar_first = do_polar && two_streams && P.polar_precision == 0.0;
-    int side_rc = 0;
-    bool side_done = false;
-    auto enqueue_side = [&]() {
-        if (side_done) return;
-        side_done = true;
-        side_rc = [&]() -> int {
-        // after apply_moves: the new coordinates are in place (unless this stream's pair kernel brings the move itself)
-        if (two_streams && !(k.side_carry && k.side_moves.n > 0)) side_wait_for_moves(c, sb);
-        // ---- the static sums depend on parameters, the volume and WHICH atoms exist -- not on coordinates: summed once,
-        // their tile partials kept, and only the tiles of inserted / removed atoms' blocks redone afterwards.  The list of
-        // those atoms is read here, by every static sum of the call (this one, launch_disp / launch_rdc / launch_rdform),
-        // and cleared behind the last of them.
-        const bool lrc_overflow = !blocks_of(c->lrc_dirty_atoms, k.lrc_blocks);
-        k.lrc_edited = !c->lrc_dirty_atoms.empty();
-        // ---- LJ long-range correction (lj.c:56-107)
-        if (P.rd_lrc) {
-            DirtyBlocks lsel;
-            const bool stale = lrc_selection(c, !c->lrc.valid || lrc_overflow, lsel);
-            if (static_pass(c, c->lrc, stale, ntile * ntile, R_LRC, sb, [&] {
-                    hipLaunchKernelGGL(lj_lrc_kernel, dim3(ntile, lsel.n > 0 ? lsel.n : ntile), dim3(64 * kLrcWaves), 0, sb, a, bx,
-                                       lsel, c->lrc.part);
-                }))
-                return -1;
-        } else {
-            k.res_zero_mask |= 1u << R_LRC;  // (zeroed by the publish kernel: a memset is a launch of its own)
-            c->lrc.valid = false;
-        }
-
-        // ---- fused pair kernel: LJ(+FH) and real-space Ewald(+FH, + intra-molecular screening)
-        const bool ewald_recip = !P.rd_only && !P.wolf && c->nk > 0;
-        if (ewald_recip) {
-            // partial structure factors per 64-atom block stay resident; only the moved blocks are redone
-            const size_t need = (size_t)(c->max_npad / 64) * c->nk;
-            const size_t nchunk = (c->nk + 63) / 64;
-            if (c->d_sfpart.size() < need || c->d_recipsum.size() < nchunk) {
-                HIPCHK(c->d_sfpart.alloc(need));
-                HIPCHK(c->d_recipsum.alloc(nchunk));
-                c->recip_part_valid = false;
-            }
-        }
-        {
-            ScopedTimer t(c, T_PAIR, sb);
-            if (launch_pair_kernel(c, a, bx, sb, ewald_recip)) return -1;
-            if (two_streams) {
-                // beside the polarization chain the sum is free on the side stream, and would be 3.5 us of the main one
-                hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(kReduceThreads), 0, sb, c->d_pairpart, ntile * ntile,
-                                   kPairChannels, c->d_res + R_RD_PAIR);
-                k.pair_rows_to_sum = 0;
-            } else {
-                k.pair_rows_to_sum = ntile * ntile;  // summed by the publish kernel (same arithmetic, one launch less)
-            }
-        }
-        // ---- disp_expansion: exp repulsion + damped C6 / C8 / C10 over ALL pairs, and its long-range correction
-        if (c->disp_on) {
-            if (launch_disp(c, a, bx, sb)) return -1;
-            k.res_zero_mask |= 1u << R_RDC_SELF;
-        } else if (c->rdc_order) {
-            // ---- rd_crystal: Lennard-Jones over the lattice images, its self part and its long-range correction
-            if (launch_rdc(c, a, bx, sb)) return -1;
-        } else if (c->vdw_on) {
-            // ---- polarvdw: repulsion-only Lennard-Jones, then the coupled-dipole term (it owns R_AT and R_RDC_SELF here)
-            if (launch_vdw(c, a, bx, sb)) return -1;
-        } else if (c->rd_form) {
-            // ---- set_rd_form: the dense sum of the form, and the LJ form's long-range correction
-            if (launch_rdform(c, a, bx, sb)) return -1;
-            k.res_zero_mask |= 1u << R_RDC_SELF;
-        } else {
-            k.res_zero_mask |= (1u << R_DISP) | (1u << R_DISP_LRC) | (1u << R_RDC_SELF);
-        }
-        // ---- axilrod_teller: the triple-dipole sum over ALL triples that are not on one molecule
-        if (c->at_on) {
-            if (launch_at(c, a, bx, sb)) return -1;
-        } else if (!c->vdw_on) {
-            k.res_zero_mask |= 1u << R_AT;
-        }
-        c->lrc_dirty_atoms.clear();  // (every static sum of the call has consumed it)
-
-        // ---- reciprocal + self (absent under Wolf summation, coulombic.c:27-28)
-        if (!P.rd_only && !P.wolf) {
-            ScopedTimer t(c, T_RECIP, sb);
-            if (c->nk > 0) {
-                if (!k.recip_fused && launch_recip_partial(c, a, sb)) return -1;
-                hipLaunchKernelGGL(recip_sum_kernel, dim3((c->nk + 63) / 64), dim3(64 * kRecipGroups), 0, sb, c->d_kvec,
-                                   c->nk, ntile, c->d_sfpart, c->d_recipsum);
-                k.recip_chunks = (c->nk + 63) / 64;
-            } else {
-                k.res_zero_mask |= 1u << R_RECIP;
-            }
-            // depends on the charges and alpha only: summed at upload / edit / parameter change, then kept in d_res
-            if (!c->self_valid || c->self_alpha != c->ewald_alpha) {
-                hipLaunchKernelGGL(ewald_self_kernel, dim3(1), dim3(256), 0, sb, a, c->ewald_alpha, c->d_res + R_SELF);
-                c->self_valid = true;
-                c->self_alpha = c->ewald_alpha;
-            }
-        } else {
-            k.res_zero_mask |= (1u << R_RECIP) | (1u << R_SELF);
-            c->self_valid = false;
-        }
-        if (k.split)
-            hipLaunchKernelGGL(publish_side_kernel, dim3(1), dim3(64), 0, sb, c->d_res, c->h_res2_dev, (int)R_COUNT,
-                               (double)c->energy_calls, (const double *)c->d_recipsum, k.recip_chunks, k.res_zero_mask,
-                               kSideSlots);
-        else if (two_streams)
-            hipEventRecord(c->ev_join, sb);
-        return 0;
-        }();
-    };
-    k.enqueue_side = polar_first ? std::function<void()>(enqueue_side) : std::function<void()>();
-    if (!polar_first) enqueue_side();
+    k.polar_first = do_polar && two_streams && P.polar_precision == 0.0;
     // Early publication.  A fixed-count Jacobi solve whose last sweep is deferred knows U_pol after the finish of sweep
     // ceil(n / 2) (engine_polar.inc, defer_last_sweep()); sweeps up to n - 1 serve only a later reader of the dipoles.  With
     // the side stream publishing its own slots nothing else of the record is the main stream's, so run_polarization()
@@ -3105,33 +2949,171 @@ static int enqueue_direct(mpmc_hip_ctx *c) {
     // dipoles (PendingSweep): the next call's launches queue right behind the record.  Not when the call is
     // timed with events (ev_last marks the end of the chain) nor in a captured step: both keep the placement at the end,
     // and the same bits (tests/test_gpu_early_publish.py holds a timed context against an untimed one).
-    int publish_rc = 0;
-    if (k.split && polar_first && !is_timed_call(c))
-        k.publish_early = [&]() {
-            if (k.published || k.build_join_pending) return;
-            k.published = true;
-            publish_rc = launch_publish(c);
-        };
-    {
-        // ---- polarization (main stream)
-        if (do_polar) {
-            const int rc = run_polarization(c, a, bx, &polar_iterations, &iter_success);
-            k.publish_early = nullptr;
-            if (rc || publish_rc) {
-                k.enqueue_side = nullptr;
-                return -1;
-            }
-            if (k.moves_deferred) return fail("MPMC_HIP: internal: a deferred move was not applied");
-        } else {
-            k.res_zero_mask |= (1u << R_UPOL) | (1u << R_RRMS);
-        }
-        // the resident A only tracks moves while it is being maintained
-        if (!do_polar || P.polar_zodid) c->view[0].A_valid = c->view[0].C_valid = false;
+    k.may_publish_early = k.split && k.polar_first && !is_timed_call(c);
+}
+
+// The side stream's launches of the call: the static sums, the pair kernel, the dense terms, reciprocal space and self
+// term, and its own part of the record (or the join event).  On the main stream when the call has only one.
+static int enqueue_side_stream(mpmc_hip_ctx *c) {
+    const mpmc_hip_params &P = c->par;
+    CallState &k = c->call;
+    const bool two_streams = k.two_streams;
+    const DevAtoms a = dev_atoms(c);
+    const DevBox bx = dev_box(c);
+    const int ntile = c->npad / 64;
+    hipStream_t sb = two_streams ? c->stream2 : c->stream;
+    // after apply_moves: the new coordinates are in place (unless this stream's pair kernel brings the move itself)
+    if (two_streams && !(k.side_carry && k.side_moves.n > 0)) side_wait_for_moves(c, sb);
+    // ---- the static sums depend on parameters, the volume and WHICH atoms exist -- not on coordinates: summed once,
+    // their tile partials kept, and only the tiles of inserted / removed atoms' blocks redone afterwards.  The list of
+    // those atoms is read here, by every static sum of the call (this one, launch_disp / launch_rdc / launch_rdform),
+    // and cleared behind the last of them.
+    const bool lrc_overflow = !blocks_of(c->lrc_dirty_atoms, k.lrc_blocks);
+    k.lrc_edited = !c->lrc_dirty_atoms.empty();
+    // ---- LJ long-range correction (lj.c:56-107)
+    if (P.rd_lrc) {
+        DirtyBlocks lsel;
+        const bool stale = lrc_selection(c, !c->lrc.valid || lrc_overflow, lsel);
+        if (static_pass(c, c->lrc, stale, ntile * ntile, R_LRC, sb, [&] {
+                hipLaunchKernelGGL(lj_lrc_kernel, dim3(ntile, lsel.n > 0 ? lsel.n : ntile), dim3(64 * kLrcWaves), 0, sb, a, bx,
+                                   lsel, c->lrc.part);
+            }))
+            return -1;
+    } else {
+        k.res_zero_mask |= 1u << R_LRC;  // (zeroed by the publish kernel: a memset is a launch of its own)
+        c->lrc.valid = false;
     }
-    k.enqueue_side = nullptr;
-    k.publish_early = nullptr;
-    enqueue_side();
-    if (side_rc) return -1;
+
+    // ---- fused pair kernel: LJ(+FH) and real-space Ewald(+FH, + intra-molecular screening)
+    const bool ewald_recip = !P.rd_only && !P.wolf && c->nk > 0;
+    if (ewald_recip) {
+        // partial structure factors per 64-atom block stay resident; only the moved blocks are redone
+        const size_t need = (size_t)(c->max_npad / 64) * c->nk;
+        const size_t nchunk = (c->nk + 63) / 64;
+        if (c->d_sfpart.size() < need || c->d_recipsum.size() < nchunk) {
+            HIPCHK(c->d_sfpart.alloc(need));
+            HIPCHK(c->d_recipsum.alloc(nchunk));
+            c->recip_part_valid = false;
+        }
+    }
+    {
+        ScopedTimer t(c, T_PAIR, sb);
+        if (launch_pair_kernel(c, a, bx, sb, ewald_recip)) return -1;
+        if (two_streams) {
+            // beside the polarization chain the sum is free on the side stream, and would be 3.5 us of the main one
+            hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(kReduceThreads), 0, sb, c->d_pairpart, ntile * ntile,
+                               kPairChannels, c->d_res + R_RD_PAIR);
+            k.pair_rows_to_sum = 0;
+        } else {
+            k.pair_rows_to_sum = ntile * ntile;  // summed by the publish kernel (same arithmetic, one launch less)
+        }
+    }
+    // ---- disp_expansion: exp repulsion + damped C6 / C8 / C10 over ALL pairs, and its long-range correction
+    if (c->disp_on) {
+        if (launch_disp(c, a, bx, sb)) return -1;
+        k.res_zero_mask |= 1u << R_RDC_SELF;
+    } else if (c->rdc_order) {
+        // ---- rd_crystal: Lennard-Jones over the lattice images, its self part and its long-range correction
+        if (launch_rdc(c, a, bx, sb)) return -1;
+    } else if (c->vdw_on) {
+        // ---- polarvdw: repulsion-only Lennard-Jones, then the coupled-dipole term (it owns R_AT and R_RDC_SELF here)
+        if (launch_vdw(c, a, bx, sb)) return -1;
+    } else if (c->rd_form) {
+        // ---- set_rd_form: the dense sum of the form, and the LJ form's long-range correction
+        if (launch_rdform(c, a, bx, sb)) return -1;
+        k.res_zero_mask |= 1u << R_RDC_SELF;
+    } else {
+        k.res_zero_mask |= (1u << R_DISP) | (1u << R_DISP_LRC) | (1u << R_RDC_SELF);
+    }
+    // ---- axilrod_teller: the triple-dipole sum over ALL triples that are not on one molecule
+    if (c->at_on) {
+        if (launch_at(c, a, bx, sb)) return -1;
+    } else if (!c->vdw_on) {
+        k.res_zero_mask |= 1u << R_AT;
+    }
+    c->lrc_dirty_atoms.clear();  // (every static sum of the call has consumed it)
+
+    // ---- reciprocal + self (absent under Wolf summation, coulombic.c:27-28)
+    if (!P.rd_only && !P.wolf) {
+        ScopedTimer t(c, T_RECIP, sb);
+        if (c->nk > 0) {
+            if (!k.recip_fused && launch_recip_partial(c, a, sb)) return -1;
+            hipLaunchKernelGGL(recip_sum_kernel, dim3((c->nk + 63) / 64), dim3(64 * kRecipGroups), 0, sb, c->d_kvec,
+                               c->nk, ntile, c->d_sfpart, c->d_recipsum);
+            k.recip_chunks = (c->nk + 63) / 64;
+        } else {
+            k.res_zero_mask |= 1u << R_RECIP;
+        }
+        // depends on the charges and alpha only: summed at upload / edit / parameter change, then kept in d_res
+        if (!c->self_valid || c->self_alpha != c->ewald_alpha) {
+            hipLaunchKernelGGL(ewald_self_kernel, dim3(1), dim3(256), 0, sb, a, c->ewald_alpha, c->d_res + R_SELF);
+            c->self_valid = true;
+            c->self_alpha = c->ewald_alpha;
+        }
+    } else {
+        k.res_zero_mask |= (1u << R_RECIP) | (1u << R_SELF);
+        c->self_valid = false;
+    }
+    if (k.split)
+        hipLaunchKernelGGL(publish_side_kernel, dim3(1), dim3(64), 0, sb, c->d_res, c->h_res2_dev, (int)R_COUNT,
+                           (double)c->energy_calls, (const double *)c->d_recipsum, k.recip_chunks, k.res_zero_mask,
+                           kSideSlots);
+    else if (two_streams)
+        hipEventRecord(c->ev_join, sb);
+    return 0;
+}
+
+static void side_stream_once(mpmc_hip_ctx *c) {
+    if (c->call.side_done) return;
+    c->call.side_done = true;
+    c->call.side_rc = enqueue_side_stream(c);
+}
+static void feed_side_stream(mpmc_hip_ctx *c) {
+    if (c->call.side_open) side_stream_once(c);
+}
+static void publish_early(mpmc_hip_ctx *c) {
+    CallState &k = c->call;
+    if (!k.side_open || !k.may_publish_early || k.published || k.build_join_pending) return;
+    k.published = true;
+    k.publish_rc = launch_publish(c);
+}
+
+// One evaluation, launch by launch (also what stream capture records for the step graph): plan, fork, polarization chain
+// with the side stream fed from inside it (or in front of it), join, publish.
+static int enqueue_direct(mpmc_hip_ctx *c) {
+    const mpmc_hip_params &P = c->par;
+    CallState &k = c->call;
+    plan_call(c);
+    const bool do_polar = k.do_polar, two_streams = k.two_streams;
+    // ---- the pending move, unless a later launch of the call carries it
+    if (!k.moves_deferred && !k.moves_in_pair) {
+        if (c->opt.side_moves && !c->main_writes && c->pending.n > 0 && two_streams && k.plain_launches)
+            k.side_apply = c->pending;  // (the side stream applies it too: no fork event, see side_wait_for_moves)
+        if (flush_moves(c)) return -1;
+    } else if (k.moves_deferred && k.gs_mode) {
+        if (c->opt.side_moves && !c->main_writes) k.side_apply = c->pending;  // (else: the fork event behind the coefficient job)
+    }
+    if (is_timed_call(c)) hipEventRecord(c->ev_first, c->stream);
+    // ---- fork
+    if (two_streams && !k.moves_deferred && k.side_apply.n == 0)
+        hipEventRecord(c->ev_fork, c->stream);  // (the side stream's wait is issued when it is fed)
+    if (!k.polar_first) side_stream_once(c);
+    // ---- polarization (main stream); feed_side_stream() and publish_early() act only inside this window
+    int polar_iterations = 0, iter_success = 0;
+    if (do_polar) {
+        k.side_open = k.polar_first;
+        const int rc = run_polarization(c, dev_atoms(c), dev_box(c), &polar_iterations, &iter_success);
+        k.side_open = false;
+        if (rc || k.publish_rc) return -1;
+        if (k.moves_deferred) return fail("MPMC_HIP: internal: a deferred move was not applied");
+    } else {
+        k.res_zero_mask |= (1u << R_UPOL) | (1u << R_RRMS);
+    }
+    // the resident A only tracks moves while it is being maintained
+    if (!do_polar || P.polar_zodid) c->view[0].A_valid = c->view[0].C_valid = false;
+    // ---- the side stream, if the chain did not feed it; join
+    side_stream_once(c);
+    if (k.side_rc) return -1;
     if (c->pending.n > 0 && flush_moves(c)) return -1;  // (a move no launch of this call carried: cannot happen, but cheap)
     k.moves_in_pair = false;
     if (k.build_join_pending) {  // (a builder launch no chain launch of this call waited for)
@@ -3254,16 +3236,9 @@ extern "C" int mpmc_hip_energy(mpmc_hip_ctx *c, mpmc_hip_result *out) {
     return mpmc_hip_energy_end(c, out);
 }
 
-// Enqueue the whole evaluation; nothing waits for the device (except the per-iteration convergence test
-// of polar_precision mode), so the caller can do host work before mpmc_hip_energy_end() collects it.
-extern "C" int mpmc_hip_energy_begin(mpmc_hip_ctx *c) {
-    if (!c) return fail("MPMC_HIP: energy: null argument");
-    if (c->in_flight) return fail("MPMC_HIP: energy_begin: the previous evaluation has not been collected");
-    if (!c->have_atoms) return fail("MPMC_HIP: energy: no configuration uploaded");
-    if (!c->have_box) return fail("MPMC_HIP: energy: no box set");
-    if (c->order_stale && gs_order_mode(c))
-        return fail("MPMC_HIP: energy: Gauss-Seidel after insert_molecule / remove_molecule needs the sweep order of the "
-                    "new configuration (mpmc_hip_set_sweep_order)");
+// The combinations of modes an evaluation refuses, in the order they are checked (tests match on these strings).  Also where
+// polarvdw's e_iso cache goes once the mode is off.
+static int refuse_unsupported(mpmc_hip_ctx *c) {
     if (c->disp_on && c->rdc_order)
         return fail("MPMC_HIP: energy: rd_crystal with disp_expansion is not implemented (the reference's disp_expansion() "
                     "ignores rd_crystal)");
@@ -3315,6 +3290,20 @@ extern "C" int mpmc_hip_energy_begin(mpmc_hip_ctx *c) {
                c->par.polar_max_iter <= 0) {
         return fail("MPMC_HIP: polar_max_iter must be > 0 when polar_precision is 0");  // (accepted by set_params in the exact mode)
     }
+    return 0;
+}
+
+// Enqueue the whole evaluation; nothing waits for the device (except the per-iteration convergence test
+// of polar_precision mode), so the caller can do host work before mpmc_hip_energy_end() collects it.
+extern "C" int mpmc_hip_energy_begin(mpmc_hip_ctx *c) {
+    if (!c) return fail("MPMC_HIP: energy: null argument");
+    if (c->in_flight) return fail("MPMC_HIP: energy_begin: the previous evaluation has not been collected");
+    if (!c->have_atoms) return fail("MPMC_HIP: energy: no configuration uploaded");
+    if (!c->have_box) return fail("MPMC_HIP: energy: no box set");
+    if (c->order_stale && gs_order_mode(c))
+        return fail("MPMC_HIP: energy: Gauss-Seidel after insert_molecule / remove_molecule needs the sweep order of the "
+                    "new configuration (mpmc_hip_set_sweep_order)");
+    if (const int rc = refuse_unsupported(c)) return rc;
     if (!c->exact_polar) c->chol_nv = 0;
     HIPCHK(hipSetDevice(c->device));
     if (c->vdw_on && !c->par.rd_only && vdw_ensure_iso(c)) return -1;
@@ -3417,63 +3406,11 @@ static int repeat_call(mpmc_hip_ctx *c, bool &flag) {
     return rc ? -1 : wait_record(c);
 }
 
-extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
-    if (!c || !out) return fail("MPMC_HIP: energy: null argument");
-    if (!c->in_flight) return fail("MPMC_HIP: energy_end: no evaluation in flight");
-    c->in_flight = false;
-    memset(out, 0, sizeof(*out));
+// The result of the call from the record(s) the publish kernels wrote (energy.c:149-196).
+static void assemble_result(mpmc_hip_ctx *c, int iter_success, mpmc_hip_result *out) {
     const mpmc_hip_params &P = c->par;
-    timespec ts1, ts2;
-    clock_gettime(CLOCK_MONOTONIC, &ts1);
-    if (wait_record(c)) return -1;
-    if (c->call.spec_rank && c->h_res[R_GS_ERR] == 0.0 && c->h_res[R_RANKCHG] != 0.0) {
-        // polar_gs_ranked, speculative call: the ranking metric is not the one the resident ranked view was built
-        // for (molecules came within 1.5 r_min of each other, or moved apart again).  Nothing that call produced is
-        // used; the evaluation is repeated with the host sorting the new metric (which rebuilds the ranked view).
-        // Everything else resident -- pair / field partials, view 0 -- is already up to date and is not redone.
-        ++c->spec_redos;
-        if (repeat_call(c, c->force_host_rank)) return -1;
-    }
-    if (c->call.resident && c->h_res[R_GS_ERR] != 0.0) {
-        // The resident Jacobi launch gave up on a hand-off (its workgroups were not all running at once: the device
-        // is shared with another process, or a test asked for it).  Nothing it produced is used: the evaluation is
-        // repeated on the multi-launch path, which this context then keeps to; the partial-sum slots are refilled
-        // before the resident kernel could ever run again.
-        ++c->resident_fallbacks;
-        c->resident_off = true;
-        // a shared device may be free again later: one more attempt after `backoff` clean calls (a failed attempt costs
-        // the bounded waits, ~0.2 s, so the interval doubles every time it fails)
-        c->resident_backoff = c->resident_backoff ? std::min(2 * c->resident_backoff, 1L << 20) : 4096;
-        c->resident_retry_at = (long)c->energy_calls + c->resident_backoff;
-        c->view[0].resP_armed = false;
-        if (repeat_call(c, c->force_multi_launch)) return -1;
-    }
-    clock_gettime(CLOCK_MONOTONIC, &ts2);
-    c->host_wait_s += (ts2.tv_sec - ts1.tv_sec) + 1e-9 * (ts2.tv_nsec - ts1.tv_nsec);
-    const bool do_polar = c->call.do_polar, timed_call = c->call.timed;
+    const bool do_polar = c->call.do_polar;
     const int polar_iterations = c->call.iterations;
-    // (exact dipoles: the factorization's flag word came with the record, in the slot the iterative paths keep <rrms> in)
-    const int iter_success = c->call.exact ? (c->h_res[R_RRMS] != 0.0 ? 1 : 0) : c->call.iter_success;
-    if (c->call.exact) {
-        c->chol_done = true;
-        c->chol_failed = iter_success != 0;
-    }
-    const int gs_err = (int)c->h_res[R_GS_ERR];
-    c->h_gserr[0] = gs_err & 1;
-    c->h_gserr[1] = (gs_err >> 1) & 1;
-    const bool gs_timeout = gs_err != 0;
-    if (gs_timeout) {
-        unsigned dbg[8] = {0};
-        const SweepView &gv = c->view[c->h_gserr[1] ? 1 : 0];
-        hipMemcpy(dbg, gv.gsflags, sizeof(dbg), hipMemcpyDeviceToHost);  // (the allocation is exactly 8 words)
-        return fail("MPMC_HIP: persistent Gauss-Seidel kernel gave up waiting on a hand-off (spin limit) in view %d: "
-                    "workgroup %u thread %u addr-lo 0x%x; mu_new-lo 0x%x",
-                    c->h_gserr[1] ? 1 : 0, dbg[2], dbg[3], dbg[4], (unsigned)((unsigned long long)gv.mupub.get() & 0xffffffffu));
-    }
-    HIPCHK(hipGetLastError());
-    c->timed = timed_call;
-    c->stage_used = 0;
-
     double r[R_COUNT];
     for (int k = 0; k < R_COUNT; ++k) r[k] = (c->call.split && ((kSideSlots >> k) & 1u)) ? c->h_res2[k] : c->h_res[k];
     // (disp_expansion: the LJ kernels ran on zero parameters, both of their slots are exactly 0)
@@ -3516,6 +3453,63 @@ extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
     out->iter_success = iter_success;
     out->n_atoms = c->n_valid;
     out->status = std::isfinite(out->energy) ? 0 : 1;
+}
+
+extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
+    if (!c || !out) return fail("MPMC_HIP: energy: null argument");
+    if (!c->in_flight) return fail("MPMC_HIP: energy_end: no evaluation in flight");
+    c->in_flight = false;
+    memset(out, 0, sizeof(*out));
+    timespec ts1, ts2;
+    clock_gettime(CLOCK_MONOTONIC, &ts1);
+    if (wait_record(c)) return -1;
+    if (c->call.spec_rank && c->h_res[R_GS_ERR] == 0.0 && c->h_res[R_RANKCHG] != 0.0) {
+        // polar_gs_ranked, speculative call: the ranking metric is not the one the resident ranked view was built
+        // for (molecules came within 1.5 r_min of each other, or moved apart again).  Nothing that call produced is
+        // used; the evaluation is repeated with the host sorting the new metric (which rebuilds the ranked view).
+        // Everything else resident -- pair / field partials, view 0 -- is already up to date and is not redone.
+        ++c->spec_redos;
+        if (repeat_call(c, c->force_host_rank)) return -1;
+    }
+    if (c->call.resident && c->h_res[R_GS_ERR] != 0.0) {
+        // The resident Jacobi launch gave up on a hand-off (its workgroups were not all running at once: the device
+        // is shared with another process, or a test asked for it).  Nothing it produced is used: the evaluation is
+        // repeated on the multi-launch path, which this context then keeps to; the partial-sum slots are refilled
+        // before the resident kernel could ever run again.
+        ++c->resident_fallbacks;
+        c->resident_off = true;
+        // a shared device may be free again later: one more attempt after `backoff` clean calls (a failed attempt costs
+        // the bounded waits, ~0.2 s, so the interval doubles every time it fails)
+        c->resident_backoff = c->resident_backoff ? std::min(2 * c->resident_backoff, 1L << 20) : 4096;
+        c->resident_retry_at = (long)c->energy_calls + c->resident_backoff;
+        c->view[0].resP_armed = false;
+        if (repeat_call(c, c->force_multi_launch)) return -1;
+    }
+    clock_gettime(CLOCK_MONOTONIC, &ts2);
+    c->host_wait_s += (ts2.tv_sec - ts1.tv_sec) + 1e-9 * (ts2.tv_nsec - ts1.tv_nsec);
+    const bool timed_call = c->call.timed;
+    // (exact dipoles: the factorization's flag word came with the record, in the slot the iterative paths keep <rrms> in)
+    const int iter_success = c->call.exact ? (c->h_res[R_RRMS] != 0.0 ? 1 : 0) : c->call.iter_success;
+    if (c->call.exact) {
+        c->chol_done = true;
+        c->chol_failed = iter_success != 0;
+    }
+    const int gs_err = (int)c->h_res[R_GS_ERR];
+    c->h_gserr[0] = gs_err & 1;
+    c->h_gserr[1] = (gs_err >> 1) & 1;
+    const bool gs_timeout = gs_err != 0;
+    if (gs_timeout) {
+        unsigned dbg[8] = {0};
+        const SweepView &gv = c->view[c->h_gserr[1] ? 1 : 0];
+        hipMemcpy(dbg, gv.gsflags, sizeof(dbg), hipMemcpyDeviceToHost);  // (the allocation is exactly 8 words)
+        return fail("MPMC_HIP: persistent Gauss-Seidel kernel gave up waiting on a hand-off (spin limit) in view %d: "
+                    "workgroup %u thread %u addr-lo 0x%x; mu_new-lo 0x%x",
+                    c->h_gserr[1] ? 1 : 0, dbg[2], dbg[3], dbg[4], (unsigned)((unsigned long long)gv.mupub.get() & 0xffffffffu));
+    }
+    HIPCHK(hipGetLastError());
+    c->timed = timed_call;
+    c->stage_used = 0;
+    assemble_result(c, iter_success, out);
     return 0;
 }
 

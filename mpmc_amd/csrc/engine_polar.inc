@@ -28,9 +28,8 @@ static int launch_field(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx) {
     fp.cutoffterm = 0.0;
     // enough j-chunks to fill the chip: ~2048 waves in flight
     const int ntile = c->npad / 64;
-    int nchunk = std::max(1, std::min(ntile, 4096 / ntile));
-    int chunk = round_up((c->npad + nchunk - 1) / nchunk, 64);
-    nchunk = (c->npad + chunk - 1) / chunk;
+    const ChunkPlan cp = chunk_plan(c->npad, 4096);
+    const int nchunk = cp.nchunk, chunk = cp.chunk;
     fp.chunk = chunk;
     // The real-space partials persist between calls: with nothing moved since the last call the kernel is
     // skipped, after a single-molecule move only the tiles of the moved atoms' blocks are recomputed.
@@ -71,34 +70,29 @@ static int launch_field(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx) {
         c->es_stale = true;
         return 0;
     }
+    if (mode == kFieldWolfA) {
+        const double al = P.polar_wolf_alpha, R = c->cutoff, rR = 1.0 / R;
+        fp.cutoffterm = std::erfc(al * R) * rR * rR + 2.0 * al * kOneOverSqrtPi * std::exp(-al * al * R * R) * rR;
+    }
+    // KERNEL<kF> for the call's field mode (the Ewald form has returned above)
+#define MPMC_FIELD_DISPATCH(...)                                                       \
+    do switch (mode) {                                                                 \
+        case kFieldBare: { constexpr int kF = kFieldBare; __VA_ARGS__; break; }        \
+        case kFieldWolf0: { constexpr int kF = kFieldWolf0; __VA_ARGS__; break; }      \
+        default: { constexpr int kF = kFieldWolfA; __VA_ARGS__; break; }               \
+    } while (0)
     if (fused) {
         const CoefJob &cj = c->call.coef_job;
         c->call.coef_job_valid = false;
-        if (!wolf) {
-            MPMC_THOLE_DISPATCH(c, hipLaunchKernelGGL((field_coef_kernel<kFieldBare, kM>), grid, block, 0, c->stream, a, bx, fp, sel,
-                                                      c->d_fieldpart, cj));
-        } else if (P.polar_wolf_alpha == 0.0) {
-            MPMC_THOLE_DISPATCH(c, hipLaunchKernelGGL((field_coef_kernel<kFieldWolf0, kM>), grid, block, 0, c->stream, a, bx, fp, sel,
-                                                      c->d_fieldpart, cj));
-        } else {
-            const double al = P.polar_wolf_alpha, R = c->cutoff, rR = 1.0 / R;
-            fp.cutoffterm = std::erfc(al * R) * rR * rR + 2.0 * al * kOneOverSqrtPi * std::exp(-al * al * R * R) * rR;
-            MPMC_THOLE_DISPATCH(c, hipLaunchKernelGGL((field_coef_kernel<kFieldWolfA, kM>), grid, block, 0, c->stream, a, bx, fp, sel,
-                                                      c->d_fieldpart, cj));
-        }
+        MPMC_FIELD_DISPATCH(MPMC_THOLE_DISPATCH(c, hipLaunchKernelGGL((field_coef_kernel<kF, kM>), grid, block, 0, c->stream, a, bx,
+                                                                      fp, sel, c->d_fieldpart, cj)));
         HIPCHK(hipGetLastError());
         if (c->call.coef_job_fork) hipEventRecord(c->ev_fork, c->stream);
     } else if (!skip) {
-        if (!wolf) {
-            HIPCHK(launch_slot(c, GS_FIELD, static_field_kernel<kFieldBare>, grid, block, c->stream, a, bx, fp, sel, c->d_fieldpart));
-        } else if (P.polar_wolf_alpha == 0.0) {
-            HIPCHK(launch_slot(c, GS_FIELD, static_field_kernel<kFieldWolf0>, grid, block, c->stream, a, bx, fp, sel, c->d_fieldpart));
-        } else {
-            const double al = P.polar_wolf_alpha, R = c->cutoff, rR = 1.0 / R;
-            fp.cutoffterm = std::erfc(al * R) * rR * rR + 2.0 * al * kOneOverSqrtPi * std::exp(-al * al * R * R) * rR;
-            HIPCHK(launch_slot(c, GS_FIELD, static_field_kernel<kFieldWolfA>, grid, block, c->stream, a, bx, fp, sel, c->d_fieldpart));
-        }
+        MPMC_FIELD_DISPATCH(HIPCHK(launch_slot(c, GS_FIELD, static_field_kernel<kF>, grid, block, c->stream, a, bx, fp, sel,
+                                               c->d_fieldpart)));
     }
+#undef MPMC_FIELD_DISPATCH
     c->es_slots = nchunk;
     c->es_stale = true;
     return 0;
@@ -128,6 +122,151 @@ static bool collect_dirty_slots(mpmc_hip_ctx *c, const SweepView &v, DirtyList &
     }
     for (int k = 0; k < kMaxDirty; ++k) dl.slot[k] = (k < nd) ? c->h_dirty[k] : 0;
     return true;
+}
+
+// diagnostic only (option "inv_stamps"): block, then print where a gs_block_inverse_kernel launch's time went
+static int print_inv_stamps(hipStream_t st, const unsigned long long *istamps, size_t nwg, int waves, const GsBuild &gb,
+                            int nsingle, bool full) {
+    std::vector<unsigned long long> h(nwg * 4);
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(h.data(), istamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    unsigned long long t0 = ~0ull, t3 = 0;
+    double ph[3] = {0, 0, 0}, phmax[3] = {0, 0, 0}, start_max = 0;
+    int live = 0;
+    for (size_t g = 0; g < nwg; ++g) {
+        if (!h[4 * g + 3]) continue;
+        t0 = std::min(t0, h[4 * g]);
+    }
+    for (size_t g = 0; g < nwg; ++g) {
+        if (!h[4 * g + 3]) continue;
+        ++live;
+        t3 = std::max(t3, h[4 * g + 3]);
+        start_max = std::max(start_max, (double)(h[4 * g] - t0) * 0.01);
+        for (int k = 0; k < 3; ++k) {
+            const double d = (double)(h[4 * g + k + 1] - h[4 * g + k]) * 0.01;
+            ph[k] += d;
+            phmax[k] = std::max(phmax[k], d);
+        }
+    }
+    fprintf(stderr, "INV_STAMPS waves %d, %d live workgroups of %zu (lists %d %d %d, full %d): span %.2f us, last start +%.2f us; "
+                    "mean (max) us: loads %.2f (%.2f), expansion %.2f (%.2f), substitution %.2f (%.2f)\n",
+            waves, live, nwg, gb.inv.n, gb.own.n, nsingle, full ? 1 : 0, (double)(t3 - t0) * 0.01, start_max, ph[0] / std::max(live, 1),
+            phmax[0], ph[1] / std::max(live, 1), phmax[1], ph[2] / std::max(live, 1), phmax[2]);
+    return 0;
+}
+
+// Gauss-Seidel chain data (kernels_gs_chain.h) of a view of nt blocks whose coefficients setup_view() has just brought up
+// to date on stream `st`: the inverse of a diagonal block is a function of that block's atoms, the expanded tile (t, t-k) of
+// blocks t and t-k: after a move only those of the moved atoms' blocks (the view slots `dl`) and of a re-ordered tail are
+// redone.  Maintained only while every call keeps them up to date (M_call), else rebuilt.  coef_updated: the coefficients
+// were updated in place, not rebuilt.
+static int maintain_chain_data(mpmc_hip_ctx *c, SweepView &v, const DevBox &bx, hipStream_t st, int nt, bool coef_updated,
+                               int tail, const DirtyList &dl, int nd) {
+    if (ensure_view_chain(c, v, st)) return -1;
+    const bool fresh = coef_updated && v.M_epoch == v.C_epoch && v.M_call + 1 == c->energy_calls;
+    // How many lags a view caches is decided when it is rebuilt as a whole: the option's value -- unless the view was rebuilt
+    // as a whole in the previous call too (a grand-canonical chain rebuilds its ranked view every step: the rebuild, not
+    // the sweeps, bounds such a step, and a third lag costs it more than the shorter sweeps return: 1 380 vs 1 425 steps/s).
+    if (!fresh || v.nlag < 2 || v.nlag > c->opt.gs_lags) {
+        // (three calls in a row: a ranked walk that changes and changes back in consecutive NVT steps keeps the full count)
+        const bool again = v.last_full_call >= 0 && (unsigned long long)v.last_full_call + 1 >= c->energy_calls;
+        v.full_streak = again ? v.full_streak + 1 : 0;
+        v.nlag = (v.full_streak >= 2) ? std::min(2, c->opt.gs_lags) : c->opt.gs_lags;
+    }
+    const int nlag = v.nlag;
+    GsBuild gb;
+    const bool full = plan_chain_build(fresh && v.nlag_built == v.nlag, tail, nt, nlag, dl.slot, nd, gb);
+    if (full) v.last_full_call = (long long)c->energy_calls;
+    v.nlag_built = nlag;
+    gb.Minv = v.Minv;
+    for (int k = 0; k < kGsMaxLag; ++k) gb.Lnb[k] = v.Lnb[k];
+    gb.nlag = nlag;
+    int nsingle = 0, nsingle_max = 0;
+    for (int k = 0; k < nlag; ++k) {
+        nsingle += gb.nb[k].n;
+        nsingle_max = std::max(nsingle_max, gb.nb[k].n);
+    }
+    // One launch: z-slice 0 the block inverses M_t (list `inv`), z-slice 1 all neighbour matrices L(k)_t = M_t D T(t,t-k)
+    // of the blocks that changed themselves (list `own`, one pass for the nlag right-hand sides), z-slice 1 + k the one
+    // matrix L(k)_t of the block k places behind a changed one -- the same forward substitution with other right-hand sides.
+    if (full || gb.inv.n > 0 || gb.own.n > 0 || nsingle > 0) {
+        const int nblk = full ? nt : std::max(std::max(gb.inv.n, gb.own.n), nsingle_max);
+        const int nsolve = full ? 2 * nt : gb.inv.n + gb.own.n + nsingle;
+        const int waves = inverse_waves(nsolve, st == c->stream, c->opt.gs_side_waves, gs_chain_ticket_base(nt, nlag));
+        // The main stream's builder is forked to a stream of its own: nothing but the chain kernel reads its output, and the
+        // launches between here and the chain (static field, view set-up, upper-triangle sums: ~28 us) do not depend on it.
+        hipStream_t bst = st;
+        // (Only for views of 24 blocks or more: below that the launches in between are short, the front of the step is bound
+        //  by the host's launch rate, and the four event calls of the fork cost more than it hides -- 4 400 vs 4 650 steps/s
+        //  at 1 024 atoms, +3 % at 4 096; option gs_build_fork = 2 forces it.)
+        if (st == c->stream && c->opt.inv_stamps <= 0 && (c->opt.gs_build_fork == 2 || (c->opt.gs_build_fork == 1 && nt >= 24))) {
+            HIPCHK(hipEventRecord(c->ev_bfork, c->stream));
+            HIPCHK(hipStreamWaitEvent(c->stream3, c->ev_bfork, 0));
+            bst = c->stream3;
+        }
+        const dim3 gi(192 / waves, nblk, full ? 2 : 2 + nlag), bi(64 * waves);
+        unsigned long long *istamps = nullptr;
+        const size_t nwg = (size_t)gi.x * gi.y * gi.z;
+        if (c->opt.inv_stamps > 0 && st == c->stream) {
+            if (!c->d_istamps) HIPCHK(c->d_istamps.alloc((size_t)16 * 256 * 3 * 4));
+            if (nwg <= (size_t)16 * 256 * 3) {
+                HIPCHK(hipMemsetAsync(c->d_istamps, 0, nwg * 4 * sizeof(unsigned long long), st));
+                istamps = c->d_istamps;
+            }
+        }
+#define MPMC_LAUNCH_INVERSE(O, W)                                                                                          \
+    hipLaunchKernelGGL((gs_block_inverse_kernel<O, W>), gi, bi, kInverseLds, bst, v.C, v.ntld, v.px, v.py, v.pz, v.palpha, bx, \
+                       gb, istamps)
+        if (c->box_ortho) {
+            if (waves == 4) MPMC_LAUNCH_INVERSE(1, 4);
+            else if (waves == 8) MPMC_LAUNCH_INVERSE(1, 8);
+            else MPMC_LAUNCH_INVERSE(1, 16);
+        } else {
+            if (waves == 4) MPMC_LAUNCH_INVERSE(0, 4);
+            else if (waves == 8) MPMC_LAUNCH_INVERSE(0, 8);
+            else MPMC_LAUNCH_INVERSE(0, 16);
+        }
+#undef MPMC_LAUNCH_INVERSE
+        if (bst != st) {
+            HIPCHK(hipEventRecord(c->ev_bjoin, bst));
+            c->call.build_join_pending = true;
+        }
+        if (istamps) {
+            --c->opt.inv_stamps;
+            if (print_inv_stamps(st, istamps, nwg, waves, gb, nsingle, full)) return -1;
+        }
+    }
+    v.M_epoch = v.C_epoch;
+    v.M_call = c->energy_calls;
+    return 0;
+}
+
+// setup_view(): view 0's coefficient update that also applies the pending move becomes the call's CoefJob, and the move
+// is no longer pending on the main stream.
+static void hand_over_coef_job(mpmc_hip_ctx *c, const SweepView &v, const DevAtoms &pa, const TholeParams &tp,
+                               const DirtyMoves &dm, int nt) {
+    CoefJob &cj = c->call.coef_job;
+    cj.pa = pa;
+    cj.tp = tp;
+    cj.dm = dm;
+    cj.nt = nt;
+    cj.ntld = v.ntld;
+    cj.C = v.C;
+    cj.m = c->pending;
+    cj.gx = c->d_x;
+    cj.gy = c->d_y;
+    cj.gz = c->d_z;
+    cj.slot_of_atom = (const int *)v.d_slot;
+    cj.px = v.px;
+    cj.py = v.py;
+    cj.pz = v.pz;
+    c->call.coef_job_valid = true;
+    if (c->call.side_carry) c->call.side_moves = c->pending;  // the side stream's pair kernel applies it too
+    c->pending.n = 0;
+    c->call.moves_deferred = false;
+    // the new coordinates are in place (no event when the side stream does not wait for them: it carries the
+    // move in its pair kernel, or -- Gauss-Seidel modes -- applies it for itself first)
+    c->call.coef_job_fork = c->opt.overlap && !c->call.side_carry && c->call.side_apply.n == 0;
 }
 
 // gather the view's per-atom data from the current configuration and build its A block -- as pair
@@ -214,28 +353,7 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
                 if (all_found) {
                     // handed to launch_field(), the next launch of the chain, which lets it ride in the field kernel's
                     // grid (field_coef_kernel) or, when it cannot, launches update_coef_moves_kernel in front of it
-                    CoefJob &cj = c->call.coef_job;
-                    cj.pa = pa;
-                    cj.tp = tp;
-                    cj.dm = dm;
-                    cj.nt = nt;
-                    cj.ntld = v.ntld;
-                    cj.C = v.C;
-                    cj.m = c->pending;
-                    cj.gx = c->d_x;
-                    cj.gy = c->d_y;
-                    cj.gz = c->d_z;
-                    cj.slot_of_atom = (const int *)v.d_slot;
-                    cj.px = v.px;
-                    cj.py = v.py;
-                    cj.pz = v.pz;
-                    c->call.coef_job_valid = true;
-                    if (c->call.side_carry) c->call.side_moves = c->pending;  // the side stream's pair kernel applies it too
-                    c->pending.n = 0;
-                    c->call.moves_deferred = false;
-                    // the new coordinates are in place (no event when the side stream does not wait for them: it carries the
-                    // move in its pair kernel, or -- Gauss-Seidel modes -- applies it for itself first)
-                    c->call.coef_job_fork = c->opt.overlap && !c->call.side_carry && c->call.side_apply.n == 0;
+                    hand_over_coef_job(c, v, pa, tp, dm, nt);
                     // with chain data to maintain, the job cannot wait for launch_field(): the block matrices below are
                     // functions of the updated coefficients
                     if (want_chain && launch_coef_job(c, bx)) return -1;
@@ -261,169 +379,7 @@ static int setup_view(mpmc_hip_ctx *c, SweepView &v, const DevAtoms &a, const De
     } else {
         v.C_valid = false;
     }
-    if (want_chain && want_coef) {
-        // Gauss-Seidel chain data (kernels_gs_chain.h): the inverse of a diagonal block is a function of that block's
-        // atoms, the expanded tile (t, t-1) of blocks t and t-1: after a move only those of the moved atoms' blocks
-        // are redone.  Maintained only while every call keeps them up to date (M_call), else rebuilt.
-        if (ensure_view_chain(c, v, st)) return -1;
-        const bool fresh = coef_updated && v.M_epoch == v.C_epoch && v.M_call + 1 == c->energy_calls;
-        // How many lags a view caches is decided when it is rebuilt as a whole: the option's value -- unless the view was rebuilt
-        // as a whole in the previous call too (a grand-canonical chain rebuilds its ranked view every step: the rebuild, not
-        // the sweeps, bounds such a step, and a third lag costs it more than the shorter sweeps return: 1 380 vs 1 425 steps/s).
-        if (!fresh || v.nlag < 2 || v.nlag > c->opt.gs_lags) {
-            // (three calls in a row: a ranked walk that changes and changes back in consecutive NVT steps keeps the full count)
-            const bool again = v.last_full_call >= 0 && (unsigned long long)v.last_full_call + 1 >= c->energy_calls;
-            v.full_streak = again ? v.full_streak + 1 : 0;
-            v.nlag = (v.full_streak >= 2) ? std::min(2, c->opt.gs_lags) : c->opt.gs_lags;
-        }
-        const int nlag = v.nlag;
-        GsBuild gb;
-        memset(&gb, 0, sizeof(gb));
-        auto listed = [](const BlockList &l, int b) {
-            for (int q = 0; q < l.n; ++q)
-                if (l.blk[q] == b) return true;
-            return false;
-        };
-        bool full = !fresh || v.nlag_built != v.nlag;
-        // a block whose own atoms changed: M_b and every L(k)_b (z-slice 1, one pass); the blocks k places behind it: L(k)_{b+k}
-        auto add_block = [&](int b) {
-            if (listed(gb.inv, b)) return;
-            if (gb.inv.n == kMaxBlockList) {
-                full = true;
-                return;
-            }
-            gb.inv.blk[gb.inv.n++] = b;
-            if (b >= 1) gb.own.blk[gb.own.n++] = b;
-            for (int k = 1; k <= nlag; ++k) {
-                const int tt = b + k;
-                if (tt >= nt || listed(gb.nb[k - 1], tt)) continue;
-                if (gb.nb[k - 1].n == kMaxBlockList) {
-                    full = true;
-                    return;
-                }
-                gb.nb[k - 1].blk[gb.nb[k - 1].n++] = tt;
-            }
-        };
-        if (fresh && tail >= 0)  // every block of the re-ordered tail (the tiles that join it to the prefix are theirs)
-            for (int b = tail; b < nt && !full; ++b) add_block(b);
-        if (fresh)
-            for (int k = 0; k < nd && !full; ++k) add_block(dl.slot[k] / 64);
-        // (a block listed in `own` has all its lags rebuilt there: drop it from the single-lag lists)
-        for (int k = 0; k < nlag && !full; ++k) {
-            BlockList &l = gb.nb[k];
-            int m = 0;
-            for (int q = 0; q < l.n; ++q)
-                if (!listed(gb.own, l.blk[q])) l.blk[m++] = l.blk[q];
-            l.n = m;
-        }
-        if (full) {
-            memset(&gb, 0, sizeof(gb));
-            gb.nb_all = nt;
-            v.last_full_call = (long long)c->energy_calls;
-        }
-        v.nlag_built = nlag;
-        gb.Minv = v.Minv;
-        for (int k = 0; k < kGsMaxLag; ++k) gb.Lnb[k] = v.Lnb[k];
-        gb.nlag = nlag;
-        int nsingle = 0, nsingle_max = 0;
-        for (int k = 0; k < nlag; ++k) {
-            nsingle += gb.nb[k].n;
-            nsingle_max = std::max(nsingle_max, gb.nb[k].n);
-        }
-        // One launch: z-slice 0 the block inverses M_t (list `inv`), z-slice 1 all neighbour matrices L(k)_t = M_t D T(t,t-k)
-        // of the blocks that changed themselves (list `own`, one pass for the nlag right-hand sides), z-slice 1 + k the one
-        // matrix L(k)_t of the block k places behind a changed one -- the same forward substitution with other right-hand sides.
-        if (full || gb.inv.n > 0 || gb.own.n > 0 || nsingle > 0) {
-            const int nblk = full ? nt : std::max(std::max(gb.inv.n, gb.own.n), nsingle_max);
-            // Geometry: 192 / WAVES workgroups of WAVES waves per pass (each holds ~97 KB of LDS: one per CU).  4 waves x 48
-            // workgroups finish a pass soonest (the moved atoms' blocks of view 0 are on the step's critical path), but only
-            // while all of them find a CU at once: a move rebuilds M_b, {L(k)_b}, L(1)_b+1 .. L(nlag)_b+nlag = 2 + nlag passes; when
-            // two blocks moved (or the view's tail is re-ordered) 8 waves x 24 keep the launch to one dispatch round, and a
-            // rebuild of many blocks is a matter of throughput: 16 waves x 12 repeat the tile expansion least often.
-            const int nsolve = full ? 2 * nt : gb.inv.n + gb.own.n + nsingle;
-            // The other view's rebuild, in the side stream, runs BESIDE the main stream's chain kernel, whose workgroups need a CU
-            // each as well (both kinds own a CU's LDS): it takes the fastest geometry that leaves the chain its CUs -- with 8 x 24
-            // and round 2's seven passes the two launches together oversubscribed the 256 CUs and the chain took 85 us instead
-            // of 73; always 16 x 12 (a few dozen CUs, but 48 us per launch) left the main stream of a 1 024-atom step, whose
-            // sweeps are 23 us long, waiting 60 us for the ranked view at its view switch.  (gs_side_waves = 16: always 16.)
-            const int chain_wgs = gs_chain_ticket_base(nt, nlag);
-            int waves;
-            if (st == c->stream)
-                waves = (48 * nsolve <= 256) ? 4 : ((24 * nsolve <= 256) ? 8 : 16);
-            else if (c->opt.gs_side_waves == 16)
-                waves = 16;
-            else
-                waves = (48 * nsolve + chain_wgs <= 256) ? 4 : ((24 * nsolve + chain_wgs <= 256) ? 8 : 16);
-            // The main stream's builder is forked to a stream of its own: nothing but the chain kernel reads its output, and the
-            // launches between here and the chain (static field, view set-up, upper-triangle sums: ~28 us) do not depend on it.
-            hipStream_t bst = st;
-            // (Only for views of 24 blocks or more: below that the launches in between are short, the front of the step is bound
-            //  by the host's launch rate, and the four event calls of the fork cost more than it hides -- 4 400 vs 4 650 steps/s
-            //  at 1 024 atoms, +3 % at 4 096; option gs_build_fork = 2 forces it.)
-            if (st == c->stream && c->opt.inv_stamps <= 0 && (c->opt.gs_build_fork == 2 || (c->opt.gs_build_fork == 1 && nt >= 24))) {
-                HIPCHK(hipEventRecord(c->ev_bfork, c->stream));
-                HIPCHK(hipStreamWaitEvent(c->stream3, c->ev_bfork, 0));
-                bst = c->stream3;
-            }
-            const dim3 gi(192 / waves, nblk, full ? 2 : 2 + nlag), bi(64 * waves);
-            unsigned long long *istamps = nullptr;
-            const size_t nwg = (size_t)gi.x * gi.y * gi.z;
-            if (c->opt.inv_stamps > 0 && st == c->stream) {
-                if (!c->d_istamps) HIPCHK(c->d_istamps.alloc((size_t)16 * 256 * 3 * 4));
-                if (nwg <= (size_t)16 * 256 * 3) {
-                    HIPCHK(hipMemsetAsync(c->d_istamps, 0, nwg * 4 * sizeof(unsigned long long), st));
-                    istamps = c->d_istamps;
-                }
-            }
-#define MPMC_LAUNCH_INVERSE(O, W)                                                                                          \
-    hipLaunchKernelGGL((gs_block_inverse_kernel<O, W>), gi, bi, kInverseLds, bst, v.C, v.ntld, v.px, v.py, v.pz, v.palpha, bx, \
-                       gb, istamps)
-            if (c->box_ortho) {
-                if (waves == 4) MPMC_LAUNCH_INVERSE(1, 4);
-                else if (waves == 8) MPMC_LAUNCH_INVERSE(1, 8);
-                else MPMC_LAUNCH_INVERSE(1, 16);
-            } else {
-                if (waves == 4) MPMC_LAUNCH_INVERSE(0, 4);
-                else if (waves == 8) MPMC_LAUNCH_INVERSE(0, 8);
-                else MPMC_LAUNCH_INVERSE(0, 16);
-            }
-#undef MPMC_LAUNCH_INVERSE
-            if (bst != st) {
-                HIPCHK(hipEventRecord(c->ev_bjoin, bst));
-                c->call.build_join_pending = true;
-            }
-            if (istamps) {  // diagnostic only: block, then print where the launch's time went
-                --c->opt.inv_stamps;
-                std::vector<unsigned long long> h(nwg * 4);
-                HIPCHK(hipStreamSynchronize(st));
-                HIPCHK(hipMemcpy(h.data(), istamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-                unsigned long long t0 = ~0ull, t3 = 0;
-                double ph[3] = {0, 0, 0}, phmax[3] = {0, 0, 0}, start_max = 0;
-                int live = 0;
-                for (size_t g = 0; g < nwg; ++g) {
-                    if (!h[4 * g + 3]) continue;
-                    t0 = std::min(t0, h[4 * g]);
-                }
-                for (size_t g = 0; g < nwg; ++g) {
-                    if (!h[4 * g + 3]) continue;
-                    ++live;
-                    t3 = std::max(t3, h[4 * g + 3]);
-                    start_max = std::max(start_max, (double)(h[4 * g] - t0) * 0.01);
-                    for (int k = 0; k < 3; ++k) {
-                        const double d = (double)(h[4 * g + k + 1] - h[4 * g + k]) * 0.01;
-                        ph[k] += d;
-                        phmax[k] = std::max(phmax[k], d);
-                    }
-                }
-                fprintf(stderr, "INV_STAMPS waves %d, %d live workgroups of %zu (lists %d %d %d, full %d): span %.2f us, last start +%.2f us; "
-                                "mean (max) us: loads %.2f (%.2f), expansion %.2f (%.2f), substitution %.2f (%.2f)\n",
-                        waves, live, nwg, gb.inv.n, gb.own.n, nsingle, full ? 1 : 0, (double)(t3 - t0) * 0.01, start_max, ph[0] / std::max(live, 1),
-                        phmax[0], ph[1] / std::max(live, 1), phmax[1], ph[2] / std::max(live, 1), phmax[2]);
-            }
-        }
-        v.M_epoch = v.C_epoch;
-        v.M_call = c->energy_calls;
-    }
+    if (want_chain && want_coef && maintain_chain_data(c, v, bx, st, nt, coef_updated, tail, dl, nd)) return -1;
     if (want_matrix) {
         if (ensure_view_matrix(v)) return -1;
         if (can_update && v.A_valid) {
@@ -724,18 +680,8 @@ static int launch_resident(mpmc_hip_ctx *c, SweepView &v, const DevBox &bx, cons
     rs.niter = P.polar_max_iter;
     rs.palmo = P.polar_palmo ? 1 : 0;
     rs.want_rrms = want_rrms ? 1 : 0;
-    for (int k = 1; k <= kResMaxSweeps; ++k) {  // the mixing weights of iteration k (thole_iterative.c:238-252)
-        double w_new = 1.0, w_old = 0.0;
-        if (P.polar_sor) {
-            w_new = P.polar_gamma;
-            w_old = 1.0 - P.polar_gamma;
-        } else if (P.polar_esor) {
-            w_old = std::exp(-P.polar_gamma * k);
-            w_new = 1.0 - w_old;
-        }
-        rs.w_new[k - 1] = w_new;
-        rs.w_old[k - 1] = w_old;
-    }
+    for (int k = 1; k <= kResMaxSweeps; ++k)
+        mixing_weights(P.polar_sor, P.polar_esor, P.polar_gamma, k, rs.w_new[k - 1], rs.w_old[k - 1]);
     rs.bx = bx;
     rs.fault = c->opt.res_fault;
     c->opt.res_fault = 0;
@@ -748,7 +694,7 @@ static int launch_resident(mpmc_hip_ctx *c, SweepView &v, const DevBox &bx, cons
         HIPCHK(hipMemsetAsync(c->d_stamps, 0, nstamp * sizeof(unsigned long long), c->stream));
         rs.stamps = c->d_stamps;
     }
-    if (c->opt.res_side && c->call.enqueue_side) c->call.enqueue_side();
+    if (c->opt.res_side) feed_side_stream(c);
     ResidentKernel kern = resident_kernel_of(c->box_ortho ? 1 : 0, rp.K, rp.fold);
     HIPCHK(launch_timed(c, T_SWEEP, kern, dim3(nrole), dim3(kResThreads), (size_t)rp.lds, c->stream, rs));
     if (rs.stamps) {
@@ -799,7 +745,7 @@ static int launch_resident(mpmc_hip_ctx *c, SweepView &v, const DevBox &bx, cons
                     mean[4], mx[4]);
         }
     }
-    if (c->call.enqueue_side) c->call.enqueue_side();
+    feed_side_stream(c);
     ++c->resident_calls;
     c->call.gs_used[0] = true;  // the sticky error word travels with the result record (publish_result_kernel)
     c->energy_part = v.energy_part;
@@ -882,7 +828,7 @@ static int run_exact_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevB
         ScopedTimer t(c, T_PALMO);  // (the whole solve; the trailing updates alone are the call's T_SWEEP records)
         if (exact_factor(c, *V)) return -1;
         // the device is busy now: feed the LJ / Ewald stream
-        if (c->call.enqueue_side) c->call.enqueue_side();
+        feed_side_stream(c);
         if (exact_substitute<1>(c, V->nv, V->nvpad, V->es)) return -1;
         hipLaunchKernelGGL(chol_energy_kernel, dim3(1), dim3(256), 0, c->stream, V->nv, V->nvpad,
                            (const double *)(c->d_chol_vec + 6 * (size_t)(3 * V->nvpad)), (const double *)V->palpha,
@@ -901,9 +847,159 @@ static int run_exact_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevB
     return 0;
 }
 
+// polar_gs_ranked: the ranking work of one call (a local of run_polarization()).  Two parts: (A) the metric's four kernels,
+// (B) the ranked view's maintenance (speculative form) or the copy for the host's sort, and the event the main stream waits
+// for at the view switch.
+struct RankJob {
+    bool ranked = false;     // the call ranks at all
+    bool spec_rank = false;  // speculative form: the previous call's walk is assumed, the device checks it
+    bool rank_side = false;  // the work runs on the side stream
+    hipStream_t rs = nullptr;
+    bool enqueued = false, metric_enqueued = false;  // part B (which includes A) / part A went out
+};
+
+// (A) the ranking metric (pairs.c:337-360), once per call
+static void enqueue_rank_metric(mpmc_hip_ctx *c, RankJob &rj, const DevAtoms &a, const DevBox &bx) {
+    if (rj.metric_enqueued || !rj.ranked) return;
+    rj.metric_enqueued = true;
+    const int npad = c->npad, n = c->n;
+    const hipStream_t rs = rj.rs;
+    if (rj.rank_side) side_wait_for_moves(c, rs);  // the new coordinates are in place on this stream too
+    ScopedTimer t(c, T_OTHER, rs);
+    const int ntile = npad / 64;
+    // scratch of its own: the static-field and pair partials persist between calls
+    hipLaunchKernelGGL(rank_rmin_kernel, dim3(ntile, ntile), dim3(64), 0, rs, a, bx, c->d_rankpart);
+    // (the counters and the "ranking changed" word are cleared by the same launch)
+    hipLaunchKernelGGL(reduce_min_kernel, dim3(1), dim3(256), 0, rs, c->d_rankpart, ntile * ntile,
+                       c->d_res + R_RMIN, c->d_rankcnt, npad, c->d_res + R_RANKCHG);
+    const ChunkPlan cp = chunk_plan(npad, 2048);
+    hipLaunchKernelGGL(rank_count_kernel, dim3(cp.nchunk, ntile), dim3(64), 0, rs, a, c->d_res + R_RMIN, cp.chunk,
+                       c->d_rankcnt);
+    hipLaunchKernelGGL(count_to_rank_kernel, dim3((npad + 255) / 256), dim3(256), 0, rs, npad, c->d_rankcnt,
+                       c->d_rank, n, rj.spec_rank ? (const double *)c->d_rank_used : (const double *)nullptr,
+                       c->d_res + R_RANKCHG);
+}
+
+// (B) and (A), once per call
+static int enqueue_rank(mpmc_hip_ctx *c, RankJob &rj, const DevAtoms &a, const DevBox &bx) {
+    if (rj.enqueued || !rj.ranked) return 0;
+    rj.enqueued = true;
+    const hipStream_t rs = rj.rs;
+    if (rj.spec_rank) {
+        // The ranked view, for the same walk as in the previous call: only what the moved atoms touch is redone.  This
+        // does not depend on the metric, and it is what the main stream waits for at the view switch: it goes FIRST
+        // (unless the metric's kernels are out already: rank_late = 2), the metric's kernels -- whose verdict only the
+        // host reads, at the end of the call -- behind it.  (At 1024 atoms the side stream's eight small launches in
+        // the old order took longer than the main stream's set-up + first sweep, which then waited ~25 us.)
+        SweepView &W = c->view[1];
+        if (rj.rank_side) side_wait_for_moves(c, rs);
+        W.ranked_call = c->energy_calls;
+        if (setup_view(c, W, a, bx, true, true, false, true, rs)) return -1;
+        hipEventRecord(c->ev_rank, rs);
+        enqueue_rank_metric(c, rj, a, bx);
+    } else if (rj.rank_side) {
+        // the metric is only needed after the first sweep: it is computed on the side stream, beside that sweep
+        enqueue_rank_metric(c, rj, a, bx);
+        // the host will sort the metric: bring it over behind the rank kernels, so that at the view switch the host
+        // waits for this copy only (not for the first sweep) and sorts while the device still works on that sweep
+        HIPCHK(hipMemcpyAsync(c->h_rank, c->d_rank, c->n * sizeof(double), hipMemcpyDeviceToHost, rs));
+        hipEventRecord(c->ev_rank, rs);
+    } else {
+        enqueue_rank_metric(c, rj, a, bx);  // (one stream: the metric's kernels in line, the host copies it at the view switch)
+    }
+    c->call.rank_on_side = rj.rank_side && !rj.spec_rank;
+    return 0;
+}
+
+// update_ranking (thole_iterative.c:143-164), host form: the metric comes to the host, is sorted (ranked_walk), and view 1
+// becomes the ranked view -- maintained if the walk is the previous call's, else rebuilt.  On the side stream where the
+// metric was made there, beside the first sweep that the main stream is still working on.
+static int rebuild_ranked_view(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, bool chain_mode) {
+    const int npad = c->npad, n = c->n;
+    SweepView &W = c->view[1];
+    const SweepView &V0 = c->view[0];
+    if (c->call.rank_on_side) {
+        HIPCHK(hipEventSynchronize(c->ev_rank));           // the metric is on the host
+        hipStreamWaitEvent(c->stream, c->ev_rank, 0);      // and d_rank is complete for the main stream
+    } else {
+        HIPCHK(hipMemcpyAsync(c->h_rank, c->d_rank, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    // The ranked view is (re)built on the SIDE stream, where the metric was made, beside the first sweep that
+    // the main stream is still working on -- after a grand-canonical edit that is a whole view (coefficient
+    // tiles, block inverses, tensor tiles: ~100 us at 4096 atoms), which used to wait in the main stream's
+    // queue behind that sweep and then run alone.  (The side stream has nothing else queued yet: the LJ /
+    // Ewald kernels are fed at the end of the call.)
+    const bool view_on_side = c->call.rank_on_side && chain_mode && c->opt.rank_view_side;
+    const hipStream_t ws = view_on_side ? c->stream2 : c->stream;
+    const double *rk = c->h_rank;
+    c->rank_saved.assign(rk, rk + n);  // for mpmc_hip_download_ranking (the full ranked_array is made there)
+    c->perm_ranked = true;
+    // a stable sort of view 0's order (= the caller's atom order, also after grand-canonical edits) by the metric
+    const int nv = (int)V0.h_idx.size();
+    ranked_walk(rk, V0.h_idx, c->h_perm.get());
+    // A single-molecule move rarely changes the ranked order: if the walk is the one of the previous
+    // call, the ranked view's data are still resident and only what the moved atoms touch is redone
+    // (the reference rebuilds everything; so did this engine: 118 us at 4096 atoms).
+    const bool same_walk = (chain_mode ? W.C_valid : (W.A_valid && (W.C_valid || !c->opt.pair_coef))) &&
+                           W.ranked_call + 1 == c->energy_calls && W.nv == nv &&
+                           W.nvpad == V0.nvpad && std::equal(c->h_perm.get(), c->h_perm + nv, W.h_idx.begin());
+    W.ranked_call = c->energy_calls;
+    if (!same_walk) {
+        W.nv = nv;
+        W.nvpad = V0.nvpad;
+        W.h_idx.assign(c->h_perm.get(), c->h_perm + nv);
+        W.slot_of_atom.assign(n, -1);
+        for (int k = 0; k < npad; ++k) c->h_slotmap[k] = -1;
+        for (int k = 0; k < nv; ++k) {
+            W.slot_of_atom[c->h_perm[k]] = k;
+            c->h_slotmap[c->h_perm[k]] = k;
+        }
+        // (pinned sources: asynchronous copies in stream order; the host does not touch them again
+        // before energy_end() has returned)
+        HIPCHK(hipMemcpyAsync(W.d_idx, c->h_perm, nv * sizeof(int), hipMemcpyHostToDevice, ws));
+        HIPCHK(hipMemcpyAsync(W.d_slot, c->h_slotmap, npad * sizeof(int), hipMemcpyHostToDevice, ws));
+        W.A_valid = false;
+        W.C_valid = false;
+    }
+    if (setup_view(c, W, a, bx, same_walk, c->opt.pair_coef != 0, !chain_mode, chain_mode,
+                   view_on_side ? ws : (hipStream_t) nullptr))
+        return -1;
+    // what later speculative calls are checked against: the metric this walk was sorted from
+    HIPCHK(hipMemcpyAsync(c->d_rank_used, c->d_rank, n * sizeof(double), hipMemcpyDeviceToDevice, ws));
+    c->rank_used_valid = true;
+    if (view_on_side) {  // the main stream picks the ranked view up at the view switch
+        hipEventRecord(c->ev_rank, ws);
+        hipStreamWaitEvent(c->stream, c->ev_rank, 0);
+    }
+    return 0;
+}
+
+// The switch to the ranked view behind the first sweep: the view is ready (speculative form: maintained on the side
+// stream; else rebuild_ranked_view()), then the static field and current dipoles of the same atoms go from view 0 to
+// view 1 and the per-call scratch is cleared.  The solve goes on in view 1: V, mu_in, mu_out are its.
+static int switch_to_ranked_view(mpmc_hip_ctx *c, const RankJob &rj, const DevAtoms &a, const DevBox &bx, bool chain_mode,
+                                 SweepView *&V, double *&mu_in, double *&mu_out) {
+    SweepView &W = c->view[1];
+    ScopedTimer t(c, T_OTHER);
+    if (rj.spec_rank) {
+        // the walk of the previous call, already maintained on the side stream
+        hipStreamWaitEvent(c->stream, c->ev_rank, 0);
+    } else if (rebuild_ranked_view(c, a, bx, chain_mode)) {
+        return -1;
+    }
+    const dim3 gvec((V->nvpad + 255) / 256), bvec(256);
+    hipLaunchKernelGGL(switch_view_kernel, gvec, bvec, 0, c->stream, W.nv, W.nvpad, W.d_idx, c->view[0].d_slot,
+                       c->view[0].es, mu_in, W.es, W.mu0, W.efchg, W.rrms);
+    V = &W;
+    mu_in = W.mu0;
+    mu_out = W.mu1;
+    return 0;
+}
+
 static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx, int *n_iter, int *iter_success) {
     const mpmc_hip_params &P = c->par;
-    const int npad = c->npad, n = c->n;
+    const int n = c->n;
     const bool gs = c->call.gs_mode;
     const bool want_rrms = P.polar_rrms || P.polar_precision > 0.0;
     *n_iter = 0;
@@ -930,65 +1026,14 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
     //  own first kernels to be enqueued; the side stream still has the whole first sweep to do its work in.)
     // Two parts: (A) the metric's four kernels, (B) the ranked view's maintenance (speculative form) or the copy for the
     // host's sort, and the event the main stream waits for at the view switch.
-    bool rank_enqueued = false, rank_metric_enqueued = false;
-    int rank_rc = 0;
-    const bool rank_side = ranked && (spec_rank || (c->opt.overlap && chain_mode));
-    const hipStream_t rs = rank_side ? c->stream2 : c->stream;
-    auto enqueue_rank_metric = [&]() {
-        if (rank_metric_enqueued || !ranked) return;
-        rank_metric_enqueued = true;
-        if (rank_side) side_wait_for_moves(c, rs);  // the new coordinates are in place on this stream too
-        ScopedTimer t(c, T_OTHER, rs);
-        const int ntile = npad / 64;
-        // scratch of its own: the static-field and pair partials persist between calls
-        hipLaunchKernelGGL(rank_rmin_kernel, dim3(ntile, ntile), dim3(64), 0, rs, a, bx, c->d_rankpart);
-        // (the counters and the "ranking changed" word are cleared by the same launch)
-        hipLaunchKernelGGL(reduce_min_kernel, dim3(1), dim3(256), 0, rs, c->d_rankpart, ntile * ntile,
-                           c->d_res + R_RMIN, c->d_rankcnt, npad, c->d_res + R_RANKCHG);
-        int nchunk = std::max(1, std::min(ntile, 2048 / ntile));
-        const int chunk = round_up((npad + nchunk - 1) / nchunk, 64);
-        nchunk = (npad + chunk - 1) / chunk;
-        hipLaunchKernelGGL(rank_count_kernel, dim3(nchunk, ntile), dim3(64), 0, rs, a, c->d_res + R_RMIN, chunk,
-                           c->d_rankcnt);
-        hipLaunchKernelGGL(count_to_rank_kernel, dim3((npad + 255) / 256), dim3(256), 0, rs, npad, c->d_rankcnt,
-                           c->d_rank, n, spec_rank ? (const double *)c->d_rank_used : (const double *)nullptr,
-                           c->d_res + R_RANKCHG);
-    };
-    auto enqueue_rank = [&]() {
-        if (rank_enqueued || !ranked) return;
-        rank_enqueued = true;
-        rank_rc = [&]() -> int {
-        if (spec_rank) {
-            // The ranked view, for the same walk as in the previous call: only what the moved atoms touch is redone.  This
-            // does not depend on the metric, and it is what the main stream waits for at the view switch: it goes FIRST
-            // (unless the metric's kernels are out already: rank_late = 2), the metric's kernels -- whose verdict only the
-            // host reads, at the end of the call -- behind it.  (At 1024 atoms the side stream's eight small launches in
-            // the old order took longer than the main stream's set-up + first sweep, which then waited ~25 us.)
-            if (rank_side) side_wait_for_moves(c, rs);
-            W.ranked_call = c->energy_calls;
-            if (setup_view(c, W, a, bx, true, true, false, true, rs)) return -1;
-            hipEventRecord(c->ev_rank, rs);
-            enqueue_rank_metric();
-        } else if (rank_side) {
-            // the metric is only needed after the first sweep: it is computed on the side stream, beside that sweep
-            enqueue_rank_metric();
-            // the host will sort the metric: bring it over behind the rank kernels, so that at the view switch the host
-            // waits for this copy only (not for the first sweep) and sorts while the device still works on that sweep
-            HIPCHK(hipMemcpyAsync(c->h_rank, c->d_rank, n * sizeof(double), hipMemcpyDeviceToHost, rs));
-            hipEventRecord(c->ev_rank, rs);
-        } else {
-            enqueue_rank_metric();  // (one stream: the metric's kernels in line, the host copies it at the view switch)
-        }
-        c->call.rank_on_side = rank_side && !spec_rank;
-        return 0;
-        }();
-    };
+    RankJob rj;
+    rj.ranked = ranked;
+    rj.spec_rank = spec_rank;
+    rj.rank_side = ranked && (spec_rank || (c->opt.overlap && chain_mode));
+    rj.rs = rj.rank_side ? c->stream2 : c->stream;
     // (only the speculative form waits: when the host has to sort the metric in the middle of the call, the sooner the
     //  rank kernels start the sooner it can)
-    if (!(c->opt.rank_late && spec_rank)) {
-        enqueue_rank();
-        if (rank_rc) return -1;
-    }
+    if (!(c->opt.rank_late && spec_rank) && enqueue_rank(c, rj, a, bx)) return -1;
 
     // ---- A matrix of the polarizable block (thole_matrix.c:38-146)
     SweepView *V = &c->view[0];
@@ -1006,7 +1051,7 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
     // (rank_late = 2: the metric's four kernels go out here, behind the main stream's first launches -- the moved blocks'
     //  coefficient update and block inverse keep the device busy for ~25 us while the host enqueues them -- so that the
     //  heavy ranking kernels run beside the view set-up rather than beside the latency-bound chain of the first sweep)
-    if (ranked && spec_rank && c->opt.rank_late >= 2) enqueue_rank_metric();
+    if (ranked && spec_rank && c->opt.rank_late >= 2) enqueue_rank_metric(c, rj, a, bx);
 
     // ---- static field for every atom (thole_field.c:14-36)
     if (launch_field(c, a, bx)) return -1;
@@ -1048,36 +1093,17 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
                 *iter_success = 1;
                 break;
             }
-            double w_new = 1.0, w_old = 0.0;
-            if (P.polar_sor) {
-                w_new = P.polar_gamma;
-                w_old = 1.0 - P.polar_gamma;
-            } else if (P.polar_esor) {
-                w_old = std::exp(-P.polar_gamma * iteration_counter);
-                w_new = 1.0 - w_old;
-            }
+            double w_new, w_old;
+            mixing_weights(P.polar_sor, P.polar_esor, P.polar_gamma, iteration_counter, w_new, w_old);
             const double *palmo_mu = mu_in;  // Jacobi: mu still holds the pre-sweep values
             if (!gs) {
-                SweepParams sp;
-                sp.w_new = w_new;
-                sp.w_old = w_old;
-                sp.want_rrms = want_rrms;
-                sp.want_err = P.polar_precision > 0.0;
-                sp.err_slot = iteration_counter;
-                sp.skip_sums = (P.polar_precision == 0.0 && iteration_counter < P.polar_max_iter) ? 1 : 0;
-                // the deferral: U_pol comes from the finish of sweep m = ceil(n / 2) (pair_finish_kernel); no other finish
-                // of the call writes the block sums
+                const SweepParams sp = jacobi_sweep_params(iteration_counter, P.polar_max_iter, P.polar_precision, want_rrms,
+                                                           defer, w_new, w_old);
                 const int mid = (P.polar_max_iter + 1) / 2;
-                if (defer) {
-                    const bool odd = P.polar_max_iter & 1;
-                    sp.skip_sums = 1;
-                    if (odd && iteration_counter == P.polar_max_iter - mid) sp.energy_mode |= kEnergyStoreSums;
-                    if (iteration_counter == mid) sp.energy_mode |= kEnergyMid | (odd ? kEnergyPrevSums : 0);
-                }
                 // sweep n, and sweeps m + 1 .. n - 1 once the record HAS gone out behind the finish of sweep m (published: not
                 // on a timed or captured call, nor while a builder join is pending): recorded in order, not launched
                 // (complete_pending_sweep()).  The ping-pong below goes on as if they had been.
-                if (defer && (iteration_counter == P.polar_max_iter || (iteration_counter > mid && c->call.published))) {
+                if (sweep_is_pending(iteration_counter, P.polar_max_iter, defer, c->call.published)) {
                     PendingSweep &ps = c->psweep;
                     ps.view = V;
                     ps.bx = bx;
@@ -1091,13 +1117,13 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
                 }
                 // the device is busy now: feed the LJ/Ewald stream (its ~55 us of kernels only have to be done by the
                 // time the last sweep is)
-                if (c->call.enqueue_side && (iteration_counter == c->opt.side_after || P.polar_max_iter < c->opt.side_after)) c->call.enqueue_side();
+                if (iteration_counter == c->opt.side_after || P.polar_max_iter < c->opt.side_after) feed_side_stream(c);
                 // U_pol is complete behind this finish: the record goes out here, and sweeps m + 1 .. n - 1, which only a
                 // later reader of the dipoles needs, are then left to that reader (above) (enqueue_direct; the side stream
                 // is fed first, so that the host is not left waiting for a record whose other half has not been enqueued)
-                if (defer && iteration_counter == mid && c->call.publish_early) {
-                    if (c->call.enqueue_side) c->call.enqueue_side();
-                    c->call.publish_early();
+                if (defer && iteration_counter == mid && c->call.may_publish_early) {
+                    feed_side_stream(c);
+                    publish_early(c);
                 }
             } else {
                 GsFinishArgs gfa;
@@ -1146,112 +1172,16 @@ static int run_polarization(mpmc_hip_ctx *c, const DevAtoms &a, const DevBox &bx
 
             // update_ranking (thole_iterative.c:143-164): stable descending sort of rank_metric.  After the
             // first call the order is final, so the ranked view is set up exactly once per energy().
-            if (ranked && !rank_enqueued) {  // the first sweep is enqueued: now the ranking work, on its stream
-                enqueue_rank();
-                if (rank_rc) return -1;
-            }
+            // the first sweep is enqueued: now the ranking work, on its stream
+            if (enqueue_rank(c, rj, a, bx)) return -1;
             if (ranked && keep_iterating && !ranked_active) {
-                ScopedTimer t(c, T_OTHER);
-                if (spec_rank) {
-                    // the walk of the previous call, already maintained on the side stream
-                    hipStreamWaitEvent(c->stream, c->ev_rank, 0);
-                } else {
-                    if (c->call.rank_on_side) {
-                        HIPCHK(hipEventSynchronize(c->ev_rank));           // the metric is on the host
-                        hipStreamWaitEvent(c->stream, c->ev_rank, 0);      // and d_rank is complete for the main stream
-                    } else {
-                        HIPCHK(hipMemcpyAsync(c->h_rank, c->d_rank, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-                        HIPCHK(hipStreamSynchronize(c->stream));
-                    }
-                    // The ranked view is (re)built on the SIDE stream, where the metric was made, beside the first sweep that
-                    // the main stream is still working on -- after a grand-canonical edit that is a whole view (coefficient
-                    // tiles, block inverses, tensor tiles: ~100 us at 4096 atoms), which used to wait in the main stream's
-                    // queue behind that sweep and then run alone.  (The side stream has nothing else queued yet: the LJ /
-                    // Ewald kernels are fed at the end of the call.)
-                    const bool view_on_side = c->call.rank_on_side && chain_mode && c->opt.rank_view_side;
-                    const hipStream_t ws = view_on_side ? c->stream2 : c->stream;
-                    const double *rk = c->h_rank;
-                    c->rank_saved.assign(rk, rk + n);  // for mpmc_hip_download_ranking (the full ranked_array is made there)
-                    c->perm_ranked = true;
-                    // the polarizable sites keep their relative order in the ranked walk: a stable sort of view 0's
-                    // order (= the caller's atom order, also after grand-canonical edits) by the metric
-                    // (the metric is a neighbour COUNT: a stable counting sort, O(n), instead of a comparison sort --
-                    // this runs on the host in the middle of a call, every grand-canonical step)
-                    const std::vector<int> &v0idx = c->view[0].h_idx;
-                    const int nv = (int)v0idx.size();
-                    {
-                        constexpr int kMaxRank = 1024;
-                        bool small = true;
-                        int cnt[kMaxRank + 1] = {0};
-                        for (int k = 0; k < nv && small; ++k) {
-                            const double r = rk[v0idx[k]];
-                            if (!(r >= 0.0 && r < kMaxRank && r == (double)(int)r)) small = false;
-                            else ++cnt[(int)r];
-                        }
-                        if (small) {
-                            int start[kMaxRank + 1];
-                            int acc = 0;
-                            for (int r = kMaxRank - 1; r >= 0; --r) {  // descending metric
-                                start[r] = acc;
-                                acc += cnt[r];
-                            }
-                            for (int k = 0; k < nv; ++k) c->h_perm[start[(int)rk[v0idx[k]]]++] = v0idx[k];
-                        } else {
-                            std::vector<int> walk(v0idx);
-                            std::stable_sort(walk.begin(), walk.end(), [rk](int x, int y) { return rk[x] > rk[y]; });
-                            std::copy(walk.begin(), walk.end(), c->h_perm.get());
-                        }
-                    }
-                    // A single-molecule move rarely changes the ranked order: if the walk is the one of the previous
-                    // call, the ranked view's data are still resident and only what the moved atoms touch is redone
-                    // (the reference rebuilds everything; so did this engine: 118 us at 4096 atoms).
-                    const bool same_walk = (chain_mode ? W.C_valid : (W.A_valid && (W.C_valid || !c->opt.pair_coef))) &&
-                                           W.ranked_call + 1 == c->energy_calls && W.nv == nv &&
-                                           W.nvpad == V->nvpad && std::equal(c->h_perm.get(), c->h_perm + nv, W.h_idx.begin());
-                    W.ranked_call = c->energy_calls;
-                    if (!same_walk) {
-                        W.nv = nv;
-                        W.nvpad = V->nvpad;
-                        W.h_idx.assign(c->h_perm.get(), c->h_perm + nv);
-                        W.slot_of_atom.assign(n, -1);
-                        for (int k = 0; k < npad; ++k) c->h_slotmap[k] = -1;
-                        for (int k = 0; k < nv; ++k) {
-                            W.slot_of_atom[c->h_perm[k]] = k;
-                            c->h_slotmap[c->h_perm[k]] = k;
-                        }
-                        // (pinned sources: asynchronous copies in stream order; the host does not touch them again
-                        // before energy_end() has returned)
-                        HIPCHK(hipMemcpyAsync(W.d_idx, c->h_perm, nv * sizeof(int), hipMemcpyHostToDevice, ws));
-                        HIPCHK(hipMemcpyAsync(W.d_slot, c->h_slotmap, npad * sizeof(int), hipMemcpyHostToDevice, ws));
-                        W.A_valid = false;
-                        W.C_valid = false;
-                    }
-                    if (setup_view(c, W, a, bx, same_walk, c->opt.pair_coef != 0, !chain_mode, chain_mode,
-                                   view_on_side ? ws : (hipStream_t) nullptr))
-                        return -1;
-                    // what later speculative calls are checked against: the metric this walk was sorted from
-                    HIPCHK(hipMemcpyAsync(c->d_rank_used, c->d_rank, n * sizeof(double), hipMemcpyDeviceToDevice, ws));
-                    c->rank_used_valid = true;
-                    if (view_on_side) {  // the main stream picks the ranked view up at the view switch, below
-                        hipEventRecord(c->ev_rank, ws);
-                        hipStreamWaitEvent(c->stream, c->ev_rank, 0);
-                    }
-                }
-                // static field and current dipoles of the same atoms, view 0 -> view 1; per-call scratch cleared
-                hipLaunchKernelGGL(switch_view_kernel, gvec, bvec, 0, c->stream, W.nv, W.nvpad, W.d_idx, c->view[0].d_slot,
-                                   c->view[0].es, mu_in, W.es, W.mu0, W.efchg, W.rrms);
-                V = &W;
-                mu_in = W.mu0;
-                mu_out = W.mu1;
+                if (switch_to_ranked_view(c, rj, a, bx, chain_mode, V, mu_in, mu_out)) return -1;
                 ranked_active = true;
             }
         }
     }
     *n_iter = iteration_counter;
-    if (ranked && !rank_enqueued) {  // (no sweep ran: the metric is still part of the call's results)
-        enqueue_rank();
-        if (rank_rc) return -1;
-    }
+    if (enqueue_rank(c, rj, a, bx)) return -1;  // (no sweep ran: the metric is still part of the call's results)
 
     {
         // calibration for the event-pair timings above: two event records with nothing in between

@@ -98,7 +98,7 @@ __device__ __forceinline__ int minv_index(int row, int col, int e) {  // row > c
 // as 36 loads:
 //   Pnb[t * 36864 + ((((j >> 3) * 4 + ((j & 7) >> 1)) * 9 + e) * 64 + i) * 2 + (j & 1)]
 constexpr int kPnbDoubles = 64 * 9 * 64;  // per block (294 912 B)
-constexpr int kGsMaxLag = 4;              // cached lags: P (1), Q (2), and up to two more
+// (kGsMaxLag, the number of cached lags -- P (1), Q (2), and up to two more: step_pods.h)
 static_assert(kGsMaxLag == kGsArmRegions, "one armed hand-off region per lag (region 0 = mu_t itself)");
 __device__ __forceinline__ int pnb_index(int i, int j, int e) {
     return ((((j >> 3) * 4 + ((j & 7) >> 1)) * 9 + e) * 64 + i) * 2 + (j & 1);
@@ -272,11 +272,7 @@ __device__ __forceinline__ void lds_tensor_wait(LdsTensor &t) {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t.a), "+v"(t.b), "+v"(t.c));
 }
 
-constexpr int kMaxBlockList = 48;
-struct BlockList {
-    int n;
-    int blk[kMaxBlockList];
-};
+// (BlockList, kMaxBlockList and GsBuild, the lists the kernel below works through: step_pods.h)
 
 // ---------------------------------------------------------------------------------------------
 // M_t = (I + D L)^-1 of block t = blk[blockIdx.y] (or blockIdx.y with nsel = 0): forward substitution on the
@@ -302,15 +298,6 @@ constexpr int kInverseLds = (kGsPairs * 6 + 8 + 4 * 64) * 8;  // tensors + one a
 // Two geometries (WAVES waves per workgroup, 192 / WAVES workgroups per block): 4 waves x 48 workgroups finishes a
 // couple of blocks soonest (17.5 vs 24 us: the moved atoms' blocks of view 0 are on the step's critical path), 16 waves
 // x 12 workgroups repeats the tile expansion a quarter as often and rebuilds a whole view 3.6x faster (46 vs 166 us).
-struct GsBuild {
-    BlockList inv;             // z-slice 0: M_t of these blocks
-    BlockList own;             // z-slice 1: every L(k)_t, k = 1 .. min(t, nlag), of these blocks (their M_t changed), ONE pass
-    BlockList nb[kGsMaxLag];   // z-slice 1 + k: L(k)_t alone (the tile (t-k, t) changed: t = a changed block + k)
-    double *Minv;
-    double *Lnb[kGsMaxLag];
-    int nlag;
-    int nb_all;                // > 0: every block of the view (slices 0 and 1 take blockIdx.y as the block, the others nothing)
-};
 
 template <int ORTHO, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void gs_block_inverse_kernel(const double2 *__restrict__ C, int ntld,

@@ -637,21 +637,7 @@ __device__ __forceinline__ double2 stream_load2(const double *p) {
     return make_double2(v.x, v.y);
 }
 
-struct SweepParams {
-    double w_new;    // weight of new_mu in mu_out (1 for plain Jacobi)
-    double w_old;    // weight of old mu
-    int want_rrms;   // polar_rrms || polar_precision > 0
-    int want_err;    // polar_precision > 0: the host reads max (new-old)^2 after every sweep
-    int err_slot;    // index into errmax[] for this iteration
-    int skip_sums;   // 1: the block's energy / RRMS sums are not wanted (an iteration that is known not to be the last)
-    // Fixed-count plain Jacobi with the last sweep deferred (pair_finish_kernel): which of the
-    // extra jobs this sweep's finish does.  0 everywhere else.
-    int energy_mode = 0;      // kEnergyStoreSums | kEnergyMid [| kEnergyPrevSums]
-};
-// n sweeps, m = ceil(n / 2); s_k = T mu_{k-1} are the sums of sweep k
-constexpr int kEnergyStoreSums = 1;  // sweep n - m of an odd n: keep the sums s_{n-m} per site (SweepView::tmu0)
-constexpr int kEnergyMid = 2;        // sweep m: the block's energy share is sum_i (mu_m.E - (mu_m - mu_{m-1}).s_{n-m})
-constexpr int kEnergyPrevSums = 4;   // with kEnergyMid, odd n: s_{n-m} are the stored sums, not this sweep's own
+// (SweepParams and the kEnergy* bits of its energy_mode: step_pods.h)
 
 template <int MODE>
 __global__ __launch_bounds__(64) void sweep_kernel(const double *__restrict__ A, int lda, int npad,
