@@ -151,8 +151,11 @@ void mpmc_hip_destroy(mpmc_hip_ctx *ctx);
  *                          kernel no longer uses: it holds P_t = M_t D T(t,t-1), built in the block-inverse launch);
  *   "gs_lags"             (default 3; 2 .. 4): how many of a block's most recent sources the chain kernel takes from cached
  *                          matrices L(k)_t = M_t D T(t,t-k) (k = 1: main workgroup's registers, k >= 2: one auxiliary workgroup
- *                          each) instead of from the pair coefficients; rounding of the sweep differs at 1e-13 between values; a
- *                          view that is rebuilt as a whole in consecutive calls (grand-canonical chains) uses 2;
+ *                          each) instead of from the pair coefficients; rounding of the sweep differs at 1e-13 between values; the
+ *                          count belongs to a VIEW: one that is rebuilt as a whole in three consecutive calls (the evaluation of
+ *                          an upload counts) uses min(2, gs_lags) from the third on, and the option's value again from the first whole
+ *                          rebuild that does not directly follow another -- the ranked view of a grand-canonical chain, whose atom-order view keeps its prefix and the option's
+ *                          value, and both views of a context with incremental_amatrix = 0;
  *   "gs_build_fork"       (default 1): the chain-data rebuild of the main stream's view runs on a stream of its own beside the
  *                          step's next launches (views of 24+ blocks; 2 = always, 0 = in the main stream; bit-neutral);
  *   "gs_side_waves"       (default 0): the OTHER view's incremental rebuild in the side stream takes the fastest workgroup geometry

@@ -104,14 +104,7 @@ __device__ __forceinline__ int pnb_index(int i, int j, int e) {
     return ((((j >> 3) * 4 + ((j & 7) >> 1)) * 9 + e) * 64 + i) * 2 + (j & 1);
 }
 
-// number of workgroups in front of block t's (= tickets before aux(t, nlag)), and of the whole chain with t = nb
-__host__ __device__ inline int gs_chain_ticket_base(int t, int nlag) {
-    // block u has 1 + min(u, nlag) - 1 ... = max(1, min(u, nlag)) workgroups
-    int n = 0;
-    for (int u = 0; u < t && u < nlag; ++u) n += (u < 1 ? 1 : u);
-    if (t > nlag) n += (t - nlag) * nlag;
-    return n;
-}
+// (gs_chain_ticket_base(), the number of workgroups in front of block t's: step_pods.h)
 
 struct GsChain {
     const double2 *C;  // pair-coefficient tiles of the view (kernels_coef.h)

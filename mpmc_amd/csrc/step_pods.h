@@ -33,6 +33,19 @@ constexpr int kEnergyPrevSums = 4;   // with kEnergyMid, odd n: s_{n-m} are the 
 
 constexpr int kGsMaxLag = 4;              // cached lags: P (1), Q (2), and up to two more
 
+// ---- the chain kernel's workgroups (kernels_gs_chain.h): block u has max(1, min(u, nlag)) of them -- main(u) and one
+// auxiliary workgroup aux(u, k) per lag k = 2 .. min(u, nlag).  Number of workgroups in front of block t's (= tickets before
+// aux(t, nlag)), and of the whole chain with t = nb.  (constexpr: the device compiler takes a constexpr function for the
+// host and the device alike, so the kernel, the host's grid size and the CPU check of tests/step_plan_check.cpp run the
+// same text and this header still names nothing of HIP.)
+constexpr int gs_chain_ticket_base(int t, int nlag) {
+    // block u has 1 + min(u, nlag) - 1 ... = max(1, min(u, nlag)) workgroups
+    int n = 0;
+    for (int u = 0; u < t && u < nlag; ++u) n += (u < 1 ? 1 : u);
+    if (t > nlag) n += (t - nlag) * nlag;
+    return n;
+}
+
 constexpr int kMaxBlockList = 48;
 struct BlockList {
     int n;

@@ -5,6 +5,8 @@ Sized cases come from synth.s_pol by setting chosen alpha to 0, which hits EXACT
 sites inside the 64-site blocks: 1, 2, 63, 64, 65, 128, 129 (block edges), 1024 / 1025 (the one-launch solver without and
 with finisher workgroups), 1344 / 1345 (21 and 22 blocks: the last one-launch size and the first that defers sweeps); 1024 and 1344 are 1025 and 1345
 with one more alpha set to 0, so three geometries above 1024 sites are built in all (1025, 1345 and 1345 after a move).
+GS_LAG_SIZES are the views of 3 .. 7 blocks at which the Gauss-Seidel chain's cached lags first have a source and its
+far-source loop first has one and two (tests/test_gpu_gs_lags.py); 'nv321_m2' is nv321 after the first two of lag_moves(321).
 Special geometries are small: half-box ties in a sheared cell, polarizable sites 1e-1 .. 1e-3 A apart across a cell face,
 two coincident polarizable sites, molecules moved by 10^4 lattice vectors, a frozen polarizable framework.
 
@@ -35,6 +37,18 @@ GS_VARIANTS = {
     "gs_ranked": dict(BASE, polar_max_iter=4, polar_gs_ranked=1),
     "production": PRODUCTION,
 }
+# views of the chain kernel's lag machinery (option gs_lags = nlag in 2 .. 4; block t takes its sources t-1 .. t-nlag from cached
+# matrices, lag k >= 2 through an auxiliary workgroup, and the sources s <= t-nlag-1 from the pair coefficients):
+#   129 = 3 blocks: lag 2 first has a source; no far source under any nlag
+#   193 = 4 blocks: aux(t = 3, 3) reads block 0; one far source under nlag = 2
+#   256 = 4 blocks, the last one full
+#   257 = 5 blocks: aux(t = 4, 4) reads block 0; one far source under nlag = 3, two under nlag = 2; a last block of one site
+#   321 = 6 blocks: one far source under nlag = 4, two under nlag = 3
+#   385 = 7 blocks: two far sources under nlag = 4
+GS_LAG_SIZES = (129, 193, 256, 257, 321, 385)
+GS_LAG_COUNTS = (2, 3, 4)
+GS_LAG_VARIANTS = {"gs": GS_VARIANTS["gs"], "production": PRODUCTION}
+GS_LAG_MOVED_SIZES = (321, 385)  # six and seven blocks: the incremental chain data behind a moved block
 SHEARED_GS = dict(BASE, polar_max_iter=3, polar_gs=1)  # on sheared_640: the multi-block chain outside the orthorhombic branch
 JACOBI_VARIANTS = {  # at 129 sites
     "sor": dict(BASE, polar_max_iter=6, polar_sor=1, polar_gamma=0.8),
@@ -45,7 +59,7 @@ JACOBI_VARIANTS = {  # at 129 sites
     "zodid": dict(BASE, polar_zodid=1),
 }
 # atoms of the box a sized view is cut from: 3 polarizable sites per five-site molecule
-_PARENT = {1024: 1750, 1025: 1750, 1344: 2300, 1345: 2300}
+_PARENT = {1024: 1750, 1025: 1750, 1344: 2300, 1345: 2300, 193: 700, 256: 700, 257: 700, 321: 700, 385: 700}
 
 
 _ONE_LESS = {1024: 1025, 1344: 1345}  # the same geometry with one more alpha set to 0: one tensor serves both
@@ -191,7 +205,15 @@ def coincident_only():
 
 @functools.lru_cache(maxsize=None)
 def system(name):
-    """name: 'nv<count>', 'nv1345_moved' or a key of SPECIAL"""
+    """name: 'nv<count>', 'nv1345_moved', 'nv<count>_m<k>' (after the first k of lag_moves(count)) or a key of SPECIAL"""
+    if name.startswith("nv") and "_m" in name and name.split("_m")[1].isdigit():
+        nv, k = int(name[2:].split("_m")[0]), int(name.split("_m")[1])
+        s = system("nv%d" % nv)
+        out = dict(s)
+        out["pos"] = s["pos"].copy()
+        for _, first, shift, _ in lag_moves(nv)[:k]:
+            out["pos"][first:first + 5] += shift
+        return out
     if name == "nv1345_moved":
         s = system("nv1345")
         first, new = molecule_move(s)
@@ -208,6 +230,33 @@ def molecule_move(s, k=100, shift=(0.11, -0.07, 0.05)):
     """(first, new positions) of the k-th five-site molecule displaced rigidly"""
     first = 5 * k
     return first, np.asarray(s["pos"])[first:first + 5] + np.asarray(shift)
+
+
+_LAG_SHIFTS = ((0.11, -0.07, 0.05), (-0.06, 0.09, 0.08), (0.05, 0.10, -0.07), (-0.09, -0.04, 0.10))
+
+
+@functools.lru_cache(maxsize=None)
+def lag_moves(nv):
+    """Four rigid moves of one five-site molecule each, made one after the other on sized(nv) under plain Gauss-Seidel (the
+    view is then the polarizable sites in atom order, 64 to a block): (label, first atom, displacement, view blocks of the
+    molecule's polarizable sites).  A molecule all in block 0, one all in the middle block, the molecule of the last site,
+    and one that straddles two inner blocks.  At 321 and 385 sites the last block holds ONE site, so no molecule lies in
+    it alone: the molecule of that site reaches back into the block before it, which is asserted instead."""
+    alpha = sized(nv)["alpha"]
+    view = np.flatnonzero(alpha != 0.0)
+    nt = (nv + 63) // 64
+    blocks = {}
+    for k, a in enumerate(view):
+        blocks.setdefault(int(a) // 5, []).append(k // 64)
+    sets = {m: tuple(sorted(set(b))) for m, b in blocks.items()}
+    pick = lambda want: next(m for m in sorted(sets) if want(m, sets[m]))
+    chosen = [("block 0", pick(lambda m, b: b == (0,) and len(blocks[m]) >= 2)),
+              ("middle block", pick(lambda m, b: b == (nt // 2,) and len(blocks[m]) >= 2)),
+              ("last block", int(view[-1]) // 5),
+              ("two blocks", pick(lambda m, b: len(b) == 2 and 1 <= b[0] and b[1] < nt - 1))]
+    assert len(set(m for _, m in chosen)) == 4, chosen
+    assert nt - 1 in sets[chosen[2][1]], (nv, sets[chosen[2][1]])
+    return tuple((label, 5 * m, np.array(shift), sets[m]) for (label, m), shift in zip(chosen, _LAG_SHIFTS))
 
 
 @functools.lru_cache(maxsize=None)
@@ -242,6 +291,15 @@ def cpu_matrix():
     for name, p in JACOBI_VARIANTS.items():
         out.append(("nv129", name, p))
     out.append(("sheared_640", "gs3", SHEARED_GS))
+    # tests/test_gpu_gs_lags.py: gs_lags is an option of the engine, not a flag -- one row serves its three values
+    for nv in GS_LAG_SIZES:
+        for name, p in GS_LAG_VARIANTS.items():
+            if ("nv%d" % nv, name, p) not in out:
+                out.append(("nv%d" % nv, name, p))
+    for nv in GS_LAG_MOVED_SIZES:
+        for k in range(1, len(lag_moves(nv)) + 1):
+            for name, p in GS_LAG_VARIANTS.items():
+                out.append(("nv%d_m%d" % (nv, k), name, p))
     for name in SPECIAL:
         out.append((name, "jacobi4", JACOBI4))
         out.append((name, "production", PRODUCTION))

@@ -84,6 +84,24 @@ static void chain_plans() {
     }
 }
 
+// ---- the chain kernel's grid: block t has main(t) and aux(t, k), k = 2 .. min(t, nlag) (kernels_gs_chain.h, "Work
+// decomposition"), so max(1, min(t, nlag)) tickets, and gs_chain_ticket_base(t, nlag) counts those of the blocks in front of
+// t -- the host's grid size with t = nt, and the kernel's own origin of block t's tickets.  (The kernel's decode of a ticket
+// into a block and a lag is written out in gs_chain_kernel and is not reachable from here.)
+static void chain_tickets() {
+    for (int nlag = 2; nlag <= kGsMaxLag; ++nlag) {
+        CHECK(gs_chain_ticket_base(0, nlag) == 0, "nlag %d: block 0 starts at ticket %d", nlag, gs_chain_ticket_base(0, nlag));
+        int roles = 0;
+        for (int t = 0; t < 300; ++t) {  // (nt = t + 1 = 1 .. 300)
+            const int cnt = std::max(1, std::min(t, nlag));
+            CHECK(gs_chain_ticket_base(t + 1, nlag) - gs_chain_ticket_base(t, nlag) == cnt, "nlag %d block %d", nlag, t);
+            roles += cnt;
+            CHECK(gs_chain_ticket_base(t + 1, nlag) == roles, "nlag %d nt %d: grid %d, roles %d", nlag, t + 1,
+                  gs_chain_ticket_base(t + 1, nlag), roles);
+        }
+    }
+}
+
 // ---- ranked walk
 static void check_walk(const std::vector<double> &metric, const std::vector<int> &order) {
     std::vector<int> want(order);
@@ -202,6 +220,7 @@ static void small_plans() {
 
 int main() {
     chain_plans();
+    chain_tickets();
     ranked_walks();
     sweep_schedule();
     small_plans();

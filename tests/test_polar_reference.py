@@ -184,6 +184,30 @@ def test_oracle_is_within_the_bound(case, variant, params):
     assert d <= allow, (case, variant, want["polarization_energy"], float(res["upol"]), d, allow)
 
 
+@pytest.mark.parametrize("nv", pc.GS_LAG_MOVED_SIZES)
+def test_lag_moves_touch_the_view_blocks_they_are_named_for(nv):
+    """the moves of tests/test_gpu_gs_lags.py: the blocks restated from the view order (polarizable sites in atom order,
+    64 to a block), four different molecules, and each moved geometry differs from the one before in that molecule only"""
+    s0 = pc.system("nv%d" % nv)
+    view = np.flatnonzero(s0["alpha"] != 0.0)
+    nt = (nv + 63) // 64
+    assert len(view) == nv and nt in (6, 7)
+    moves = pc.lag_moves(nv)
+    assert len(set(first for _, first, _, _ in moves)) == 4
+    for k, (label, first, shift, blocks) in enumerate(moves, 1):
+        slots = [i for i, a in enumerate(view) if first <= a < first + 5]
+        assert len(slots) >= 2 and tuple(sorted(set(i // 64 for i in slots))) == blocks, (label, slots)
+        before, after = pc.system("nv%d_m%d" % (nv, k - 1) if k > 1 else "nv%d" % nv), pc.system("nv%d_m%d" % (nv, k))
+        d = after["pos"] - before["pos"]
+        assert np.array_equal(after["pos"][first:first + 5], before["pos"][first:first + 5] + shift) and shift.any()
+        d[first:first + 5] = 0.0
+        assert not d.any() and np.array_equal(after["alpha"], s0["alpha"])
+    assert [m[3] for m in moves[:3]] == [(0,), (nt // 2,), (nt - 2, nt - 1)]  # (the last block holds one site)
+    assert view[-1] // 5 == moves[2][1] // 5 and (nv - 1) // 64 == nt - 1 and nv % 64 == 1
+    b = moves[3][3]
+    assert len(b) == 2 and b[1] == b[0] + 1 and 1 <= b[0] and b[1] < nt - 1
+
+
 def test_divergence_falls_back_to_alpha_E_at_128_iterations():
     s = synth.s_pol(320, spacing=3.0)
     s["alpha"] = s["alpha"] * 40.0

@@ -1,5 +1,5 @@
 """The host's step plans (mpmc_amd/csrc/step_plan.h: which chain data a move invalidates, the ranked walk, what each Jacobi
-sweep's finish does, blocks_of, chunking, molecule placement) on a CPU: tests/step_plan_check.cpp, a stand-alone program,
+sweep's finish does, blocks_of, chunking, molecule placement; step_pods.h: the chain kernel's ticket count per block) on a CPU: tests/step_plan_check.cpp, a stand-alone program,
 is compiled against the header alone -- plain host C++17, no HIP header -- with AddressSanitizer and UBSan, and run.  No GPU,
 nothing loaded into Python."""
 import os
