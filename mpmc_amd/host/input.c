@@ -255,6 +255,7 @@ int do_command(system_t *system, char **token) {
     TEXT("pqr_input", pqr_input);
     TEXT("traj_input", traj_input);
     TEXT("pqr_output", pqr_output);
+    TEXT("pqr_restart", pqr_restart);
     TEXT("energy_output", energy_output);
     if (!strcasecmp(k, "basis1") || !strcasecmp(k, "basis2") || !strcasecmp(k, "basis3")) {
         const int r = k[5] - '1';
@@ -264,7 +265,7 @@ int do_command(system_t *system, char **token) {
     /* keywords of the reference that do not touch the NVT energy path are accepted and ignored */
     {
         static const char *ignored[] = {"free_volume",
-                                        "pqr_restart",        "traj_output",   "dipole_output",  "field_output",
+                                        "traj_output",   "dipole_output",  "field_output",
                                         "pop_histogram",      "pop_histogram_output", "histogram_output", NULL};
         for (int i = 0; ignored[i]; i++)
             if (!strcasecmp(k, ignored[i])) return 0;
@@ -665,8 +666,10 @@ void free_system(system_t *system) {
 int write_molecules(system_t *system, const char *filename) {
     FILE *fp = fopen(filename, "w");
     if (!fp) return -1;
-    int i = 1;
-    for (molecule_t *m = system->molecules; m; m = m->next)
+    int i = 1, j = 1;
+    /* molecules are numbered in list order (output.c:356-391), not by the id they were read with: an inserted molecule is a
+     * copy of its neighbour in the list, id included, and a reader starts a new molecule only where the id changes */
+    for (molecule_t *m = system->molecules; m; m = m->next, j++)
         for (atom_t *a = m->atoms; a; a = a->next, i++)
             /* omega (written only while polarvdw is on: every other run's file stays what it was) and gwp_alpha (not held
              * here: 0), then c6 c8 c10 c9, as output.c:436-447 writes them: a restart from this file keeps the dispersion
@@ -674,9 +677,46 @@ int write_molecules(system_t *system, const char *filename) {
             fprintf(fp, "ATOM  %5d %-4.45s %-3.3s %-1.1s %4d   %8.3f%8.3f%8.3f %8.5f %8.5f %8.5f %8.5f %8.5f %8.5f %8.5f %8.5f "
                         "%8.5f %8.5f %8.5f\n", i,
                     a->atomtype[0] ? a->atomtype : "X", m->moleculetype[0] ? m->moleculetype : "M",
-                    m->frozen ? "F" : "M", m->id, a->pos[0], a->pos[1], a->pos[2], a->mass, a->charge / E2REDUCED,
+                    m->frozen ? "F" : "M", j, a->pos[0], a->pos[1], a->pos[2], a->mass, a->charge / E2REDUCED,
                     a->polarizability, a->epsilon, a->sigma, system->polarvdw ? a->omega : 0.0, 0.0, a->c6, a->c8, a->c10,
                     a->c9);
+    fprintf(fp, "END\n");
+    fclose(fp);
+    return 0;
+}
+
+/* The restart file of the reference (output.c:315-564; mc.c:392 rewrites it at every corrtime, the driver writes the one
+ * that stays: the state after the last step).  Unlike write_molecules() above it numbers the molecules in list order -- an
+ * inserted molecule is a copy of the one behind it, id included, and read_molecules() starts a molecule where the id
+ * changes -- and writes what wrapall() makes of the coordinates (pairs.c:331-334 leaves them so after every energy()).
+ * The box follows as the reference's REMARK lines; its CRYST1 line and the eight BOX marker atoms, which a reader skips,
+ * are not written. */
+int write_restart(system_t *system, const char *filename) {
+    FILE *fp = fopen(filename, "w");
+    if (!fp) return -1;
+    const pbc_t *p = system->pbc;
+    int ext_output = 0; /* output.c:326-335: %8.3f unless a basis component needs more room */
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++)
+            if (p->basis[i][j] >= 100.0) ext_output = 1;
+    update_com(system->molecules);
+    wrapall(system->molecules, system->pbc);
+    int i = 1, j = 1;
+    for (molecule_t *m = system->molecules; m; m = m->next, j++)
+        for (atom_t *a = m->atoms; a; a = a->next, i++) {
+            const double *x = system->wrapall ? a->wrapped_pos : a->pos;
+            fprintf(fp, "ATOM  %5d %-4.45s %-3.3s %-1.1s %4d   ", i, a->atomtype[0] ? a->atomtype : "X",
+                    m->moleculetype[0] ? m->moleculetype : "M", a->frozen ? "F" : "M", j);
+            if (ext_output)
+                fprintf(fp, "%11.6f %11.6f %11.6f ", x[0], x[1], x[2]);
+            else
+                fprintf(fp, "%8.3f%8.3f%8.3f", x[0], x[1], x[2]);
+            fprintf(fp, " %8.5f %8.5f %8.5f %8.5f %8.5f %8.5f %8.5f %8.5f %8.5f %8.5f %8.5f\n", a->mass,
+                    a->charge / E2REDUCED, a->polarizability, a->epsilon, a->sigma, a->omega, 0.0, a->c6, a->c8, a->c10,
+                    a->c9);
+        }
+    for (int k = 0; k < 3; k++)
+        fprintf(fp, "REMARK BOX BASIS[%d] = %20.14f %20.14f %20.14f\n", k, p->basis[k][0], p->basis[k][1], p->basis[k][2]);
     fprintf(fp, "END\n");
     fclose(fp);
     return 0;

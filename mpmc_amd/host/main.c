@@ -49,6 +49,10 @@ int main(int argc, char **argv) {
                  (system->numsteps + 1) / sec);
         output(linebuf);
         if (system->pqr_output[0]) write_molecules(system, system->pqr_output);
+        if (!rc && system->pqr_restart[0] && write_restart(system, system->pqr_restart) < 0) {
+            error("MC: could not write restart state to disk\n"); /* mc.c:392-396 */
+            rc = -1;
+        }
     }
     free_system(system);
     return rc ? 1 : 0;

@@ -154,6 +154,7 @@ typedef struct _system {
     int iter_success; /* the reference's convergence-FAILURE flag */
     int natoms;
     char job_name[MAXLINE], pqr_input[MAXLINE], energy_output[MAXLINE], pqr_output[MAXLINE];
+    char pqr_restart[MAXLINE]; /* the state after the last step, as the reference's restart file has it (write_restart()) */
     pbc_t *pbc;
     molecule_t *molecules;
     observables_t *observables;
@@ -222,6 +223,9 @@ int wrapall(molecule_t *molecules, pbc_t *pbc);
 void output(const char *msg);
 void error(const char *msg);
 int write_molecules(system_t *system, const char *filename);
+/* `pqr_restart`: the configuration in the layout of the reference's restart file (output.c:315-564) -- molecules numbered
+ * in list order, coordinates wrapped molecule by molecule under `wrapall`, the box as REMARK BOX BASIS lines */
+int write_restart(system_t *system, const char *filename);
 
 #ifdef __cplusplus
 }

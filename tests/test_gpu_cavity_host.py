@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import cavity_reference as cr
+import reference_chain_compare as rcc
 from mpmc_amd import host, synth
 from oracle import oracle
 
@@ -156,22 +157,15 @@ def test_driver_walks_the_reference_programs_chain(tmp_path):
     """tests/golden/cavity_bias/reference_chain: a seeded 200-step `ensemble uvt` + `cavity_bias on` run (13 frozen framework
     atoms, 12 two-site sorbates, user_fugacities) and the energy-output lines the reference program wrote for it.  The
     driver on the same input must give the same N in every line -- every insertion, removal and coin fell as in the
-    reference, draw for draw -- and the energy columns to the printed digits, with the tolerance
-    tests/test_gpu_reference_inputs.py uses (the device adds its pair sums in another order)."""
+    reference, draw for draw -- and the energy columns to the printed digits, by the rules of
+    tests/reference_chain_compare.py (the device adds its pair sums in another order)."""
     src = os.path.join(ROOT, "tests", "golden", "cavity_bias", "reference_chain")
     for name in ("input", "in.pqr"):
         shutil.copy(os.path.join(src, name), tmp_path / name)
     r = subprocess.run([host.EXE_PATH, "input"], cwd=str(tmp_path), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    want = open(os.path.join(src, "reference_energy.dat")).read().splitlines()
-    got = open(tmp_path / "energy.dat").read().splitlines()
-    assert got[0] == want[0] and len(got) == len(want) == 42
-    worst = 0.0
-    for g, w in zip(got[1:], want[1:]):
-        g, w = g.split(), w.split()
-        assert g[0] == w[0] and g[8] == w[8], (g, w)  # step and N
-        for k in (1, 2, 3, 4, 5, 10):
-            worst = max(worst, abs(float(g[k]) - float(w[k])))
-    print("largest deviation from the reference's printed energies: %.3g K" % worst)
-    assert worst < 1.5e-6
+    want = rcc.energy_lines(os.path.join(src, "reference_energy.dat"))
+    assert len(want) == 42
+    worst = rcc.compare_energy(rcc.energy_lines(tmp_path / "energy.dat"), want)
+    print("largest deviation from the reference's printed energies: %s K" % worst)
     assert len({w.split()[8] for w in want[1:]}) > 5  # N moved both ways in the reference's run
