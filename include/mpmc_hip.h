@@ -544,6 +544,71 @@ int mpmc_hip_edit_molecules(mpmc_hip_ctx *ctx,
 int mpmc_hip_set_sweep_order(mpmc_hip_ctx *ctx, int count, const int *slots);
 int mpmc_hip_slot_count(mpmc_hip_ctx *ctx);
 
+/* Dimer scans: the energies of a NON-PERIODIC dimer of two rigid molecules for many placements at once -- the hot path of
+ * the reference's `ensemble surf` (src/mc/surface.c:16-76, :289-376) and what a force-field fitting loop asks for.  Per
+ * placement three numbers, as surface_energy() splits them:
+ *   es     sum q_i q_j / r over the inter-molecular pairs with both charges non-zero (coulombic_nopbc, coulombic.c:198-217);
+ *          0 under rd_only;
+ *   rd     Lennard-Jones as lj_nopbc has it (lj.c:279-317: no cutoff, no long-range correction, no Feynman-Hibbs term,
+ *          fabs(sigma)) under the mixing rule `mixing`, or under disp_expansion the PHAHST term (disp_expansion.c:105-153),
+ *          over the inter-molecular pairs pair_exclusions() leaves in (pairs.c:56-78);
+ *   polar  -1/2 sum mu . E_static (+ mu . ef_induced_change under polar_palmo) of the Thole system of ALL sites of both
+ *          molecules: A over every pair, intra-molecular ones included, without cutoff (tensor: damp_type, as
+ *          mpmc_hip_set_thole_model has it, without wolf_full); static field from the OTHER molecule's charges only
+ *          (thole_field_nopbc, thole_field.c:39-68); solver of thole_iterative.c: dipoles start at alpha E polar_gamma, then
+ *          Jacobi, polar_gs (order: molecule a's sites, then b's) or polar_gs_ranked (metric of pairs.c:337-359; the first
+ *          sweep in list order, the later ones in stable descending order of the metric), polar_max_iter sweeps, or with
+ *          polar_precision > 0 (polar_max_iter = 0) until no dipole component changed by more than polar_precision Debye;
+ *          the 128th sweep is not run: the dipoles fall back to alpha E and the placement is flagged.  Sites with
+ *          alpha = 0 are skipped.  0 when rd_only is set or no site is polarizable.
+ * Geometry of a placement (r, alpha1, beta1, gamma1, alpha2, beta2, gamma2), surface_dimer_geometry() (surface.c:383-433)
+ * applied to the PRISTINE body frames (coordinates minus the mass-weighted centre, pairs.c:364-385), without FMA
+ * contraction: molecule b's centre to (r, 0, 0), then each molecule is rotated about its own centre.  The rotation matrices
+ * are formed on the host with the host's cos / sin: molecule_rotate_euler() (surface.c:116-125), or with global_axis
+ * molecule_rotate_quaternion() (:177-193), kept as it is: the angles are divided by 57.2957795 although the scan hands it
+ * radians, and the third rotation is about x.
+ * OWNED DEVIATION: the reference rotates and un-rotates the live coordinates cumulatively; every placement here starts
+ * from the pristine frame.
+ * A placement's numbers depend on that placement alone -- not on its place in the batch, the batch size or the form of
+ * the call -- and the means of the grid form are summed in an order the grid sizes fix.
+ * Both entries use the context for its device, its stream and buffers of their own: they work on a context that has had
+ * no upload, and leave the resident configuration, its cached sums and the last result alone.  Not allowed between
+ * energy_begin() and energy_end().  Inputs are not screened for overlapping sites: r = 0 between two sites gives the
+ * reference's inf / NaN. */
+typedef struct mpmc_hip_dimer_params {
+    int rd_form;   /* 0 or MPMC_HIP_RD_LJ (the other forms are refused) */
+    int mixing;    /* MPMC_HIP_RD_MIX_* (Lennard-Jones) */
+    int disp_expansion, damp_dispersion, extrapolate_disp_coeffs, schmidt_mixing; /* as mpmc_hip_disp_params */
+    int rd_only;
+    int damp_type;          /* 0 off, 1 linear, 2 exponential */
+    double polar_damp;
+    int polar_max_iter;
+    double polar_precision;
+    int polar_gs, polar_gs_ranked, polar_palmo;
+    double polar_gamma;
+    int global_axis;        /* surf_global_axis */
+} mpmc_hip_dimer_params;
+void mpmc_hip_default_dimer_params(mpmc_hip_dimer_params *p);
+
+#define MPMC_HIP_DIMER_CHUNK 256                /* placements per workgroup: the unit of the grid form's fixed-order sum */
+#define MPMC_HIP_DIMER_NOT_CONVERGED 0x40000000 /* status bit: the 128-sweep give-up (dipoles = alpha E) */
+#define MPMC_HIP_DIMER_MAX_CONF (1 << 20)       /* placements per list call, and rotations per molecule of a grid call */
+
+/* List form.  a, b: 1 .. 16 sites each; x / y / z, charge, polarizability, epsilon, sigma, mass are read, c6 / c8 / c10
+ * under disp_expansion (atomic units; epsilon / sigma are then the exponent b and the range rho); frozen and c9 are not.
+ * conf: [nconf][7] = r, alpha1, beta1, gamma1, alpha2, beta2, gamma2.  es, rd, polar: [nconf].  status: [nconf], the
+ * sweeps taken, | MPMC_HIP_DIMER_NOT_CONVERGED.  mu: NULL, or [nconf][32][3], the dipoles, a's sites first then b's, the
+ * rest zeros. */
+int mpmc_hip_dimer_energies(mpmc_hip_ctx *ctx, const mpmc_hip_dimer_params *p, const mpmc_hip_molecule *a,
+                            const mpmc_hip_molecule *b, int nconf, const double *conf, double *es, double *rd,
+                            double *polar, int *status, double *mu);
+/* Grid form: one separation and six lists of angle values, angles[k][0 .. n[k]) for k = alpha1, beta1, gamma1, alpha2,
+ * beta2, gamma2; the placements are their Cartesian product, the last index fastest (surface.c:306-311).  Nothing per
+ * placement leaves the device.  means: es, rd, polar.  counts: [0] the placements, [1] those flagged not converged. */
+int mpmc_hip_dimer_grid_means(mpmc_hip_ctx *ctx, const mpmc_hip_dimer_params *p, const mpmc_hip_molecule *a,
+                              const mpmc_hip_molecule *b, double r, const int n[6], const double *const angles[6],
+                              double means[3], long long counts[2]);
+
 /* One full energy() evaluation on the device.
  * What has been computed when it returns: every energy term of the result, and the dipoles of all sweeps the energy
  * needs.  A fixed-count plain Jacobi solve -- polar_max_iter = n >= 2, polar_precision = 0, polar_gamma = 1, none of

@@ -51,6 +51,7 @@
 #include "kernels_coef.h"
 #include "kernels_volume.h"
 #include "kernels_cavity.h"
+#include "kernels_dimer.h"
 
 using namespace mpmc;
 
@@ -522,6 +523,16 @@ struct mpmc_hip_ctx {
     PinnedBuf<double> h_cav;             // pinned, mapped: the CavRecord
     double *h_cav_dev = nullptr;
     unsigned long long cav_seq = 0;
+    // ---- dimer scans (mpmc_hip_dimer_energies / _grid_means, engine_dimer.inc): buffers of their own, grown on demand;
+    // they share nothing with the resident configuration
+    DevBuf<unsigned char> d_dimer_mols;  // one DimerMols
+    DevBuf<double> d_dimer_rot[2];       // [K][9] rotation matrices per molecule
+    DevBuf<double> d_dimer_r;            // [nconf] separations (list form)
+    DevBuf<double> d_dimer_tab[2];       // [K][16][3] rotated sites per molecule
+    DevBuf<double> d_dimer_out;          // list form: es, rd, polar [3][nconf]; grid form: chunk sums [3][nchunk]
+    DevBuf<int> d_dimer_status;          // list form [nconf]; grid form [nchunk] non-converged placements
+    DevBuf<double> d_dimer_mu;           // list form, on request [nconf][32][3]
+    DevBuf<double> d_dimer_means;        // [3] + the non-converged count
     double lrc_cached = 0.0;
     DevBuf<KVec> d_kvec;
     int nk = 0;
@@ -3792,6 +3803,10 @@ extern "C" int mpmc_hip_download_cavity_grid(mpmc_hip_ctx *c, int *occupancy, do
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
+
+static_assert(kDimerChunk == MPMC_HIP_DIMER_CHUNK && kDimerNotConverged == MPMC_HIP_DIMER_NOT_CONVERGED,
+              "kernels_dimer.h and mpmc_hip.h disagree");
+#include "engine_dimer.inc"
 
 extern "C" int mpmc_hip_get_timings(mpmc_hip_ctx *c, mpmc_hip_timings *t) {
     if (!c || !t) return fail("MPMC_HIP: get_timings: null argument");

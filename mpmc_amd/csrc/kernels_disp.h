@@ -152,6 +152,52 @@ __global__ __launch_bounds__(64 * kDispWaves) void disp_tile_kernel(DevAtoms a, 
     block_sum_store<kDispWaves>(acc, red, out);
 }
 
+// The term of one pair that is in the sum, at its distance r: mixing, repulsion, damped dispersion -- the pair term of
+// disp_tile_kernel below, statement by statement, for the non-periodic sum of kernels_dimer.h (disp_expansion.c:118-140).
+// disp_tile_kernel keeps its own text: calling this function from it changed which products the compiler fuses into an
+// FMA, and with that the last bit of sums that are on record.
+__device__ __forceinline__ double disp_pair_energy(const DispParams &dp, double bi, double rhoi, double c6i, double c8i,
+                                                   double c10i, double bj, double rhoj, double c6j, double c8j, double c10j,
+                                                   double r) {
+    // mixing (pairs.c:147-149, :180-181): followed literally, 0 / 0 = NaN included
+    const double rho = 0.5 * (rhoi + rhoj);
+    const double b = dp.schmidt ? (bi + bj) * bi * bj / (bi * bi + bj * bj) : 2.0 * bi * bj / (bi + bj);
+    double c6, c8, c10;
+    disp_mix_coeffs(dp, c6i, c8i, c10i, c6j, c8j, c10j, c6, c8, c10);
+
+    double repulsion = 0.0;
+    if (b != 0.0 && rho != 0.0) repulsion = kDispRepulsion * exp(-b * (r - rho));
+
+    // one reciprocal for the three inverse powers
+    const double r2 = r * r;
+    const double ir2 = 1.0 / r2, ir4 = ir2 * ir2;
+    const double ir6 = ir4 * ir2, ir8 = ir4 * ir4, ir10 = ir8 * ir2;
+    double f6 = 1.0, f8 = 1.0, f10 = 1.0;
+    if (dp.damp) {
+        // tt_damping(n, x) = 1 - exp(-x) sum_{k <= n} x^k / k!, exactly 0 unless > 1e-9 (disp_expansion.c:164-177):
+        // one exp, the three partial sums from one running term
+        const double x = b * r;
+        const double ex = exp(-x);
+        double term = x, sum = 1.0 + x;
+        term *= x * (1.0 / 2.0); sum += term;
+        term *= x * (1.0 / 3.0); sum += term;
+        term *= x * (1.0 / 4.0); sum += term;
+        term *= x * (1.0 / 5.0); sum += term;
+        term *= x * (1.0 / 6.0); sum += term;
+        f6 = 1.0 - ex * sum;
+        term *= x * (1.0 / 7.0); sum += term;
+        term *= x * (1.0 / 8.0); sum += term;
+        f8 = 1.0 - ex * sum;
+        term *= x * (1.0 / 9.0); sum += term;
+        term *= x * (1.0 / 10.0); sum += term;
+        f10 = 1.0 - ex * sum;
+        f6 = (f6 > 0.000000001) ? f6 : 0.0;  // (NaN compares false: 0, as in the reference)
+        f8 = (f8 > 0.000000001) ? f8 : 0.0;
+        f10 = (f10 > 0.000000001) ? f10 : 0.0;
+    }
+    return -f6 * c6 * ir6 - f8 * c8 * ir8 - f10 * c10 * ir10 + repulsion;
+}
+
 // Long-range correction (disp_expansion.c:5-38, :50-53, :92-100): parameters, the cutoff, the volume and which atoms
 // exist, no coordinate.  A full pass at upload / set_dispersion and at box change; after mpmc_hip_edit_molecules only the
 // tiles of the edited atoms' blocks are redone, like lj_lrc_kernel's.  Grids: owned_tile(); tile partials [I][J], summed by

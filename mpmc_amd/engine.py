@@ -23,7 +23,8 @@ EXPORTS = [
     "mpmc_hip_download_cavity_grid",
     "mpmc_hip_set_exact_polar", "mpmc_hip_get_polarizability_tensor", "mpmc_hip_set_thole_model",
     "mpmc_hip_update_atoms", "mpmc_hip_insert_molecule", "mpmc_hip_remove_molecule", "mpmc_hip_edit_molecules",
-    "mpmc_hip_slot_count", "mpmc_hip_set_sweep_order", "mpmc_hip_energy", "mpmc_hip_energy_begin", "mpmc_hip_energy_end",
+    "mpmc_hip_slot_count", "mpmc_hip_set_sweep_order",
+    "mpmc_hip_default_dimer_params", "mpmc_hip_dimer_energies", "mpmc_hip_dimer_grid_means", "mpmc_hip_energy", "mpmc_hip_energy_begin", "mpmc_hip_energy_end",
     "mpmc_hip_download_dipoles",
     "mpmc_hip_download_amatrix", "mpmc_hip_download_ranking", "mpmc_hip_get_timings",
     "mpmc_hip_comm_unique_id", "mpmc_hip_comm_create", "mpmc_hip_comm_size", "mpmc_hip_comm_rank",
@@ -139,6 +140,31 @@ class Molecule(C.Structure):
                                   "c6", "c8", "c10", "c9")]
 
 
+class DimerParams(C.Structure):
+    """mpmc_hip_dimer_params: what a dimer scan computes (mpmc_hip_dimer_energies / _grid_means)."""
+    _fields_ = [
+        ("rd_form", C.c_int),
+        ("mixing", C.c_int),
+        ("disp_expansion", C.c_int),
+        ("damp_dispersion", C.c_int),
+        ("extrapolate_disp_coeffs", C.c_int),
+        ("schmidt_mixing", C.c_int),
+        ("rd_only", C.c_int),
+        ("damp_type", C.c_int),
+        ("polar_damp", C.c_double),
+        ("polar_max_iter", C.c_int),
+        ("polar_precision", C.c_double),
+        ("polar_gs", C.c_int),
+        ("polar_gs_ranked", C.c_int),
+        ("polar_palmo", C.c_int),
+        ("polar_gamma", C.c_double),
+        ("global_axis", C.c_int),
+    ]
+
+
+DIMER_CHUNK = 256  # MPMC_HIP_DIMER_CHUNK: placements per workgroup, the unit of the grid form's fixed-order sum
+DIMER_NOT_CONVERGED = 0x40000000  # MPMC_HIP_DIMER_NOT_CONVERGED
+DIMER_SITES = 32  # rows per placement of the dipoles dimer_energies(mu=True) returns
 THOLE_DAMPINGS = {"off": 0, "none": 0, "linear": 1, "exponential": 2}  # the reference's DAMPING_* values
 RD_FORMS = {"off": 0, "lj": 1, "sg": 2, "dreiding": 3, "lj_buffered_14_7": 4}  # MPMC_HIP_RD_*
 RD_MIXINGS = {"lb": 0, "waldmanhagler": 1, "halgren_mixing": 2, "c6_mixing": 3}  # MPMC_HIP_RD_MIX_*
@@ -211,6 +237,12 @@ def load():
     lib.mpmc_hip_edit_molecules.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.POINTER(Molecule), vp]
     lib.mpmc_hip_slot_count.argtypes = [vp]
     lib.mpmc_hip_set_sweep_order.argtypes = [vp, C.c_int, vp]
+    lib.mpmc_hip_default_dimer_params.argtypes = [C.POINTER(DimerParams)]
+    lib.mpmc_hip_default_dimer_params.restype = None
+    lib.mpmc_hip_dimer_energies.argtypes = [vp, C.POINTER(DimerParams), C.POINTER(Molecule), C.POINTER(Molecule), C.c_int,
+                                            vp, vp, vp, vp, vp, vp]
+    lib.mpmc_hip_dimer_grid_means.argtypes = [vp, C.POINTER(DimerParams), C.POINTER(Molecule), C.POINTER(Molecule),
+                                              C.c_double, ip, C.POINTER(vp), dp, C.POINTER(C.c_longlong)]
     lib.mpmc_hip_energy.argtypes = [vp, C.POINTER(Result)]
     lib.mpmc_hip_energy_begin.argtypes = [vp]
     lib.mpmc_hip_energy_end.argtypes = [vp, C.POINTER(Result)]
@@ -273,6 +305,50 @@ def rd_form_of(params):
         raise ValueError("INPUT: more than one mixing rule specified")
     form = next((f for f in ("sg", "dreiding", "lj_buffered_14_7") if params.get(f)), "lj" if mix else "off")
     return form, (mix[0] if mix else "lb")
+
+
+def make_dimer_params(**flags):
+    """mpmc_hip_dimer_params from reference keywords: waldmanhagler / halgren_mixing / c6_mixing, the PHAHST switches,
+    rd_only, polar_damp_type ("exponential" | "linear" | "off" | "none"), polar_damp, polar_max_iter, polar_precision,
+    polar_gs, polar_gs_ranked, polar_palmo, polar_gamma, and surf_global_axis (or global_axis)."""
+    p = DimerParams()
+    load().mpmc_hip_default_dimer_params(C.byref(p))
+    flags = dict(flags)
+    form, mix = rd_form_of(flags)
+    if form not in ("off", "lj"):
+        raise ValueError("a dimer scan has Lennard-Jones or disp_expansion, not %s" % form)
+    p.rd_form, p.mixing = RD_FORMS["lj"], RD_MIXINGS[mix]
+    for k in ("waldmanhagler", "halgren_mixing", "c6_mixing"):
+        flags.pop(k, None)
+    damping = flags.pop("polar_damp_type", "exponential")
+    p.damp_type = THOLE_DAMPINGS[damping.lower()] if isinstance(damping, str) else int(damping)
+    p.global_axis = int(bool(flags.pop("surf_global_axis", flags.pop("global_axis", 0))))
+    flags.pop("polarization", None)  # (a site's polarizability says whether the Thole system is solved)
+    for k, v in flags.items():
+        if k not in dict(DimerParams._fields_):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _dimer_molecule(d, keep):
+    """mpmc_hip_molecule of a dict with pos [k, 3], charge, alpha, epsilon, sigma, mass and optionally c6 / c8 / c10."""
+    m = Molecule()
+    pos = np.ascontiguousarray(d["pos"], dtype=np.float64).reshape(-1, 3)
+    m.count, m.frozen = pos.shape[0], 0
+    for k, name in enumerate("xyz"):
+        keep.append(np.ascontiguousarray(pos[:, k]))
+        setattr(m, name, keep[-1].ctypes.data)
+    for field, key in (("charge", "charge"), ("polarizability", "alpha"), ("epsilon", "epsilon"), ("sigma", "sigma"),
+                       ("mass", "mass"), ("c6", "c6"), ("c8", "c8"), ("c10", "c10")):
+        if d.get(key) is None:
+            continue
+        a = np.ascontiguousarray(d[key], dtype=np.float64)
+        if a.shape != (pos.shape[0],):
+            raise ValueError("dimer: %s must have one entry per site of the molecule" % key)
+        keep.append(a)
+        setattr(m, field, a.ctypes.data)
+    return m
 
 
 class Engine:
@@ -577,6 +653,46 @@ class Engine:
         """Gauss-Seidel modes after insert / remove: device slots of the polarizable atoms in the caller's atom order."""
         a = np.ascontiguousarray(slots, dtype=np.int32)
         _chk(self.lib.mpmc_hip_set_sweep_order(self.ctx, len(a), a.ctypes.data))
+
+    def dimer_energies(self, a, b, conf, mu=False, **flags):
+        """Energies of the non-periodic dimer a + b at the placements conf [n, 7] = (r, alpha1, beta1, gamma1, alpha2, beta2,
+        gamma2) (mpmc_hip_dimer_energies).  a, b: dicts with pos [k, 3], charge, alpha, epsilon, sigma, mass and, under
+        disp_expansion, c6 / c8 / c10; flags: make_dimer_params().  Returns dict(es, rd, polar [n], iterations [n],
+        not_converged [n]) and with mu=True the dipoles mu [n, 32, 3] (a's sites first, then b's)."""
+        p = flags.pop("_struct", None) or make_dimer_params(**flags)
+        conf = np.ascontiguousarray(conf, dtype=np.float64).reshape(-1, 7)
+        n = conf.shape[0]
+        keep = []
+        ma, mb = _dimer_molecule(a, keep), _dimer_molecule(b, keep)
+        out = {k: np.zeros(n) for k in ("es", "rd", "polar")}
+        status = np.zeros(n, dtype=np.int32)
+        dip = np.zeros((n, DIMER_SITES, 3)) if mu else None
+        _chk(self.lib.mpmc_hip_dimer_energies(self.ctx, C.byref(p), C.byref(ma), C.byref(mb), n, conf.ctypes.data,
+                                              out["es"].ctypes.data, out["rd"].ctypes.data, out["polar"].ctypes.data,
+                                              status.ctypes.data, dip.ctypes.data if mu else None))
+        out["iterations"] = status & ~DIMER_NOT_CONVERGED
+        out["not_converged"] = (status & DIMER_NOT_CONVERGED) != 0
+        if mu:
+            out["mu"] = dip
+        return out
+
+    def dimer_grid_means(self, a, b, r, angles, **flags):
+        """Means of es, rd and polar over the Cartesian product of six angle lists (alpha1, beta1, gamma1, alpha2, beta2,
+        gamma2; the last fastest) at separation r (mpmc_hip_dimer_grid_means).  Returns dict(es, rd, polar, count,
+        not_converged)."""
+        p = flags.pop("_struct", None) or make_dimer_params(**flags)
+        lists = [np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in angles]
+        if len(lists) != 6:
+            raise ValueError("dimer_grid_means: six angle lists")
+        keep = []
+        ma, mb = _dimer_molecule(a, keep), _dimer_molecule(b, keep)
+        n = (C.c_int * 6)(*[len(x) for x in lists])
+        ptrs = (C.c_void_p * 6)(*[x.ctypes.data for x in lists])
+        means = (C.c_double * 3)()
+        counts = (C.c_longlong * 2)()
+        _chk(self.lib.mpmc_hip_dimer_grid_means(self.ctx, C.byref(p), C.byref(ma), C.byref(mb), float(r), n, ptrs, means,
+                                                counts))
+        return dict(es=means[0], rd=means[1], polar=means[2], count=int(counts[0]), not_converged=int(counts[1]))
 
     def energy(self):
         r = Result()

@@ -105,11 +105,43 @@ int do_command(system_t *system, char **token) {
             system->ensemble = ENSEMBLE_TE;
         else if (!strcasecmp(v, "replay"))
             system->ensemble = ENSEMBLE_REPLAY;
-        else {
-            error("INPUT: only `ensemble nvt`, `uvt`, `npt`, `total_energy` and `replay` are implemented by this host "
-                  "layer\n");
+        else if (!strcasecmp(v, "surf"))
+            system->ensemble = ENSEMBLE_SURF;
+        else if (!strcasecmp(v, "surf_fit")) {
+            error("INPUT: ensemble surf_fit is not implemented by this host layer\n");
+            return 1;
+        } else if (!strcasecmp(v, "nve")) {
+            error("INPUT: ensemble nve is not implemented by this host layer\n");
+            return 1;
+        } else {
+            error("INPUT: only `ensemble nvt`, `uvt`, `npt`, `total_energy`, `replay` and `surf` are implemented by this "
+                  "host layer\n");
             return 1;
         }
+        return 0;
+    }
+    /* ensemble surf, input.c:170-335 */
+    REAL("surf_min", surf_min);
+    REAL("surf_max", surf_max);
+    REAL("surf_inc", surf_inc);
+    REAL("surf_ang", surf_ang);
+    FLAG("surf_preserve", surf_preserve);
+    FLAG("surf_decomp", surf_decomp);
+    FLAG("surf_global_axis", surf_global_axis_on);
+    FLAG("surf_virial", surf_virial);          /* refused by name (check_system) */
+    INT("surf_print_level", surf_print_level); /* likewise */
+    if (!strcasecmp(k, "surf_output")) {       /* likewise */
+        system->surf_output_on = 1;
+        return 0;
+    }
+    if (!strcasecmp(k, "surf_preserve_rotation")) {
+        if (system->surf_preserve_rotation_on) {
+            error("INPUT: surf_preserve_rotationalready set.\n");
+            return 1;
+        }
+        system->surf_preserve_rotation_on = 1;
+        for (int i = 0; i < 6; i++)
+            if (safe_atof(token[1 + i], &system->surf_preserve_rotation[i])) return 1;
         return 0;
     }
     if (!strcasecmp(k, "preset_seeds")) {
@@ -436,6 +468,47 @@ int check_cavity_bias(system_t *system) {
     return 0;
 }
 
+/* ensemble_surf_options(), check_input.c:88-132, and what this layer's surface() does not run */
+static int check_surf(system_t *system) {
+    char linebuf[MAXLINE];
+    if (!system->surf_min) system->surf_min = 0.5; /* SURF_MIN, SURF_MAX, SURF_INC: defines.h:144-146 */
+    if (!system->surf_max) system->surf_max = 25.0;
+    if (!system->surf_inc) system->surf_inc = 0.25;
+    if (system->surf_max < system->surf_min) {
+        error("INPUT: surf_max is greater than surf_min\n");
+        return -1;
+    }
+    snprintf(linebuf, MAXLINE, "INPUT: minimum surface coordinate is %.3f\n", system->surf_min);
+    output(linebuf);
+    snprintf(linebuf, MAXLINE, "INPUT: maximum surface coordinate is %.3f\n", system->surf_max);
+    output(linebuf);
+    if (system->surf_inc <= 0.0) {
+        error("INPUT: surf_inc is less than or equal to 0\n");
+        return -1;
+    }
+    snprintf(linebuf, MAXLINE, "INPUT: incremental surface displacement coordinate is %.3f\n", system->surf_inc);
+    output(linebuf);
+    if (!system->surf_preserve && !system->surf_virial) {
+        if (system->surf_ang <= 0.0) {
+            error("INPUT: surf_ang is less than or equal to 0\n");
+            return -1;
+        }
+        snprintf(linebuf, MAXLINE, "INPUT: incremental surface angle coordinate is %.3f\n", system->surf_ang);
+        output(linebuf);
+    }
+    if (system->read_pqr_box_on) {
+        error("INPUT: read_pqr_box is not compatible with surf.\n");
+        return -1;
+    }
+    const char *why = surface_refused(system);
+    if (why) {
+        snprintf(linebuf, MAXLINE, "INPUT: ensemble surf: %s\n", why);
+        error(linebuf);
+        return -1;
+    }
+    return 0;
+}
+
 /* the checks of reference src/io/check_input.c that concern this path */
 static int check_system(system_t *system) {
     char linebuf[MAXLINE];
@@ -444,10 +517,11 @@ static int check_system(system_t *system) {
         return -1;
     }
     if (system->ensemble != ENSEMBLE_NVT && system->ensemble != ENSEMBLE_TE && system->ensemble != ENSEMBLE_UVT &&
-        system->ensemble != ENSEMBLE_NPT && system->ensemble != ENSEMBLE_REPLAY) {
-        error("INPUT: ensemble must be nvt, uvt, npt, total_energy or replay\n");
+        system->ensemble != ENSEMBLE_NPT && system->ensemble != ENSEMBLE_REPLAY && system->ensemble != ENSEMBLE_SURF) {
+        error("INPUT: ensemble must be nvt, uvt, npt, total_energy, replay or surf\n");
         return -1;
     }
+    if (system->ensemble == ENSEMBLE_SURF && check_surf(system)) return -1;
     if (system->ensemble == ENSEMBLE_REPLAY && !system->traj_input[0]) {
         error("INPUT: ensemble replay needs traj_input\n");
         return -1;
@@ -530,6 +604,7 @@ static int check_system(system_t *system) {
             return -1;
         }
     }
+    if (system->ensemble == ENSEMBLE_SURF) return 0; /* no basis is required: a zero volume gives cutoff = MAXVALUE (pbc.c:19) */
     if ((system->pbc->volume <= 0.0) || (system->pbc->cutoff <= 0.0)) {
         error("INPUT: invalid simulation box dimensions.\n");
         return -1;

@@ -1,6 +1,6 @@
 /* main.c -- `mpmc_hip <config>`: the reference's entry point (src/main/main.c:34-304) reduced to the
- * modes this layer supports: the Monte Carlo ensembles (mc()), `ensemble total_energy` (single point) and
- * `ensemble replay` (replay_trajectory()). */
+ * modes this layer supports: the Monte Carlo ensembles (mc()), `ensemble total_energy` (single point),
+ * `ensemble replay` (replay_trajectory()) and `ensemble surf` (surface()). */
 #include <stdlib.h>
 #include <string.h>
 #include <sys/time.h>
@@ -39,6 +39,8 @@ int main(int argc, char **argv) {
         output(linebuf);
     } else if (system->ensemble == ENSEMBLE_REPLAY) {
         rc = replay_trajectory(system);
+    } else if (system->ensemble == ENSEMBLE_SURF) {
+        rc = surface(system, device);
     } else {
         struct timeval t0, t1;
         gettimeofday(&t0, NULL);

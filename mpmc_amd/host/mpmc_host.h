@@ -151,6 +151,12 @@ typedef struct _system {
      * read so that replay can refuse it by name */
     int read_pqr_box_on, calc_pressure;
     char traj_input[MAXLINE];
+    /* ensemble surf (structs.h; check_input.c:88-132, surface.c): the scan and its switches.  surf_virial, surf_output and
+     * surf_print_level are read so that check_system() can refuse them by name, like ensemble surf_fit and nve */
+    double surf_min, surf_max, surf_inc, surf_ang;
+    int surf_preserve, surf_decomp, surf_global_axis_on, surf_virial, surf_print_level, surf_output_on;
+    int surf_preserve_rotation_on;     /* the keyword was given: its six angles (radians) follow */
+    double surf_preserve_rotation[6];  /* alpha1 beta1 gamma1 alpha2 beta2 gamma2 */
     int iter_success; /* the reference's convergence-FAILURE flag */
     int natoms;
     char job_name[MAXLINE], pqr_input[MAXLINE], energy_output[MAXLINE], pqr_output[MAXLINE];
@@ -197,6 +203,12 @@ int mc(system_t *system);
  * read_frame(): the next frame's molecules (and box, under read_pqr_box) into `system`, whose old molecules it frees;
  * 0 = a frame was read, 1 = end of the trajectory, -1 = error. */
 int replay_trajectory(system_t *system);
+/* ensemble surf (reference src/mc/surface.c:227-380): the dimer curve on device `device`, the reference's lines on stdout.
+ * surface_refused(): NULL, or why this layer does not run the input (each reason names its keyword).
+ * surface_loop_count(): how many values `for (x = 0; x <= top; x += step)` visits, in double, as the reference loops. */
+int surface(system_t *system, int device);
+const char *surface_refused(const system_t *system);
+int surface_loop_count(double top, double step);
 int read_frame(FILE *fp, system_t *system);
 void write_observables(FILE *fp, system_t *system, observables_t *o, double core_temp);
 void checkpoint(system_t *system);
