@@ -212,7 +212,10 @@ void mpmc_hip_destroy(mpmc_hip_ctx *ctx);
  *   "step_graph"          (default 0): replay a steady-state MC step as a HIP graph (bit-identical; measured
  *                          slower than direct launches on ROCm 7.2);
  *   "cavity_incremental"  (default 1): 0 = mpmc_hip_cavity_update() answers 1 to every non-empty edit (A/B; same bits).
- *                          A knob of the cavity grid, kept with the grid's state: it touches nothing of an evaluation. */
+ *                          A knob of the cavity grid, kept with the grid's state: it touches nothing of an evaluation;
+ *   "trial_batched"       (default 1): 0 = mpmc_hip_trial_energies() takes its serial path in every mode (A/B, and the
+ *                          batched path's check).  A knob of that entry, like the one above: it touches nothing of an
+ *                          evaluation, and setting it does not count as a change since the last energy(). */
 int mpmc_hip_set_option(mpmc_hip_ctx *ctx, const char *name, int value);
 
 void mpmc_hip_default_params(mpmc_hip_params *p);
@@ -608,6 +611,41 @@ int mpmc_hip_dimer_energies(mpmc_hip_ctx *ctx, const mpmc_hip_dimer_params *p, c
 int mpmc_hip_dimer_grid_means(mpmc_hip_ctx *ctx, const mpmc_hip_dimer_params *p, const mpmc_hip_molecule *a,
                               const mpmc_hip_molecule *b, double r, const int n[6], const double *const angles[6],
                               double means[3], long long counts[2]);
+
+/* Trial placements: the total energy of the resident configuration with ONE molecule at each of ntrial placements, the
+ * configuration itself left untouched -- what the reference's quantum_rotation scan takes 2 x 256 full energy() calls per
+ * molecule for (rotational_eigenspectrum.c:219-266, rotational_potential.c:211-253), and what Widom insertion, multiple-try
+ * and configurational-bias moves would ask for.
+ *   first_slot, count   the molecule: one whole valid, non-frozen molecule of 1 .. 16 sites, by its slot range;
+ *   xyz                 [ntrial][count][3], the sites of each placement in slot order.  The placements are RIGID re-placements
+ *                       of the molecule (rotations, translations): its intra-molecular terms are taken from the resident result;
+ *   energy              [ntrial]: what energy() would return as mpmc_hip_result.energy after update_atoms(first_slot, count,
+ *                       placement t);
+ *   terms               NULL, or [ntrial][3]: rd, es_real and es_recip of placement t as the batched path forms them -- the
+ *                       molecule's Lennard-Jones (+ Feynman-Hibbs) and real-space Ewald / Wolf sums with every other atom, and
+ *                       (4 pi / V) sum_k w_k |S_rest(k) + s_t(k)|^2.  With (rd_0, es_0, recip_0) the terms of the molecule's
+ *                       CURRENT placement (pass its coordinates as a placement to read them) and E the energy of the last
+ *                       energy(),   energy[t] == (E - ((rd_0 + es_0) + recip_0)) + ((rd_t + es_t) + recip_t)   in fp64, one
+ *                       rounding per operation.
+ * The call needs a completed energy() on the current configuration and leaves the resident configuration, every cached sum,
+ * the last result record and any pending deferred sweeps as they were.  Refused by name, before anything changes: a call
+ * between energy_begin() and energy_end(); ntrial < 1; an upload, move (update_atoms), edit (insert / remove / edit_molecules),
+ * box change (set_box / scale_box), set_params, mode setter or evaluation option since the last completed energy(); a slot
+ * range that is not one whole valid, non-frozen molecule of 1 .. 16 sites.
+ * Two paths, the same numbers to 1e-12 of the sum of the magnitudes of the energy's terms:
+ *   batched  the standard pair path without polarization (Lennard-Jones with Lorentz-Berthelot mixing, feynman_hibbs, Ewald /
+ *            Wolf / rd_only, rd_lrc): at most 4 launches per call whatever ntrial (kernels_trial.h).
+ *            A placement's bits depend on the molecule, the placement and the resident configuration -- not on ntrial or on
+ *            the placement's position in the batch;
+ *   serial   with polarization, disp_expansion, set_rd_form, rd_crystal, axilrod_teller, polarvdw or the exact dipoles, and
+ *            whenever option "trial_batched" (default 1; mpmc_hip_set_option; setting it is no change of the evaluation) is 0:
+ *            update_atoms() + energy() per placement, then the original coordinates and one more energy().  energy[t] is,
+ *            bit for bit, what that public sequence returns, and the context afterwards gives the bits of one that never made
+ *            the call.  terms must be NULL on this path (refused by name).
+ * mpmc_hip_trial_call_count(): calls so far that passed their checks. */
+int mpmc_hip_trial_energies(mpmc_hip_ctx *ctx, int first_slot, int count, int ntrial, const double *xyz, double *energy,
+                            double *terms);
+long long mpmc_hip_trial_call_count(mpmc_hip_ctx *ctx);
 
 /* One full energy() evaluation on the device.
  * What has been computed when it returns: every energy term of the result, and the dipoles of all sweeps the energy

@@ -186,6 +186,16 @@ void hook_cavity_update_grid(system_t *system) {
 void hook_make_move_cavity_point(system_t *system, int random_index, double com[3]) {
     if (system->hip) energy_hip_cavity_point(system, random_index, com);
 }
+/* src/quantum_rotation/rotational_eigenspectrum.c, quantum_rotational_grid() (:219-266) under `hip on`: the 256 grid
+ * energies of a molecule in ONE call instead of an energy_no_observables() + energy() pair per grid point inside
+ * rotational_potential().  xyz: the placements align_molecule() + rotate_spherical() give, [p * 16 + t][sites][3], formed
+ * from copies of the molecule's coordinates; energies: [p * 16 + t].  The molecule and the observables stay untouched;
+ * the caller multiplies with sin(theta) into quantum_rotational_potential_grid[t][p] as before. */
+int hook_quantum_rotational_grid(system_t *system, molecule_t *molecule, const double *xyz, double *energies) {
+    if (system->hip)
+        return energy_hip_trial_energies(system, molecule, QUANTUM_ROTATION_GRID * QUANTUM_ROTATION_GRID, xyz, energies);
+    return 1; /* ... unchanged CPU path ... */
+}
 /* restore(), default branch (:778-797), where the backup is linked into the list in place of the altered node: */
 void hook_restore_displace(system_t *system) {
     energy_hip_note_moved(system, system->checkpoint->molecule_backup, system->checkpoint->molecule_altered);

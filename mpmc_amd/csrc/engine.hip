@@ -52,6 +52,7 @@
 #include "kernels_volume.h"
 #include "kernels_cavity.h"
 #include "kernels_dimer.h"
+#include "kernels_trial.h"
 
 using namespace mpmc;
 
@@ -533,6 +534,18 @@ struct mpmc_hip_ctx {
     DevBuf<int> d_dimer_status;          // list form [nconf]; grid form [nchunk] non-converged placements
     DevBuf<double> d_dimer_mu;           // list form, on request [nconf][32][3]
     DevBuf<double> d_dimer_means;        // [3] + the non-converged count
+    // ---- trial placements (mpmc_hip_trial_energies, engine_trial.inc): what the last completed energy() returned and
+    // under which config_rev, and buffers of the batched path's own, grown on demand
+    bool result_valid = false;           // an energy_end() has completed since the last energy_begin()
+    unsigned long long result_rev = 0;   // config_rev at that moment
+    mpmc_hip_result last_result;
+    unsigned long long trial_calls = 0;  // calls that passed their checks
+    int trial_batched = 1;               // option "trial_batched": 0 = the serial path in every mode (A/B; the batched path's check)
+    DevBuf<double> d_trial_xyz;          // [ntrial][count][3]
+    DevBuf<double> d_trial_pair;         // [ntrial + 1][2] rd, es_real of the molecule; row 0 = the current placement
+    DevBuf<double> d_trial_chunk;        // [ntrial + 1][ceil(nk / 64)]
+    DevBuf<double2> d_trial_srest;       // [nk] the structure factor without the molecule
+    DevBuf<double> d_trial_out;          // [ntrial] energies, then [ntrial][3] terms
     double lrc_cached = 0.0;
     DevBuf<KVec> d_kvec;
     int nk = 0;
@@ -882,6 +895,12 @@ extern "C" int mpmc_hip_set_option(mpmc_hip_ctx *c, const char *name, int value)
     // change completes pending sweeps and retires a captured step; this one touches neither.
     if (!strcmp(name, "cavity_incremental")) {
         c->cav_incremental = value;
+        return 0;
+    }
+    // Likewise the path of mpmc_hip_trial_energies(): no evaluation reads it, so setting it completes no pending sweep and
+    // leaves config_rev -- and with it the "completed energy() on the current configuration" the entry asks for -- alone.
+    if (!strcmp(name, "trial_batched")) {
+        c->trial_batched = value;
         return 0;
     }
     if (complete_pending_sweep(c)) return -1;  // (launched under the options of the call it belongs to)
@@ -3309,6 +3328,7 @@ static int refuse_unsupported(mpmc_hip_ctx *c) {
 extern "C" int mpmc_hip_energy_begin(mpmc_hip_ctx *c) {
     if (!c) return fail("MPMC_HIP: energy: null argument");
     if (c->in_flight) return fail("MPMC_HIP: energy_begin: the previous evaluation has not been collected");
+    c->result_valid = false;
     if (!c->have_atoms) return fail("MPMC_HIP: energy: no configuration uploaded");
     if (!c->have_box) return fail("MPMC_HIP: energy: no box set");
     if (c->order_stale && gs_order_mode(c))
@@ -3521,6 +3541,9 @@ extern "C" int mpmc_hip_energy_end(mpmc_hip_ctx *c, mpmc_hip_result *out) {
     c->timed = timed_call;
     c->stage_used = 0;
     assemble_result(c, iter_success, out);
+    c->last_result = *out;
+    c->result_rev = c->config_rev;
+    c->result_valid = true;
     return 0;
 }
 
@@ -3807,6 +3830,7 @@ extern "C" int mpmc_hip_download_cavity_grid(mpmc_hip_ctx *c, int *occupancy, do
 static_assert(kDimerChunk == MPMC_HIP_DIMER_CHUNK && kDimerNotConverged == MPMC_HIP_DIMER_NOT_CONVERGED,
               "kernels_dimer.h and mpmc_hip.h disagree");
 #include "engine_dimer.inc"
+#include "engine_trial.inc"
 
 extern "C" int mpmc_hip_get_timings(mpmc_hip_ctx *c, mpmc_hip_timings *t) {
     if (!c || !t) return fail("MPMC_HIP: get_timings: null argument");

@@ -24,7 +24,8 @@ EXPORTS = [
     "mpmc_hip_set_exact_polar", "mpmc_hip_get_polarizability_tensor", "mpmc_hip_set_thole_model",
     "mpmc_hip_update_atoms", "mpmc_hip_insert_molecule", "mpmc_hip_remove_molecule", "mpmc_hip_edit_molecules",
     "mpmc_hip_slot_count", "mpmc_hip_set_sweep_order",
-    "mpmc_hip_default_dimer_params", "mpmc_hip_dimer_energies", "mpmc_hip_dimer_grid_means", "mpmc_hip_energy", "mpmc_hip_energy_begin", "mpmc_hip_energy_end",
+    "mpmc_hip_default_dimer_params", "mpmc_hip_dimer_energies", "mpmc_hip_dimer_grid_means",
+    "mpmc_hip_trial_energies", "mpmc_hip_trial_call_count", "mpmc_hip_energy", "mpmc_hip_energy_begin", "mpmc_hip_energy_end",
     "mpmc_hip_download_dipoles",
     "mpmc_hip_download_amatrix", "mpmc_hip_download_ranking", "mpmc_hip_get_timings",
     "mpmc_hip_comm_unique_id", "mpmc_hip_comm_create", "mpmc_hip_comm_size", "mpmc_hip_comm_rank",
@@ -243,6 +244,9 @@ def load():
                                             vp, vp, vp, vp, vp, vp]
     lib.mpmc_hip_dimer_grid_means.argtypes = [vp, C.POINTER(DimerParams), C.POINTER(Molecule), C.POINTER(Molecule),
                                               C.c_double, ip, C.POINTER(vp), dp, C.POINTER(C.c_longlong)]
+    lib.mpmc_hip_trial_energies.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.mpmc_hip_trial_call_count.argtypes = [vp]
+    lib.mpmc_hip_trial_call_count.restype = C.c_longlong
     lib.mpmc_hip_energy.argtypes = [vp, C.POINTER(Result)]
     lib.mpmc_hip_energy_begin.argtypes = [vp]
     lib.mpmc_hip_energy_end.argtypes = [vp, C.POINTER(Result)]
@@ -693,6 +697,25 @@ class Engine:
         _chk(self.lib.mpmc_hip_dimer_grid_means(self.ctx, C.byref(p), C.byref(ma), C.byref(mb), float(r), n, ptrs, means,
                                                 counts))
         return dict(es=means[0], rd=means[1], polar=means[2], count=int(counts[0]), not_converged=int(counts[1]))
+
+    def trial_energies(self, first, xyz, terms=False):
+        """Total energies of the resident configuration with the molecule in slots [first, first + k) at each of the
+        placements xyz [ntrial, k, 3] (mpmc_hip_trial_energies); the configuration is left as it is.  Needs a completed
+        energy() on the current configuration.  Returns energy [ntrial]; with terms=True (batched path only) the pair
+        (energy, terms [ntrial, 3]) with the molecule's rd, es_real and es_recip per placement."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        if xyz.ndim != 3 or xyz.shape[2] != 3:
+            raise ValueError("trial_energies: xyz must be [ntrial, sites, 3]")
+        nt, k = xyz.shape[0], xyz.shape[1]
+        e = np.zeros(nt)
+        tr = np.zeros((nt, 3)) if terms else None
+        _chk(self.lib.mpmc_hip_trial_energies(self.ctx, int(first), k, nt, xyz.ctypes.data, e.ctypes.data,
+                                              tr.ctypes.data if terms else None))
+        return (e, tr) if terms else e
+
+    def trial_call_count(self):
+        """mpmc_hip_trial_energies() calls of this context that passed their checks."""
+        return int(self.lib.mpmc_hip_trial_call_count(self.ctx))
 
     def energy(self):
         r = Result()

@@ -112,6 +112,27 @@ def load():
     lib.host_get_sync_counts.restype = None
     lib.host_effective_c9.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double]
     lib.host_effective_c9.restype = C.c_double
+    lib.host_qrot_evaluate.argtypes = [vp]
+    lib.host_qrot_levels.argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
+    lib.host_qrot_counts.argtypes = [vp, C.POINTER(C.c_long)]
+    lib.host_qrot_counts.restype = None
+    lib.host_last_movetype.argtypes = [vp]
+    lib.host_qrot_placements.argtypes = [vp, C.c_int, vp]
+    lib.host_qrot_times.argtypes = [vp]
+    lib.host_qrot_times.restype = None
+    lib.qrot_jacobi.argtypes = [C.c_int, vp, vp, vp, C.POINTER(C.c_long)]
+    lib.qrot_hamiltonian.argtypes = [C.c_int, C.c_double, vp, vp]
+    lib.host_get_spin_ratio.argtypes = [vp]
+    lib.host_get_spin_ratio.restype = C.c_double
+    lib.host_last_energy.argtypes = [vp]
+    lib.host_last_energy.restype = C.c_double
+    lib.qrot_hindered_grid.argtypes = [C.c_double, C.c_double, vp]
+    lib.qrot_hindered_grid.restype = None
+    lib.qrot_symmetry.argtypes = [vp, C.c_int, vp]
+    lib.qrot_basis.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
+    lib.qrot_basis.restype = C.c_double
+    lib.qrot_last_times.argtypes = [vp]
+    lib.qrot_last_times.restype = None
     lib.volume_change.argtypes = [vp]
     lib.volume_change.restype = None
     lib.revert_volume_change.argtypes = [vp]
@@ -128,7 +149,8 @@ def config_text(flags, extra=None):
              "midzuno_kihara_approx", "rd_crystal", "read_pqr_box", "calc_pressure", "polarvdw", "cdvdw",
              "cavity_autoreject_absolute", "cavity_bias", "cdvdw_exp_repulsion", "cdvdw_sig_repulsion",
              "cdvdw_9th_repulsion", "sg", "dreiding", "lj_buffered_14_7", "waldmanhagler", "halgren_mixing", "c6_mixing",
-             "polar_iterative", "polarizability_tensor", "polar_wolf_full"}
+             "polar_iterative", "polarizability_tensor", "polar_wolf_full", "quantum_rotation",
+             "quantum_rotation_hindered", "quantum_rotation_eigenvectors"}
     lines = []
     for k, v in flags.items():
         if k in ("polarvdw", "cdvdw") and isinstance(v, str):
@@ -277,10 +299,45 @@ class HostSystem:
         return b.reshape(3, 3)
 
     def next_movetype(self):
-        """What checkpoint() decided the next make_move() does: 'insert', 'remove', 'displace' or 'volume'."""
+        """What checkpoint() decided the next make_move() does: 'insert', 'remove', 'displace', 'volume' or 'spinflip'."""
         npt = np.zeros(5)
         self.lib.host_get_npt(self.ptr, npt.ctypes.data)
-        return ("insert", "remove", "displace", "volume")[int(npt[4])]
+        return ("insert", "remove", "displace", "volume", "spinflip")[int(npt[4])]
+
+    # ---- quantum_rotation
+    def qrot_evaluate(self):
+        """One quantum_system_rotational_energies() over the movable molecules (needs a completed energy() unless the
+        potential is the hindered rotor's); prints the DEBUG_QROT lines."""
+        if self.lib.host_qrot_evaluate(self.ptr) != 0:
+            raise engine.EngineError("quantum_rotation: the evaluation failed")
+
+    def rotational_levels(self):
+        """Per movable molecule, as the last evaluation left them: dict(levels [level_max] in K, symmetry [level_max]
+        (0 symmetric, 1 antisymmetric), rot_partfunc_g, rot_partfunc_u, rot_partfunc, nuclear_spin (0 para, 1 ortho))."""
+        out = []
+        while True:
+            lev, sym, pf, spin = np.zeros(81), np.zeros(81, dtype=np.int32), np.zeros(3), C.c_int(0)
+            n = self.lib.host_qrot_levels(self.ptr, len(out), lev.ctypes.data, sym.ctypes.data, pf.ctypes.data, C.byref(spin))
+            if n < 0:
+                return out
+            out.append(dict(levels=lev[:n].copy(), symmetry=sym[:n].copy(), rot_partfunc_g=pf[0], rot_partfunc_u=pf[1],
+                            rot_partfunc=pf[2], nuclear_spin=spin.value))
+
+    def spin_ratio(self):
+        """observables->spin_ratio of the last energy(): the para fraction of the movable molecules (0 without
+        quantum_rotation)."""
+        return float(self.lib.host_get_spin_ratio(self.ptr))
+
+    def last_energy(self):
+        """What the last energy() returned -- a rejected trial's too."""
+        return float(self.lib.host_last_energy(self.ptr))
+
+    def qrot_counts(self):
+        """Trial-energy calls the binding has made (one per movable molecule per evaluation), accepted and rejected
+        spin-flip moves."""
+        out = (C.c_long * 3)()
+        self.lib.host_qrot_counts(self.ptr, out)
+        return dict(trial_calls=int(out[0]), accept_spinflip=int(out[1]), reject_spinflip=int(out[2]))
 
     def set_volume_notes(self, on):
         """False: the binding ignores volume-move notes, so every volume step uploads the whole configuration."""

@@ -34,8 +34,47 @@ int host_apply_config(system_t *system, const char *text) {
         ((system->cavity_autoreject_scale <= 0.0) || (system->cavity_autoreject_scale > 1.78)))
         return 1;
     if (check_cavity_bias(system)) return 1; /* check_input.c:880-892 */
+    if (qrot_check(system)) return 1;        /* check_input.c:236-280 */
     return 0;
 }
+
+/* quantum_rotation: one evaluation for every movable molecule (0, or -1); the levels, symmetries and the three partition
+ * functions (g, u, the molecule's own) of the index-th movable molecule as the last evaluation left them, and the nuclear
+ * spin of that molecule: returns the number of levels (quantum_rotation_level_max), -1 when there is no such molecule; counters: [0] trial-energy calls of the binding, [1] accepted and [2] rejected spin-flip moves */
+int host_qrot_evaluate(system_t *system) { return quantum_system_rotational_energies(system); }
+int host_qrot_levels(system_t *system, int index, double *levels, int *symmetry, double partfunc[3], int *nuclear_spin) {
+    int k = 0;
+    for (molecule_t *m = system->molecules; m; m = m->next) {
+        if (m->frozen) continue;
+        if (k++ != index) continue;
+        for (int i = 0; i < system->quantum_rotation_level_max; i++) {
+            levels[i] = m->quantum_rotational_energies[i];
+            symmetry[i] = m->quantum_rotational_eigensymmetry[i];
+        }
+        partfunc[0] = m->rot_partfunc_g;
+        partfunc[1] = m->rot_partfunc_u;
+        partfunc[2] = m->rot_partfunc;
+        *nuclear_spin = m->nuclear_spin;
+        return system->quantum_rotation_level_max;
+    }
+    return -1;
+}
+double host_get_spin_ratio(system_t *system) { return system->observables->spin_ratio; }
+double host_last_energy(system_t *system) { return energy_hip_last_energy(system); }
+/* the 256 grid placements of the index-th movable molecule, xyz [256][n][3]; returns n (-1: no such molecule) */
+int host_qrot_placements(system_t *system, int index, double *xyz) {
+    int k = 0;
+    for (molecule_t *m = system->molecules; m; m = m->next)
+        if (!m->frozen && k++ == index) return qrot_placements(m, xyz);
+    return -1;
+}
+void host_qrot_times(double out[3]) { qrot_last_times(out); }
+void host_qrot_counts(system_t *system, long out[3]) {
+    out[0] = energy_hip_trial_calls(system);
+    out[1] = system->nodestats->accept_spinflip;
+    out[2] = system->nodestats->reject_spinflip;
+}
+int host_last_movetype(system_t *system) { return system->checkpoint->movetype; }
 
 /* what mc() does behind every step's accept / reject for one walker: the running means of the node statistics
  * (mc.c:362) and, at every corrtime, their average over the walkers -- here the one (mc.c:438, :470) */
@@ -56,6 +95,7 @@ int host_mc_steps(system_t *system, int nsteps) {
         if (system->cavity_bias) energy_hip_cavity_update(system); /* mc.c:245: the draws of its darts only */
         double e = energy(system);
         if (energy_hip_failed(system) || e != e) return -1;
+        if (system->quantum_rotation && quantum_system_rotational_energies(system)) return -1; /* mc.c:253-256 */
         checkpoint(system);
         system->avg_observables->counter = 1.0;
     }
@@ -65,6 +105,8 @@ int host_mc_steps(system_t *system, int nsteps) {
         make_move(system);
         const double final_energy = energy(system);
         if (energy_hip_failed(system)) return -1; /* device failure: stop, never count it as a reject */
+        const int spinflip_move = system->checkpoint->movetype == MOVETYPE_SPINFLIP;
+        if (system->quantum_rotation && spinflip_move && quantum_system_rotational_energies(system)) return -1; /* mc.c:304-308 */
         if (final_energy != final_energy || final_energy - final_energy != 0.0) {
             system->observables->energy = MAXVALUE;
             system->nodestats->boltzmann_factor = 0;
@@ -75,11 +117,13 @@ int host_mc_steps(system_t *system, int nsteps) {
             checkpoint(system);
             ++system->nodestats->accept;
             if (volume_move) ++system->nodestats->accept_volume;
+            if (spinflip_move) ++system->nodestats->accept_spinflip;
         } else {
             system->iter_success = 0;
             restore(system);
             ++system->nodestats->reject;
             if (volume_move) ++system->nodestats->reject_volume;
+            if (spinflip_move) ++system->nodestats->reject_spinflip;
         }
         step_statistics(system);
     }

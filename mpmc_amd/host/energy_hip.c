@@ -99,6 +99,7 @@ typedef struct shim_state {
     double *cav_darts; /* [cav_ndarts][3]: the last call's dart positions */
     int cav_ndarts, cav_darts_cap, cav_hits;
     int cav_failed; /* a device / ABI failure in a cavity call: the next energy_hip() reports it (sticky) */
+    long trial_calls;    /* energy_hip_trial_energies() calls that reached the engine */
     long sync_counts[3]; /* full uploads, mpmc_hip_edit_molecules calls that answered 0, molecules they removed + inserted */
     int timing;
     mpmc_hip_timings tsum;
@@ -203,7 +204,11 @@ static void countN(system_t *system) {
     system->observables->N = 0;
     system->observables->spin_ratio = 0;
     for (molecule_t *m = system->molecules; m; m = m->next)
-        if (!m->frozen) system->observables->N += 1.0;
+        if (!m->frozen) {
+            system->observables->N += 1.0;
+            /* energy.c:26-27, under quantum_rotation only: runs without it keep printing the 0 they always printed */
+            if (system->quantum_rotation && m->nuclear_spin == NUCLEAR_SPIN_PARA) system->observables->spin_ratio += 1.0;
+        }
 }
 void update_com(molecule_t *molecules) {
     for (molecule_t *m = molecules; m; m = m->next) {
@@ -594,6 +599,24 @@ void energy_hip_note_volume_change(system_t *system, const double *delta_per_mol
 void energy_hip_sync_counts(system_t *system, long out[3]) {
     shim_state *st = state_of(system, 0);
     for (int k = 0; k < 3; k++) out[k] = st ? st->sync_counts[k] : 0;
+}
+int energy_hip_trial_energies(system_t *system, molecule_t *molecule, int ntrial, const double *xyz, double *energy) {
+    shim_state *st = state_of(system, 0);
+    if (!st || !st->ctx || !st->uploaded) return hip_fail("trial_energies before the first energy()");
+    const resident_t *r = NULL;
+    for (int k = 0; k < st->nres && !r; k++)
+        if (st->res[k].mol == molecule) r = &st->res[k];
+    if (!r) return hip_fail("trial_energies: the molecule is not one the device holds");
+    ++st->trial_calls;
+    if (mpmc_hip_trial_energies(st->ctx, r->slot, r->natoms, ntrial, xyz, energy, NULL)) {
+        st->failed = 1;
+        return hip_fail("trial_energies");
+    }
+    return 0;
+}
+long energy_hip_trial_calls(system_t *system) {
+    shim_state *st = state_of(system, 0);
+    return st ? st->trial_calls : 0;
 }
 void energy_hip_set_volume_notes(system_t *system, int on) {
     shim_state *st = state_of(system, 1);

@@ -55,6 +55,12 @@ void energy_hip_set_volume_notes(system_t *system, int on);
  * mpmc_hip_edit_molecules() that were carried out (grand-canonical insertions / removals without a re-upload), out[2]
  * molecules those calls removed + inserted. */
 void energy_hip_sync_counts(system_t *system, long out[3]);
+/* quantum_rotation: the total energies of the configuration the device holds with `molecule` (a movable molecule of the
+ * lists, as of the last energy_hip()) at ntrial placements xyz [ntrial][natoms][3] -- mpmc_hip_trial_energies() on its
+ * slots.  Needs a completed energy_hip() on the lists as they are.  0, or -1 with energy_hip_failed() set.
+ * energy_hip_trial_calls(): such calls so far. */
+int energy_hip_trial_energies(system_t *system, molecule_t *molecule, int ntrial, const double *xyz, double *energy);
+long energy_hip_trial_calls(system_t *system);
 /* the per-atom c9 the engine is given: as read, or 3/4 alpha 6.7483345 c6 under midzuno_kihara_approx */
 double energy_hip_effective_c9(int midzuno_kihara_approx, double alpha, double c6, double c9);
 

@@ -62,6 +62,10 @@ static void setdefaults(system_t *system) {
     system->corrtime = 1;
     system->feynman_hibbs_order = 2;
     system->volume_change_factor = 0.25; /* input.c:1608-1611 */
+    system->quantum_rotation_level_max = QUANTUM_ROTATION_LEVEL_MAX; /* input.c:1648-1654 */
+    system->quantum_rotation_l_max = QUANTUM_ROTATION_L_MAX;
+    system->quantum_rotation_sum = QUANTUM_ROTATION_SUM;
+    system->spinflip_probability = 0;
     strcpy(system->job_name, "untitled");
 }
 
@@ -281,6 +285,16 @@ int do_command(system_t *system, char **token) {
     }
     FLAG("polar_wolf_full", polar_wolf_full);   /* input.c:530-538 */
     FLAG("polar_ewald_full", polar_ewald_full); /* input.c:508-516; refused by energy_hip.c, by name */
+    /* quantum_rotation, input.c:1271-1304 and :632 */
+    FLAG("quantum_rotation", quantum_rotation);
+    FLAG("quantum_rotation_hindered", quantum_rotation_hindered);
+    FLAG("quantum_rotation_eigenvectors", quantum_rotation_eigenvectors); /* (this layer's: print the eigenvectors too) */
+    REAL("quantum_rotation_hindered_barrier", quantum_rotation_hindered_barrier);
+    REAL("quantum_rotation_B", quantum_rotation_B);
+    INT("quantum_rotation_level_max", quantum_rotation_level_max);
+    INT("quantum_rotation_l_max", quantum_rotation_l_max);
+    INT("quantum_rotation_sum", quantum_rotation_sum);
+    REAL("spinflip_probability", spinflip_probability);
     FLAG("cuda", cuda);
     FLAG("hip", hip);
     TEXT("job_name", job_name);
@@ -563,6 +577,7 @@ static int check_system(system_t *system) {
         }
     }
     if (check_cavity_bias(system)) return -1;
+    if (qrot_check(system)) return -1;
     if (system->ensemble == ENSEMBLE_NPT && !(system->pressure > 0.0)) { /* check_input.c:673-678 */
         error("INPUT: invalid pressure set for NPT\n");
         return -1;

@@ -31,6 +31,8 @@ int main(int argc, char **argv) {
     } else if (system->ensemble == ENSEMBLE_TE) {
         const double e = energy(system);
         if (energy_hip_failed(system)) rc = -1;
+        /* single_point.c:15: solve for the rotational energy levels */
+        if (!rc && system->quantum_rotation && quantum_system_rotational_energies(system)) rc = -1;
         const observables_t *o = system->observables;
         snprintf(linebuf, MAXLINE,
                  "OUTPUT: potential energy = %.5f K\nOUTPUT: electrostatic energy = %.5f K\n"

@@ -266,6 +266,11 @@ void checkpoint(system_t *system) {
                 cp->movetype = MOVETYPE_INSERT;
             else
                 cp->movetype = MOVETYPE_REMOVE;
+        } else if (system->quantum_rotation) { /* checkpoint.c:57-65 */
+            if (get_rand(system) < system->spinflip_probability)
+                cp->movetype = MOVETYPE_SPINFLIP;
+            else
+                cp->movetype = MOVETYPE_DISPLACE;
         } else
             cp->movetype = MOVETYPE_DISPLACE;
     } else if (system->ensemble == ENSEMBLE_NPT) { /* checkpoint.c:84-98 */
@@ -280,7 +285,9 @@ void checkpoint(system_t *system) {
             else
                 cp->movetype = MOVETYPE_DISPLACE;
         }
-    } else
+    } else if (system->quantum_rotation && (get_rand(system) < system->spinflip_probability)) /* nvt, checkpoint.c:78-81 */
+        cp->movetype = MOVETYPE_SPINFLIP;
+    else
         cp->movetype = MOVETYPE_DISPLACE;
 
     /* randomly pick a (moveable) molecule: floor(rand * N) over the exchangeable ones in list order */
@@ -372,6 +379,12 @@ void make_move(system_t *system) {
             free_molecule(system, cp->molecule_altered);
             cp->molecule_altered = NULL;
             break;
+        case MOVETYPE_SPINFLIP: /* mc_moves.c:721-726: no coordinate changes */
+            if (get_rand(system) < 0.5)
+                cp->molecule_altered->nuclear_spin = NUCLEAR_SPIN_PARA;
+            else
+                cp->molecule_altered->nuclear_spin = NUCLEAR_SPIN_ORTHO;
+            break;
         default:
             translate(system, cp->molecule_altered, system->pbc, system->move_factor);
             rotate(system, cp->molecule_altered, system->pbc, system->rot_factor);
@@ -462,6 +475,9 @@ void boltzmann_factor(system_t *system, double initial_energy, double final_ener
                    (system->observables->N + 1) * system->temperature * log(v_new / v_old)) /
                  system->temperature);
     }
+    /* mc.c:95-96, :108-109: the rotational partition function ratio of the flipped molecule */
+    if (system->checkpoint->movetype == MOVETYPE_SPINFLIP && system->checkpoint->molecule_altered)
+        bf = system->checkpoint->molecule_altered->rot_partfunc * exp(-delta_energy / system->temperature);
     system->nodestats->boltzmann_factor = bf;
 }
 
@@ -536,6 +552,8 @@ int mc(system_t *system) {
     system->step = 0;
     initial_energy = energy(system);
     if (energy_hip_failed(system)) return -1; /* device failure: not a property of the configuration */
+    /* solve for the rotational energy levels (mc.c:253-256) */
+    if (system->quantum_rotation && quantum_system_rotational_energies(system)) return -1;
     /* one process per GPU started by a plain launcher: MPMC_HIP_RANK / MPMC_HIP_NRANKS / MPMC_HIP_ID_FILE name the
      * walker (the reference's `rank`, `size`: main.c:45-52); the communicator lives on the device energy() chose */
     const int size = getenv("MPMC_HIP_NRANKS") ? atoi(getenv("MPMC_HIP_NRANKS")) : 1;
@@ -575,6 +593,13 @@ int mc(system_t *system) {
             free(rcv);
             return -1;
         }
+        /* solve for the rotational energy levels (mc.c:304-308) */
+        if (system->quantum_rotation && system->checkpoint->movetype == MOVETYPE_SPINFLIP &&
+            quantum_system_rotational_energies(system)) {
+            error("MC: the device engine failed, stopping the chain\n");
+            free(rcv);
+            return -1;
+        }
         /* treat a bad contact as a reject */
         if (!isfinite(final_energy)) {
             system->observables->energy = MAXVALUE;
@@ -584,11 +609,14 @@ int mc(system_t *system) {
 
         /* Metropolis function */
         const int volume_move = system->checkpoint->movetype == MOVETYPE_VOLUME; /* mc.c:160-190 */
+        const int spinflip_move = system->checkpoint->movetype == MOVETYPE_SPINFLIP;
         if ((get_rand(system) < system->nodestats->boltzmann_factor) && (system->iter_success == 0)) {
             checkpoint(system);
             ++system->nodestats->accept;
             if (volume_move)
                 ++system->nodestats->accept_volume;
+            else if (spinflip_move)
+                ++system->nodestats->accept_spinflip;
             else
                 ++system->nodestats->accept_displace;
         } else {
@@ -597,6 +625,8 @@ int mc(system_t *system) {
             ++system->nodestats->reject;
             if (volume_move)
                 ++system->nodestats->reject_volume;
+            else if (spinflip_move)
+                ++system->nodestats->reject_spinflip;
             else
                 ++system->nodestats->reject_displace;
         }

@@ -29,8 +29,19 @@ extern "C" {
 
 enum { ENSEMBLE_UVT, ENSEMBLE_NVT, ENSEMBLE_SURF, ENSEMBLE_SURF_FIT, ENSEMBLE_NVE, ENSEMBLE_TE, ENSEMBLE_NPT,
        ENSEMBLE_REPLAY };
-enum { MOVETYPE_INSERT, MOVETYPE_REMOVE, MOVETYPE_DISPLACE, MOVETYPE_VOLUME };
+enum { MOVETYPE_INSERT, MOVETYPE_REMOVE, MOVETYPE_DISPLACE, MOVETYPE_VOLUME, MOVETYPE_SPINFLIP };
 enum { DAMPING_OFF, DAMPING_LINEAR, DAMPING_EXPONENTIAL }; /* defines.h:91-93 */
+enum { NUCLEAR_SPIN_PARA, NUCLEAR_SPIN_ORTHO };             /* defines.h:94-95 */
+/* quantum_rotation (defines.h:69-78; qrot.c) */
+#define QUANTUM_ROTATION_SYMMETRIC 0
+#define QUANTUM_ROTATION_ANTISYMMETRIC 1
+#define QUANTUM_ROTATION_SYMMETRY_POINTS 64
+#define QUANTUM_ROTATION_LEVEL_MAX 36
+#define QUANTUM_ROTATION_L_MAX 5
+#define QUANTUM_ROTATION_GRID 16
+#define QUANTUM_ROTATION_SUM 10
+#define QROT_L_LIMIT 8                                         /* the basis the reference hard-codes (rotational_basis.c) */
+#define QROT_DIM_LIMIT ((QROT_L_LIMIT + 1) * (QROT_L_LIMIT + 1)) /* 81 */
 
 typedef struct _atom {
     int id, bond_id;
@@ -53,6 +64,13 @@ typedef struct _molecule {
     double mass;
     int frozen;
     double com[3], wrapped_com[3];
+    /* quantum_rotation (structs.h:62-73): the spin isomer, the molecule's rotational partition functions and its levels.
+     * Inline arrays: copy_molecule() copies them with the molecule, restore() brings them back with it.  The eigenvectors
+     * are not kept (quantum_rotation_eigenvectors prints them where they are made). */
+    int nuclear_spin;
+    double rot_partfunc_g, rot_partfunc_u, rot_partfunc;
+    double quantum_rotational_energies[QROT_DIM_LIMIT];
+    int quantum_rotational_eigensymmetry[QROT_DIM_LIMIT];
     atom_t *atoms;
     struct _molecule *next;
 } molecule_t;
@@ -73,6 +91,7 @@ typedef struct _nodestats {
     int accept, reject;
     int accept_displace, reject_displace;
     int accept_volume, reject_volume; /* npt (mc.c:164-165, :189-190) */
+    int accept_spinflip, reject_spinflip; /* quantum_rotation (mc.c:161-162, :186-187) */
     double boltzmann_factor, acceptance_rate, acceptance_rate_displace;
     double polarization_iterations;
     double cavity_bias_probability; /* cavity_bias: open grid points / all grid points of this step (cavity.c:85-107) */
@@ -157,6 +176,11 @@ typedef struct _system {
     int surf_preserve, surf_decomp, surf_global_axis_on, surf_virial, surf_print_level, surf_output_on;
     int surf_preserve_rotation_on;     /* the keyword was given: its six angles (radians) follow */
     double surf_preserve_rotation[6];  /* alpha1 beta1 gamma1 alpha2 beta2 gamma2 */
+    /* quantum_rotation (structs.h:465-468, input.c:1271-1304, check_input.c:236-280): rotational levels of every movable
+     * molecule in the field of the others (qrot.c), and the spin-flip move (spinflip_probability) */
+    int quantum_rotation, quantum_rotation_hindered, quantum_rotation_level_max, quantum_rotation_l_max, quantum_rotation_sum;
+    int quantum_rotation_eigenvectors; /* not a reference keyword: print the eigenvectors too (the reference does under DEBUG) */
+    double quantum_rotation_B, quantum_rotation_hindered_barrier, spinflip_probability;
     int iter_success; /* the reference's convergence-FAILURE flag */
     int natoms;
     char job_name[MAXLINE], pqr_input[MAXLINE], energy_output[MAXLINE], pqr_output[MAXLINE];
@@ -210,6 +234,31 @@ int surface(system_t *system, int device);
 const char *surface_refused(const system_t *system);
 int surface_loop_count(double top, double step);
 int read_frame(FILE *fp, system_t *system);
+/* quantum_rotation (reference src/quantum_rotation/; qrot.c).  quantum_system_rotational_energies(): for every movable
+ * molecule the potential on the 16 x 16 Gauss-Legendre grid -- ONE energy_hip_trial_energies() call of 256 placements, or
+ * the hindered-rotor potential -- the Hamiltonian in the Y_lm basis, its levels, their g / u symmetry (random points from
+ * the run's generator) and the partition functions; prints the reference's DEBUG_QROT lines.  0, or -1 when the device
+ * failed.  The pieces, for tests and tools:
+ *   qrot_check()         the keyword block's checks (qrot_options(), check_input.c:236-280) and this layer's refusals;
+ *   qrot_placements()    xyz [256][n][3], index p * 16 + t: align_molecule() then rotate_spherical() from the unmodified
+ *                        coordinates; returns the site count, -1 when no site is off the centre of mass;
+ *   qrot_hamiltonian()   h [dim][dim][2] from V[t][p] (sin(theta) included), dim = (l_max + 1)^2; 0, or -1 (l_max outside
+ *                        0 .. 8, or no memory for the table of Y_lm on the grid: h is not written);
+ *   qrot_jacobi()        cyclic Jacobi for a complex Hermitian matrix: ascending eigenvalues, evec [dim][dim][2] with row i
+ *                        the i-th eigenvector; returns the sweeps taken, -1 when 64 sweeps did not converge;
+ *   qrot_symmetry()      determine_rotational_eigensymmetry() of one eigenvector (draws 128 numbers);
+ *   qrot_basis()         Y_lm(theta, phi), type 0 = real part, 1 = imaginary part. */
+int quantum_system_rotational_energies(system_t *system);
+int qrot_check(system_t *system);
+int qrot_placements(const molecule_t *molecule, double *xyz);
+void qrot_grid(double theta[QUANTUM_ROTATION_GRID], double phi[QUANTUM_ROTATION_GRID], double weights[QUANTUM_ROTATION_GRID]);
+void qrot_hindered_grid(double B, double barrier, double V[QUANTUM_ROTATION_GRID][QUANTUM_ROTATION_GRID]);
+int qrot_hamiltonian(int l_max, double B, const double V[QUANTUM_ROTATION_GRID][QUANTUM_ROTATION_GRID], double *h);
+int qrot_jacobi(int dim, const double *h, double *eval, double *evec, long *rotations);
+int qrot_symmetry(system_t *system, int l_max, const double *evec);
+double qrot_basis(int type, int l, int m, double theta, double phi);
+/* wall time of the last evaluation's parts, summed over the molecules: scan, Hamiltonian, eigen-solve + symmetry (seconds) */
+void qrot_last_times(double out[3]);
 void write_observables(FILE *fp, system_t *system, observables_t *o, double core_temp);
 void checkpoint(system_t *system);
 void restore(system_t *system);

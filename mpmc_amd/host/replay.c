@@ -114,6 +114,11 @@ int replay_trajectory(system_t *system) {
             rc = -1;
             break;
         }
+        /* replay.c:69: solve for the rotational energy levels */
+        if (system->quantum_rotation && quantum_system_rotational_energies(system)) {
+            rc = -1;
+            break;
+        }
         if (system->fp_energy) write_observables(system->fp_energy, system, system->observables, system->temperature);
     }
     fclose(finput);
