@@ -1,6 +1,8 @@
 """The longdouble reference of the coupled-dipole van der Waals mode (tests/vdw_reference.py) checked against independent
 arithmetic on the CPU: its Jacobi eigenvalues against LAPACK in fp64 and against mpmath at 40 digits, its pair sums against
-plain double loops, and the conditions the GPU parity cases rely on (tests/vdw_cases.py)."""
+plain double loops, and the conditions the GPU parity cases rely on (tests/vdw_cases.py); the certified reference of the large
+cases (prerotated_eigen_energy) against the Jacobi iteration, and its record tests/golden/vdw_large.npz against the inputs'
+hashes, fp64 LAPACK and one full regeneration."""
 import math
 
 import numpy as np
@@ -134,3 +136,81 @@ def test_contact_reference_counts():
     assert n == 2 and 0.5e-9 < margin < 2e-9  # the two edge pairs sit 1e-9 A from the scale, on either side
     for name in ("box43", "box130"):  # liquid density: nobody is that close
         assert vr.close_contacts(vc.system(name), f, vc.SCALE)[0] == 0
+
+
+# ---- the certified reference of the large cases (vdw_reference.prerotated_eigen_energy) and its record
+@pytest.mark.parametrize("n", vc.SITE_COUNTS)
+def test_prerotated_reference_against_jacobi(n):
+    name = "box%d" % n
+    Cm, _ = vr.c_matrix(vc.system(name), vc.FLAGS)
+    e, err, info = vr.prerotated_eigen_energy(Cm)
+    want = vc.reference(name)["e_total"]  # eigen_energy(jacobi_eigenvalues(C))
+    assert abs(e - want) <= err, (float(e - want), float(err))
+    assert err <= 1e-2 * vc.TOL * e
+    assert info["defect"] <= 1e-15 and info["b_min"] > 0 and info["off"] <= 1e-13 * info["norm"]
+
+
+def test_prerotated_reference_refuses_a_spectrum_that_reaches_zero():
+    Cm, _ = vr.c_matrix(vc.system("clip"), vc.CLIP_FLAGS)
+    with pytest.raises(ValueError):
+        vr.prerotated_eigen_energy(Cm)
+
+
+_large_matrix = {}
+
+
+def _large_eigvalsh(name):
+    if name not in _large_matrix:
+        Cm, _ = vr.c_matrix(vc.system(name), vc.FLAGS)
+        _large_matrix[name] = np.linalg.eigvalsh(Cm.astype(np.float64))
+    return _large_matrix[name]
+
+
+@pytest.mark.parametrize("name", vc.LARGE)
+def test_large_record_belongs_to_the_inputs(name):
+    rec = vc.large_reference(name)
+    s = vc.system(name)
+    assert rec["rows"] == vc.LARGE_ROWS[name] == vc.active_rows(s)
+    assert rec["sha256"] == vc.input_hash(s, rec["rows"])
+    # what the sizes are for: trips of the 1024-thread loops of vdw_sum_kernel (k < n) and vdw_reflect_kernel (1 + tid < n - 1)
+    trips = {"rows1023": (1, 1), "rows1026": (2, 1), "rows1029": (2, 2), "big1": (2, 2), "big2": (3, 3), "frame": (2, 2)}[name]
+    assert (-(-rec["rows"] // 1024), -(-(rec["rows"] - 2) // 1024)) == trips
+    if name == "frame":
+        assert 1027 <= vc.FRAME_ROWS <= 1100 and rec["rows"] <= 1150
+        assert float(rec["e_iso"]) > 0.95 * float(rec["e_total"])  # vdw_energy is their small difference
+
+
+@pytest.mark.parametrize("name", vc.LARGE)
+def test_large_record_against_lapack_fp64(name):
+    rec = vc.large_reference(name)
+    w = _large_eigvalsh(name)
+    assert len(w) == rec["rows"] and w.min() >= vc.COND * w.max() and rec["b_min"] >= vc.COND * rec["b_max"]
+    assert abs(w.min() - rec["b_min"]) <= 1e-12 * w.max() and abs(w.max() - rec["b_max"]) <= 1e-12 * w.max()
+    e64 = vr.CONV * LD(float(np.sqrt(w).sum()))
+    assert abs(e64 - rec["e_total"]) <= 1e-14 * rec["e_total"], float((e64 - rec["e_total"]) / rec["e_total"])
+    assert 0 < rec["err_e_total"] <= 1e-2 * vc.TOL * float(rec["e_total"])
+    assert 0 <= rec["err_e_iso"] <= 1e-2 * vc.TOL * float(rec["e_iso"])
+
+
+def test_large_record_regenerated():
+    """the one slow test of this file: rows1023 made again by the generator, whole, and compared with the file"""
+    import importlib.util
+    import os
+
+    path = os.path.join(os.path.dirname(vc.GOLDEN_LARGE), "make_vdw_large.py")
+    spec = importlib.util.spec_from_file_location("make_vdw_large", path)
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    new, rec = gen.record("rows1023"), vc.large_reference("rows1023")
+    assert str(new["sha256"]) == rec["sha256"] and int(new["rows"]) == rec["rows"]
+    for t in vc.LARGE_TERMS + tuple("abs_" + t for t in vc.LARGE_TERMS):
+        v = LD(new[t][0]) + LD(new[t][1])
+        # the eigenvalue sums start from LAPACK's basis, which may differ between builds: each is within its certified
+        # error of the truth; the pair sums are the same longdouble operations
+        if t in ("e_total", "e_iso"):
+            slack = float(new["err_" + t]) + rec["err_" + t]
+        else:
+            slack = 1e-17 * abs(float(rec["abs_" + t.replace("abs_", "")]))
+        assert abs(v - rec[t]) <= slack, (t, float(v - rec[t]), slack)
+    assert abs(float(new["b_min"]) - rec["b_min"]) <= 1e-12 * rec["b_max"]
+    assert float(new["err_e_total"]) <= 2 * rec["err_e_total"]
