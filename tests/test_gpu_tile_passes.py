@@ -97,6 +97,7 @@ def test_an_event_leaves_the_bits_of_a_fresh_context(mode, event):
     e.load_system(s, f)
     before = tp.snapshot(e)
     assert before["status"] == 0 and before[m["term"]] != 0.0
+    assert (before["close_contacts"] > 0) == (mode in tp.AUTOREJECT_MODES)  # the count is on in those, and not trivially 0
     s, f, probe, fields = tp.EVENTS[event](e, m, s, f, before)
     got = tp.snapshot(e)
     kept = tp.E_ISO_FIELDS if mode == "polarvdw" and event in tp.E_ISO_KEPT_BY else ()

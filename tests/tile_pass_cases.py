@@ -151,11 +151,28 @@ EVENT_MODES = {
                                           lambda e, s, f: e.set_axilrod_teller(s, enable=False),
                                           lambda e, s, f: e.set_axilrod_teller(s)),
 }
+# the lj and phahst modes once more with the close-contact count on (cavity_autoreject_absolute; the count rides in the pair
+# kernel's tile partials): every event then also holds close_contacts to a fresh context.  At 3.0 A the reference counts
+# 203 pairs in synth.s_pol(320) and 30 in phahst_cases' c320.
+AUTOREJECT = dict(cavity_autoreject_absolute=1, cavity_autoreject_scale=3.0)
+AUTOREJECT_MODES = {"lj+autoreject": "lj", "phahst+autoreject": "phahst"}
+
+
+def _with_autoreject(base):
+    def make():
+        m = EVENT_MODES[base]()
+        return dict(m, flags=dict(m["flags"], **AUTOREJECT))
+    return make
+
+
+for _name, _base in AUTOREJECT_MODES.items():
+    EVENT_MODES[_name] = _with_autoreject(_base)
 
 
 def snapshot(e):
     """every Result field of an energy() and every mode's getters behind it (zeros outside their mode)"""
-    return dict(e.energy(), three_body=e.three_body_energy(), vdw_energy=e.vdw_energy(), **e.vdw_terms())
+    return dict(e.energy(), three_body=e.three_body_energy(), vdw_energy=e.vdw_energy(), close_contacts=e.close_contacts(),
+                **e.vdw_terms())
 
 
 def _per_molecule(s):
@@ -222,7 +239,7 @@ EVENTS = {
     "full_passes": _ev_full_passes,
     "leave_and_back": _ev_leave_and_back,
 }
-FH4_MODES = ("lj", "rd_crystal", "lj-waldmanhagler")  # (polarvdw refuses feynman_hibbs)
+FH4_MODES = ("lj", "rd_crystal", "lj-waldmanhagler", "lj+autoreject")  # (polarvdw refuses feynman_hibbs)
 EVENT_CELLS = [(mode, ev) for mode in EVENT_MODES for ev in EVENTS if ev != "fh4" or mode in FH4_MODES]
 # polarvdw keeps e_iso per molecule type for as long as the mode stays on, through a box change and an upload (vdw.c:262-320;
 # tests/test_gpu_vdw.py::test_scale_box_leaves_the_bits_of_a_fresh_context): behind these events it is the value from before,

@@ -277,6 +277,59 @@ def close_contacts(system, flags, scale):
     return int((rimg < scale).sum()), float(np.abs(rimg - scale).min())
 
 
+def contact_table(system, flags, scale, present=None):
+    """close_contacts() pair by pair: dict(i, j, rimg, counted) over the pairs i < j of two present atoms (`present`: a
+    boolean mask, default all) on different molecules, in (i, j) order.  The decision rimg < scale is the fp64 one of
+    close_contacts(); rimg is evaluated in longdouble from the fp64 coordinates at the lattice image the fp64 path picked,
+    so that rimg - scale shows how far from the scale the decision was taken."""
+    pos = np.asarray(system["pos"], dtype=np.float64)
+    mol = np.asarray(system["molecule"])  # (ids, not runs: the slots of an edited context carry holes)
+    ok = np.ones(len(pos), dtype=bool) if present is None else np.asarray(present, dtype=bool)
+    _, rb, _ = pbc(system["basis"], flags.get("pbc_cutoff", 0.0))
+    i, j = np.triu_indices(len(pos), 1)
+    keep = (mol[i] != mol[j]) & ok[i] & ok[j]
+    i, j = i[keep], j[keep]
+    if not i.size:
+        return dict(i=i, j=j, rimg=np.zeros(0, LD), counted=np.zeros(0, dtype=bool), scale=scale)
+    d = pos[i] - pos[j]
+    image, _, rimg64, _ = minimum_image(system["basis"], rb, d)
+    shift = image.astype(LD) @ np.asarray(system["basis"], dtype=np.float64).astype(LD)
+    e = d.astype(LD) - shift
+    rimg = np.sqrt((e * e).sum(axis=1, dtype=LD))
+    return dict(i=i, j=j, rimg=rimg, counted=rimg64 < scale, scale=scale)
+
+
+def contact_tiles(table):
+    """{(i // 64, j // 64): counted pairs of the tile}, the tiles with none left out"""
+    out = {}
+    for i, j in zip(table["i"][table["counted"]], table["j"][table["counted"]]):
+        t = (int(i) // 64, int(j) // 64)
+        out[t] = out.get(t, 0) + 1
+    return out
+
+
+def explain(got, want):
+    """Lines that say which 64 x 64 tiles (i // 64, j // 64) account for the difference between two contact tables of
+    the same atoms (`got`: of the input as something else saw it; `want`: the reference's), with the pairs of each such
+    tile that are counted in one table only and their rimg - scale; in the style of pair_reference.explain_energy."""
+    def pairs(t):
+        return {(int(a), int(b)): float(r - LD(t["scale"])) for a, b, r, c in zip(t["i"], t["j"], t["rimg"], t["counted"]) if c}
+
+    g, w = pairs(got), pairs(want)
+    lines = []
+    tiles = sorted(set((a // 64, b // 64) for a, b in set(g) ^ set(w)))
+    for t in tiles:
+        extra = sorted(p for p in set(g) - set(w) if (p[0] // 64, p[1] // 64) == t)
+        missing = sorted(p for p in set(w) - set(g) if (p[0] // 64, p[1] // 64) == t)
+        lines.append("tile (%d, %d): %+d (%d extra, %d missing)" % (t[0], t[1], len(extra) - len(missing), len(extra),
+                                                                    len(missing)))
+        lines += ["  extra pair (%d, %d), rimg - scale = %.3e" % (p[0], p[1], g[p]) for p in extra[:5]]
+        lines += ["  missing pair (%d, %d), rimg - scale = %.3e" % (p[0], p[1], w[p]) for p in missing[:5]]
+    if not lines:
+        lines = ["the two tables count the same pairs (%d)" % len(w)]
+    return lines
+
+
 def vdw_terms(system, flags, iso_cache=None):
     """Everything the mode adds, in longdouble: e_total, e_iso, lr_corr, vdw_energy = e_total - e_iso + lr_corr,
     repulsion, repulsion_lrc, rd_energy; the sums of |terms| as abs_<name>; lam = the eigenvalues of C (ascending, before
