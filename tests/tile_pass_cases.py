@@ -226,6 +226,7 @@ def _ev_full_passes(e, m, s, f, before):
 def _ev_leave_and_back(e, m, s, f, before):
     m["leave"](e, s, f)
     outside = snapshot(e)
+    assert outside["status"] == 0
     m["back"](e, s, f)
     return s, f, outside, (m["term"],)
 
@@ -241,6 +242,34 @@ EVENTS = {
 }
 FH4_MODES = ("lj", "rd_crystal", "lj-waldmanhagler", "lj+autoreject")  # (polarvdw refuses feynman_hibbs)
 EVENT_CELLS = [(mode, ev) for mode in EVENT_MODES for ev in EVENTS if ev != "fh4" or mode in FH4_MODES]
+
+
+# Further inputs of leave_and_back only: from one mode that owns rd_energy straight into another and back, where the cells
+# above leave a mode only towards plain Lennard-Jones.  rd_crystal and set_rd_form are context settings, so nothing is
+# uploaded in between; the state outside is the other mode's (status 0, another rd_energy), and both cases span 3 blocks.
+def _crystal_to_form(e, s, f):
+    e.set_rd_crystal(0)
+    e.set_rd_form("lj", "lb")
+
+
+def _form_to_crystal(e, s, f):
+    e.set_rd_form("off")
+    e.set_rd_crystal(RDC_ORDER)
+
+
+def _crystal_to_lj_wh(e, s, f):
+    e.set_rd_crystal(0)
+    e.set_rd_form("lj", "waldmanhagler")
+
+
+MODE_TO_MODE = {
+    "rd_crystal>lj-lb": lambda: _event_mode(rc.system("t150"), rc.flags("lrc", RDC_ORDER), "rd_energy", _crystal_to_form,
+                                            _form_to_crystal),
+    "lj-waldmanhagler>rd_crystal": lambda: dict(_rd_form_mode("lj", "waldmanhagler", rf.POLAR), leave=_form_to_crystal,
+                                                back=_crystal_to_lj_wh),
+}
+EVENT_MODES.update(MODE_TO_MODE)
+EVENT_CELLS += [(mode, "leave_and_back") for mode in MODE_TO_MODE]
 # polarvdw keeps e_iso per molecule type for as long as the mode stays on, through a box change and an upload (vdw.c:262-320;
 # tests/test_gpu_vdw.py::test_scale_box_leaves_the_bits_of_a_fresh_context): behind these events it is the value from before,
 # not the one a fresh context makes, and so are the two sums it enters
