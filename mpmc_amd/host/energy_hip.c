@@ -48,6 +48,23 @@ typedef struct {
     int first, natoms, frozen;
 } cavity_entry_t;
 
+/* Everything a full upload sends beside the atoms and the box: fill_settings() derives it from the keywords, full_upload()
+ * applies it, and energy_hip_begin() compares the whole record -- a mode that has a member here cannot go stale. */
+typedef struct {
+    mpmc_hip_params params;
+    mpmc_hip_disp_params disp;
+    mpmc_hip_rd_form_params rd_form; /* the pair potential and mixing rule */
+    mpmc_hip_thole_model thole;      /* the dipole tensor (polar_damp_type, polar_wolf_full) */
+    int rdc_order;                   /* rd_crystal_order (0: rd_crystal off) */
+    int vdw_on;                      /* polarvdw */
+    int exact;                       /* the exact dipoles (polarization with polar_iterative off) */
+    int axilrod_teller, midzuno_kihara_approx; /* the second decides the per-atom c9 that is sent (0 while the first is off) */
+    double ar_scale;                 /* cavity_autoreject_scale (0: cavity_autoreject_absolute off) */
+} sent_settings_t;
+
+/* the per-atom columns of the host image; atom_columns() says which member of atom_t each one is */
+enum { COL_X, COL_Y, COL_Z, COL_Q, COL_ALPHA, COL_EPS, COL_SIG, COL_MASS, COL_C6, COL_C8, COL_C10, COL_C9, COL_OMEGA, NCOL };
+
 typedef struct shim_state {
     system_t *system;
     mpmc_hip_ctx *ctx;
@@ -55,23 +72,14 @@ typedef struct shim_state {
     int device;   /* -1: choose (rank % device count) */
     int capacity; /* atoms the context was created for */
     int uploaded; /* a configuration is resident */
-    int rdc_order; /* rd_crystal_order as sent with that upload (0: rd_crystal off) */
-    mpmc_hip_rd_form_params rd_form; /* the pair potential and mixing rule as sent with that upload */
-    int vdw_on;    /* polarvdw as sent with that upload */
-    mpmc_hip_thole_model thole; /* the dipole tensor (polar_damp_type, polar_wolf_full) as sent with that upload */
-    int exact;     /* the exact dipoles (polarization with polar_iterative off) as sent with that upload */
-    double ar_scale; /* cavity_autoreject_scale as sent with that upload (0: cavity_autoreject_absolute off) */
+    sent_settings_t sent; /* as sent with that upload */
     int failed;   /* device / ABI failure of the last call */
     double last_energy; /* what the last energy_hip_end() returned (restore() takes a rejected trial's out of the observables) */
-    mpmc_hip_params params; /* as last sent */
     /* host image of the device, by DEVICE SLOT (the engine keeps its own atom order once molecules are inserted
-     * or removed): coordinates as last sent, and the parameters that tell species apart */
+     * or removed): coordinates as last sent, and the parameters that tell species apart.  c6 / c8 / c10 (disp_expansion) and
+     * omega (polarvdw) go with every full upload; c9 (axilrod_teller) is kept as read, its effective value is what is sent */
     int cap;
-    double *x, *y, *z, *q, *alpha, *eps, *sig, *mass;
-    double *c6, *c8, *c10; /* disp_expansion: sent with every full upload (mpmc_hip_set_dispersion) */
-    double *c9;            /* axilrod_teller: per atom as read; its effective value goes with every full upload */
-    double *omega;         /* polarvdw: sent with every full upload (mpmc_hip_set_vdw) */
-    mpmc_hip_disp_params disp; /* as last sent */
+    double *col[NCOL];
     /* the resident molecules in LIST order */
     resident_t *res, *res2;
     int nres, res_cap;
@@ -125,10 +133,10 @@ static shim_state *state_of(system_t *system, int create) {
 }
 
 static void free_image(shim_state *st) {
-    free(st->x); free(st->y); free(st->z); free(st->q); free(st->alpha); free(st->eps); free(st->sig); free(st->mass);
-    free(st->c6); free(st->c8); free(st->c10); free(st->c9); free(st->omega);
-    st->x = st->y = st->z = st->q = st->alpha = st->eps = st->sig = st->mass = NULL;
-    st->c6 = st->c8 = st->c10 = st->c9 = st->omega = NULL;
+    for (int c = 0; c < NCOL; c++) {
+        free(st->col[c]);
+        st->col[c] = NULL;
+    }
     st->cap = 0;
 }
 
@@ -290,6 +298,27 @@ static void fill_disp_params(const system_t *s, mpmc_hip_disp_params *d) {
     d->schmidt_mixing = s->schmidt_mixing;
 }
 
+static void fill_settings(const system_t *s, sent_settings_t *t) {
+    memset(t, 0, sizeof(*t)); /* padding too: the record is compared with memcmp() */
+    fill_params(s, &t->params);
+    fill_disp_params(s, &t->disp);
+    fill_rd_form(s, &t->rd_form);
+    fill_thole_model(s, &t->thole);
+    t->rdc_order = s->rd_crystal ? s->rd_crystal_order : 0;
+    t->vdw_on = (s->polarvdw != 0);
+    t->exact = (s->polarization && !s->polar_iterative);
+    t->axilrod_teller = (s->axilrod_teller != 0);
+    t->midzuno_kihara_approx = (t->axilrod_teller && s->midzuno_kihara_approx);
+    t->ar_scale = s->cavity_autoreject_absolute ? s->cavity_autoreject_scale : 0.0;
+}
+
+/* The dense energy modes, where every change of N used to be an upload: only there does the walk look two places ahead.  On
+ * the standard path it stays as it was: where it gives up and uploads decides the slot order, the slot order the rounding
+ * of the sums, and the bits of such chains are on record (tests/golden). */
+static int dense_mode(const sent_settings_t *t) {
+    return t->disp.disp_expansion || t->axilrod_teller || t->rdc_order || t->rd_form.form;
+}
+
 /* What the engine does not compute must not be asked of it silently (the twin of the `cuda on` guard,
  * src/io/check_input.c:325-341, extended to the whole of energy()). */
 static const char *unsupported(const system_t *s) {
@@ -405,15 +434,24 @@ static int device_failed(shim_state *st) {
 static int image_reserve(shim_state *st, int cap) {
     if (st->cap >= cap) return 0;
     free_image(st);
-    const size_t b = (size_t)cap * sizeof(double);
-    st->x = malloc(b); st->y = malloc(b); st->z = malloc(b); st->q = malloc(b); st->alpha = malloc(b);
-    st->eps = malloc(b); st->sig = malloc(b); st->mass = malloc(b);
-    st->c6 = malloc(b); st->c8 = malloc(b); st->c10 = malloc(b); st->c9 = malloc(b); st->omega = malloc(b);
-    if (!(st->x && st->y && st->z && st->q && st->alpha && st->eps && st->sig && st->mass && st->c6 && st->c8 && st->c10 &&
-          st->c9 && st->omega))
-        return -1;
+    for (int c = 0; c < NCOL; c++)
+        if (!(st->col[c] = malloc((size_t)cap * sizeof(double)))) return -1;
     st->cap = cap;
     return 0;
+}
+
+/* one atom's value in every column of the image */
+static void atom_columns(const atom_t *a, double v[NCOL]) {
+    v[COL_X] = a->pos[0]; v[COL_Y] = a->pos[1]; v[COL_Z] = a->pos[2];
+    v[COL_Q] = a->charge; v[COL_ALPHA] = a->polarizability; v[COL_EPS] = a->epsilon; v[COL_SIG] = a->sigma;
+    v[COL_MASS] = a->mass;
+    v[COL_C6] = a->c6; v[COL_C8] = a->c8; v[COL_C10] = a->c10; v[COL_C9] = a->c9; v[COL_OMEGA] = a->omega;
+}
+
+/* system->pbc->basis, row-major, as the engine takes it */
+static void basis_of(const system_t *system, double basis[9]) {
+    for (int p = 0; p < 3; p++)
+        for (int r = 0; r < 3; r++) basis[3 * p + r] = system->pbc->basis[p][r];
 }
 
 static int residents_reserve(shim_state *st, int n) {
@@ -471,6 +509,13 @@ static int full_upload(shim_state *st, system_t *system) {
         error("ENERGY: HIP engine: out of host memory\n");
         return -1;
     }
+    sent_settings_t *sent = &st->sent;
+    double *const *col = st->col;
+    fill_settings(system, sent);
+    /* (in front of the parameters: the exact mode takes a set with neither polar_max_iter nor polar_precision) */
+    if (mpmc_hip_set_exact_polar(st->ctx, sent->exact)) return hip_fail("set_exact_polar");
+    /* (likewise: under polar_damp_type off the engine takes a set without polar_damp) */
+    if (mpmc_hip_set_thole_model(st->ctx, &sent->thole)) return hip_fail("set_thole_model");
     int *mol = malloc((n > 0 ? n : 1) * sizeof(int));
     uint8_t *fz = malloc(n > 0 ? n : 1);
     if (!mol || !fz) {
@@ -480,14 +525,14 @@ static int full_upload(shim_state *st, system_t *system) {
     }
     int i = 0;
     st->nres = 0;
+    st->uploaded = 0; /* until every call below has been taken: a failure half-way leaves nothing to update or edit */
     for (int mi = 0; mi < nm; mi++) {
         molecule_t *m = st->mols[mi];
         const int first = i;
         for (atom_t *a = m->atoms; a; a = a->next, i++) {
-            st->x[i] = a->pos[0]; st->y[i] = a->pos[1]; st->z[i] = a->pos[2];
-            st->q[i] = a->charge; st->alpha[i] = a->polarizability; st->eps[i] = a->epsilon; st->sig[i] = a->sigma;
-            st->mass[i] = a->mass;
-            st->c6[i] = a->c6; st->c8[i] = a->c8; st->c10[i] = a->c10; st->c9[i] = a->c9; st->omega[i] = a->omega;
+            double v[NCOL];
+            atom_columns(a, v);
+            for (int c = 0; c < NCOL; c++) st->col[c][i] = v[c];
             mol[i] = mi; /* list position: distinct per molecule even if PQR ids repeat */
             fz[i] = (uint8_t)(a->frozen != 0);
         }
@@ -495,29 +540,20 @@ static int full_upload(shim_state *st, system_t *system) {
         r->mol = m; r->atoms = m->atoms; r->slot = first; r->natoms = i - first; r->frozen = (m->frozen != 0);
     }
     double basis[9];
-    for (int p = 0; p < 3; p++)
-        for (int r = 0; r < 3; r++) basis[3 * p + r] = system->pbc->basis[p][r];
-    fill_params(system, &st->params);
-    /* (in front of the parameters: the exact mode takes a set with neither polar_max_iter nor polar_precision) */
-    st->exact = (system->polarization && !system->polar_iterative);
-    if (mpmc_hip_set_exact_polar(st->ctx, st->exact)) return hip_fail("set_exact_polar");
-    /* (likewise: under polar_damp_type off the engine takes a set without polar_damp) */
-    fill_thole_model(system, &st->thole);
-    if (mpmc_hip_set_thole_model(st->ctx, &st->thole)) return hip_fail("set_thole_model");
-    int rc = mpmc_hip_set_params(st->ctx, &st->params);
+    basis_of(system, basis);
+    int rc = mpmc_hip_set_params(st->ctx, &sent->params);
     if (!rc) rc = mpmc_hip_set_box(st->ctx, basis, system->pbc->cutoff);
-    if (!rc) rc = mpmc_hip_upload(st->ctx, n, st->x, st->y, st->z, st->q, st->alpha, st->eps, st->sig, st->mass, mol, fz);
+    if (!rc)
+        rc = mpmc_hip_upload(st->ctx, n, col[COL_X], col[COL_Y], col[COL_Z], col[COL_Q], col[COL_ALPHA], col[COL_EPS], col[COL_SIG],
+                             col[COL_MASS], mol, fz);
     free(mol); free(fz);
     if (rc) return hip_fail("upload");
-    st->rdc_order = system->rd_crystal ? system->rd_crystal_order : 0;
-    if (mpmc_hip_set_rd_crystal(st->ctx, st->rdc_order)) return hip_fail("set_rd_crystal");
-    fill_rd_form(system, &st->rd_form);
-    if (mpmc_hip_set_rd_form(st->ctx, &st->rd_form)) return hip_fail("set_rd_form");
-    fill_disp_params(system, &st->disp);
+    if (mpmc_hip_set_rd_crystal(st->ctx, sent->rdc_order)) return hip_fail("set_rd_crystal");
+    if (mpmc_hip_set_rd_form(st->ctx, &sent->rd_form)) return hip_fail("set_rd_form");
     /* (an upload leaves the context on Lennard-Jones: nothing to say unless the PHAHST potential is asked for) */
-    if (st->disp.disp_expansion && mpmc_hip_set_dispersion(st->ctx, &st->disp, n, st->c6, st->c8, st->c10))
+    if (sent->disp.disp_expansion && mpmc_hip_set_dispersion(st->ctx, &sent->disp, n, col[COL_C6], col[COL_C8], col[COL_C10]))
         return hip_fail("set_dispersion");
-    if (system->axilrod_teller) {
+    if (sent->axilrod_teller) {
         /* the engine takes the EFFECTIVE per-atom coefficient */
         double *eff = malloc((n > 0 ? n : 1) * sizeof(double));
         if (!eff) {
@@ -525,13 +561,12 @@ static int full_upload(shim_state *st, system_t *system) {
             return -1;
         }
         for (int k = 0; k < n; k++)
-            eff[k] = energy_hip_effective_c9(system->midzuno_kihara_approx, st->alpha[k], st->c6[k], st->c9[k]);
+            eff[k] = energy_hip_effective_c9(sent->midzuno_kihara_approx, col[COL_ALPHA][k], col[COL_C6][k], col[COL_C9][k]);
         rc = mpmc_hip_set_axilrod_teller(st->ctx, 1, n, eff);
         free(eff);
         if (rc) return hip_fail("set_axilrod_teller");
     }
-    st->vdw_on = (system->polarvdw != 0);
-    if (st->vdw_on) {
+    if (sent->vdw_on) {
         /* type ids: the first-seen order of moleculetype, which is what the reference's e_iso list is keyed by
          * (vdw.c:262-320) */
         int *type = malloc((n > 0 ? n : 1) * sizeof(int));
@@ -549,12 +584,11 @@ static int full_upload(shim_state *st, system_t *system) {
             if (t == nseen) seen[nseen++] = m;
             for (atom_t *a = m->atoms; a; a = a->next) type[k++] = t;
         }
-        rc = mpmc_hip_set_vdw(st->ctx, 1, n, st->omega, type);
+        rc = mpmc_hip_set_vdw(st->ctx, 1, n, col[COL_OMEGA], type);
         free(type); free(seen);
         if (rc) return hip_fail("set_vdw");
     }
-    st->ar_scale = system->cavity_autoreject_absolute ? system->cavity_autoreject_scale : 0.0;
-    if (mpmc_hip_set_autoreject(st->ctx, st->ar_scale)) return hip_fail("set_autoreject");
+    if (mpmc_hip_set_autoreject(st->ctx, sent->ar_scale)) return hip_fail("set_autoreject");
     st->uploaded = 1;
     st->in_sync = 1;
     st->nnotes = 0;
@@ -632,8 +666,8 @@ void energy_hip_set_volume_notes(system_t *system, int on) {
  * configuration again, < 0 on error. */
 static int apply_volume_notes(shim_state *st, system_t *system) {
     double basis[9];
-    for (int p = 0; p < 3; p++)
-        for (int r = 0; r < 3; r++) basis[3 * p + r] = system->pbc->basis[p][r];
+    basis_of(system, basis);
+    double *x = st->col[COL_X], *y = st->col[COL_Y], *z = st->col[COL_Z];
     for (int v = 0; v < st->nvol; v++) {
         const double *d = st->vol_delta[v];
         const int rc = mpmc_hip_scale_box(st->ctx, basis, system->pbc->cutoff, st->nres, d);
@@ -642,7 +676,7 @@ static int apply_volume_notes(shim_state *st, system_t *system) {
         for (int k = 0; k < st->nres; k++) {
             const int s = st->res[k].slot;
             for (int a = 0; a < st->res[k].natoms; a++) {
-                st->x[s + a] += d[3 * k + 0]; st->y[s + a] += d[3 * k + 1]; st->z[s + a] += d[3 * k + 2];
+                x[s + a] += d[3 * k + 0]; y[s + a] += d[3 * k + 1]; z[s + a] += d[3 * k + 2];
             }
         }
     }
@@ -656,10 +690,10 @@ static int same_place(const shim_state *st, const molecule_t *m, const resident_
     if (r->frozen) /* never moved (mc_moves.c picks among the others): no comparison of coordinates */
         return m->atoms == r->atoms || natoms_of(m) == r->natoms;
     int k = 0, moved = 0;
-    const int s = r->slot;
+    const double *x = st->col[COL_X] + r->slot, *y = st->col[COL_Y] + r->slot, *z = st->col[COL_Z] + r->slot;
     for (const atom_t *a = m->atoms; a; a = a->next, k++) {
         if (k == r->natoms) return 0;
-        moved |= (a->pos[0] != st->x[s + k]) | (a->pos[1] != st->y[s + k]) | (a->pos[2] != st->z[s + k]);
+        moved |= (a->pos[0] != x[k]) | (a->pos[1] != y[k]) | (a->pos[2] != z[k]);
     }
     return k == r->natoms && !moved;
 }
@@ -671,28 +705,27 @@ static int same_species(const shim_state *st, const molecule_t *m, const residen
     const int s = r->slot;
     for (const atom_t *a = m->atoms; a; a = a->next, k++) {
         if (k == r->natoms) return 0;
-        if (a->charge != st->q[s + k] || a->polarizability != st->alpha[s + k] || a->epsilon != st->eps[s + k] ||
-            a->sigma != st->sig[s + k] || a->mass != st->mass[s + k] || a->c6 != st->c6[s + k] || a->c8 != st->c8[s + k] ||
-            a->c10 != st->c10[s + k] || a->c9 != st->c9[s + k] || a->omega != st->omega[s + k])
-            return 0;
+        double v[NCOL];
+        atom_columns(a, v);
+        for (int c = COL_Q; c < NCOL; c++)
+            if (v[c] != st->col[c][s + k]) return 0;
     }
     return k == r->natoms;
 }
 
 /* re-send the coordinates of resident r from list node m if they differ */
 static int sync_coordinates(shim_state *st, molecule_t *m, resident_t *r) {
-    const int s = r->slot;
+    double *x = st->col[COL_X] + r->slot, *y = st->col[COL_Y] + r->slot, *z = st->col[COL_Z] + r->slot;
     int k = 0, moved = 0;
-    for (atom_t *a = m->atoms; a; a = a->next, k++)
-        moved |= (a->pos[0] != st->x[s + k]) | (a->pos[1] != st->y[s + k]) | (a->pos[2] != st->z[s + k]);
+    for (atom_t *a = m->atoms; a; a = a->next, k++) moved |= (a->pos[0] != x[k]) | (a->pos[1] != y[k]) | (a->pos[2] != z[k]);
     r->mol = m;
     r->atoms = m->atoms;
     if (!moved) return 0;
     k = 0;
     for (atom_t *a = m->atoms; a; a = a->next, k++) {
-        st->x[s + k] = a->pos[0]; st->y[s + k] = a->pos[1]; st->z[s + k] = a->pos[2];
+        x[k] = a->pos[0]; y[k] = a->pos[1]; z[k] = a->pos[2];
     }
-    if (mpmc_hip_update_atoms(st->ctx, s, k, st->x + s, st->y + s, st->z + s)) return hip_fail("update_atoms");
+    if (mpmc_hip_update_atoms(st->ctx, r->slot, k, x, y, z)) return hip_fail("update_atoms");
     return 0;
 }
 
@@ -725,146 +758,147 @@ static int sync_noted(shim_state *st) {
     return 0;
 }
 
-/* Bring the device in line with the molecule lists without a re-upload, whatever the caller did to them since the
- * last call.  The residents (in the list order of the last call) are aligned with the list as it is now, front to
- * back: a node that holds exactly what a resident's slots hold is that resident; otherwise the node is NEW if the
- * node behind it is the resident (a grand-canonical insertion goes in front of the molecule it was copied from,
- * mc_moves.c:626-637), the resident is GONE if the node is the next resident (a removal, or restore() taking an
- * insertion back), in the dense modes the same two one place further on (restore() undoing one trial and make_move()
- * making the next can leave two new nodes or two gone residents side by side, and read as displacements they would shift
- * every molecule behind them by one until the walk gives up), and else the node is the resident DISPLACED if it is the same species
- * site by site.  Only what
- * the device holds matters -- which atoms at which coordinates, and for the Gauss-Seidel solvers in which order --
- * so "the rejected insertion was taken out and its neighbour displaced" may legitimately be carried out as "the
- * rejected insertion's slots get the neighbour's new coordinates and the neighbour's slots are freed".
+/* What the walk decided: the new resident table (in `out`, n entries in list order) and what has to happen for the device
+ * to hold it.  The limits are the engine's: beyond them mpmc_hip_edit_molecules() would answer 1. */
+enum { kMol = 8, kAt = 16, kMoved = 16 };
+typedef struct {
+    int n;
+    int ngone, gone[kMol];     /* residents (indices of the old table) whose slots are given up */
+    int nfresh, fresh[kMol];   /* entries of the new table that have no slots yet (slot -1) */
+    int nmoved, moved[kMoved]; /* entries of the new table whose coordinates differ from the image */
+} walk_plan_t;
+
+/* The deciding half of sync_walk(): how the molecule list lines up with the residents, whatever the caller did to the lists
+ * since the last call.  No engine call; nothing changes but `out` and `plan`.  The residents (in the list order of the last
+ * call) are aligned with the list as it is now, front to back: a node that holds exactly what a resident's slots hold is
+ * that resident; otherwise the node is NEW if the node behind it is the resident (a grand-canonical insertion goes in front
+ * of the molecule it was copied from, mc_moves.c:626-637), the resident is GONE if the node is the next resident (a removal,
+ * or restore() taking an insertion back), in the dense modes the same two one place further on (restore() undoing one trial
+ * and make_move() making the next can leave two new nodes or two gone residents side by side, and read as displacements they
+ * would shift every molecule behind them by one until the walk gives up), and else the node is the resident DISPLACED if it
+ * is the same species site by site.  Only what the device holds matters -- which atoms at which coordinates, and for the
+ * Gauss-Seidel solvers in which order -- so "the rejected insertion was taken out and its neighbour displaced" may
+ * legitimately be carried out as "the rejected insertion's slots get the neighbour's new coordinates and the neighbour's
+ * slots are freed".  Returns 1 when there is no such alignment within the limits. */
+static int plan_walk(const shim_state *st, molecule_t *const *mols, int nm, int two_ahead, resident_t *out, walk_plan_t *plan) {
+    const resident_t *res = st->res;
+    const int nres = st->nres;
+    int i = 0, j = 0, n = 0;
+    memset(plan, 0, sizeof(*plan));
+    while (i < nm || j < nres) {
+        enum { KEPT, GONE, FRESH, MOVED } what;
+        if (i < nm && j < nres && same_place(st, mols[i], &res[j])) what = KEPT;
+        else if (i < nm && j + 1 < nres && same_place(st, mols[i], &res[j + 1])) what = GONE;
+        else if (i + 1 < nm && j < nres && same_place(st, mols[i + 1], &res[j])) what = FRESH;
+        /* two residents in a row are gone: a rejected insertion taken back and the molecule beside it removed */
+        else if (two_ahead && i < nm && j + 2 < nres && same_place(st, mols[i], &res[j + 2])) what = GONE;
+        /* two new nodes in a row: a rejected removal put back and an insertion beside it */
+        else if (two_ahead && i + 2 < nm && j < nres && same_place(st, mols[i + 2], &res[j])) what = FRESH;
+        else if (i < nm && j < nres && same_species(st, mols[i], &res[j])) what = MOVED;
+        else if (i == nm) what = GONE;
+        else if (j == nres) what = FRESH;
+        else return 1;
+        if (what == GONE) {
+            if (plan->ngone == kMol) return 1;
+            plan->gone[plan->ngone++] = j++;
+        } else if (what == FRESH) {
+            molecule_t *m = mols[i++];
+            const resident_t r = {m, m->atoms, -1, natoms_of(m), m->frozen != 0};
+            if (plan->nfresh == kMol || r.natoms > kAt) return 1;
+            plan->fresh[plan->nfresh++] = n;
+            out[n++] = r;
+        } else { /* the resident, in this node now */
+            if (what == MOVED) {
+                if (plan->nmoved == kMoved) return 1;
+                plan->moved[plan->nmoved++] = n;
+            }
+            out[n] = res[j++];
+            out[n].atoms = mols[i]->atoms;
+            out[n++].mol = mols[i++];
+        }
+    }
+    plan->n = n;
+    return 0;
+}
+
+/* The removals and insertions of a plan in one call: the engine removes first, so that an insertion of the same size can
+ * take the slots, and answers 1 before it has changed anything.  Afterwards the image holds the new molecules in the slots
+ * the engine gave them, and `out` knows those slots.  Returns the engine's 1, < 0 on error. */
+static int edit_residents(shim_state *st, resident_t *out, const walk_plan_t *plan) {
+    double buf[NCOL][kMol][kAt]; /* the new molecules, column by column as read ... */
+    double eff_c9[kMol][kAt];    /* ... and the c9 the engine is given in place of buf[COL_C9] */
+    mpmc_hip_molecule ins[kMol];
+    int rfirst[kMol], rcount[kMol], slot[kMol];
+    for (int f = 0; f < plan->ngone; f++) {
+        rfirst[f] = st->res[plan->gone[f]].slot;
+        rcount[f] = st->res[plan->gone[f]].natoms;
+    }
+    for (int f = 0; f < plan->nfresh; f++) {
+        const resident_t *r = &out[plan->fresh[f]];
+        int k = 0;
+        for (const atom_t *a = r->mol->atoms; a; a = a->next, k++) {
+            double v[NCOL];
+            atom_columns(a, v);
+            for (int c = 0; c < NCOL; c++) buf[c][f][k] = v[c];
+            eff_c9[f][k] = energy_hip_effective_c9(st->sent.midzuno_kihara_approx, v[COL_ALPHA], v[COL_C6], v[COL_C9]);
+        }
+        mpmc_hip_molecule *m = &ins[f];
+        m->count = k; m->frozen = r->frozen;
+        m->x = buf[COL_X][f]; m->y = buf[COL_Y][f]; m->z = buf[COL_Z][f]; m->charge = buf[COL_Q][f];
+        m->polarizability = buf[COL_ALPHA][f]; m->epsilon = buf[COL_EPS][f]; m->sigma = buf[COL_SIG][f]; m->mass = buf[COL_MASS][f];
+        m->c6 = buf[COL_C6][f]; m->c8 = buf[COL_C8][f]; m->c10 = buf[COL_C10][f]; m->c9 = eff_c9[f];
+        slot[f] = -1;
+    }
+    const int rc = mpmc_hip_edit_molecules(st->ctx, plan->ngone, rfirst, rcount, plan->nfresh, ins, slot);
+    if (rc < 0) return hip_fail("edit_molecules");
+    if (rc > 0) return 1;
+    st->sync_counts[1]++;
+    st->sync_counts[2] += plan->ngone + plan->nfresh;
+    for (int f = 0; f < plan->nfresh; f++) {
+        const int s = slot[f], k = ins[f].count;
+        if (s < 0 || s + k > st->cap) {
+            st->uploaded = 0; /* (cannot happen: the image was reserved for the context's capacity) */
+            return 1;
+        }
+        for (int c = 0; c < NCOL; c++) memcpy(st->col[c] + s, buf[c][f], (size_t)k * sizeof(double));
+        out[plan->fresh[f]].slot = s;
+    }
+    return 0;
+}
+
+/* Bring the device in line with the molecule lists without a re-upload: plan_walk() decides, and this carries the plan out --
+ * the edit call, the displaced molecules' coordinates, the new resident table, and for the Gauss-Seidel solvers the order.
  * Returns 1 when the engine wants the whole configuration again (no alignment, too many edits, context full,
  * solver mode without incremental edits), < 0 on error. */
 static int sync_walk(shim_state *st, system_t *system) {
     const int nm = list_to_array(st, system);
     if (nm < 0 || residents_reserve(st, nm > st->nres ? nm : st->nres)) return 1;
-    molecule_t **mols = st->mols;
     resident_t *res = st->res, *out = st->res2;
-    int gone[8], ngone = 0, fresh[8], nfresh = 0, moved[16], nmoved = 0;
-    int i = 0, j = 0, n2 = 0, natoms = 0;
-    /* The look two places ahead (above) is taken in the dense modes only, where every change of N used to be an upload.
-     * On the standard path the walk stays as it was: where it gives up and uploads decides the slot order, the slot order
-     * the rounding of the sums, and the bits of such chains are on record (tests/golden). */
-    const int two_ahead = st->disp.disp_expansion || system->axilrod_teller || st->rdc_order || st->rd_form.form;
-    while (i < nm || j < st->nres) {
-        if (i < nm && j < st->nres && same_place(st, mols[i], &res[j])) {
-            out[n2] = res[j++];
-            out[n2].atoms = mols[i]->atoms;
-            out[n2++].mol = mols[i++];
-        } else if (i < nm && j + 1 < st->nres && same_place(st, mols[i], &res[j + 1])) {
-            if (ngone == 8) return 1;
-            gone[ngone++] = j++;
-        } else if (i + 1 < nm && j < st->nres && same_place(st, mols[i + 1], &res[j])) {
-            if (nfresh == 8) return 1;
-            fresh[nfresh++] = n2;
-            out[n2].mol = mols[i++]; out[n2].atoms = out[n2].mol->atoms; out[n2].slot = -1; out[n2].natoms = natoms_of(out[n2].mol);
-            out[n2].frozen = (out[n2].mol->frozen != 0);
-            n2++;
-        } else if (two_ahead && i < nm && j + 2 < st->nres && same_place(st, mols[i], &res[j + 2])) {
-            /* two residents in a row are gone: a rejected insertion taken back and the molecule beside it removed */
-            if (ngone == 8) return 1;
-            gone[ngone++] = j++;
-        } else if (two_ahead && i + 2 < nm && j < st->nres && same_place(st, mols[i + 2], &res[j])) {
-            /* two new nodes in a row: a rejected removal put back and an insertion beside it */
-            if (nfresh == 8) return 1;
-            fresh[nfresh++] = n2;
-            out[n2].mol = mols[i++]; out[n2].atoms = out[n2].mol->atoms; out[n2].slot = -1; out[n2].natoms = natoms_of(out[n2].mol);
-            out[n2].frozen = (out[n2].mol->frozen != 0);
-            n2++;
-        } else if (i < nm && j < st->nres && same_species(st, mols[i], &res[j])) {
-            if (nmoved == 16) return 1;
-            moved[nmoved++] = n2;
-            out[n2] = res[j++];
-            out[n2].atoms = mols[i]->atoms;
-            out[n2++].mol = mols[i++];
-        } else if (i == nm) {
-            if (ngone == 8) return 1;
-            gone[ngone++] = j++;
-        } else if (j == st->nres) {
-            if (nfresh == 8) return 1;
-            fresh[nfresh++] = n2;
-            out[n2].mol = mols[i++]; out[n2].atoms = out[n2].mol->atoms; out[n2].slot = -1; out[n2].natoms = natoms_of(out[n2].mol);
-            out[n2].frozen = (out[n2].mol->frozen != 0);
-            n2++;
-        } else
-            return 1;
+    walk_plan_t plan;
+    if (plan_walk(st, st->mols, nm, dense_mode(&st->sent), out, &plan)) return 1;
+    const int edited = plan.ngone || plan.nfresh;
+    if (edited) {
+        const int rc = edit_residents(st, out, &plan);
+        if (rc) return rc;
     }
-    /* one call for both lists: the engine removes first, so that an insertion of the same size can take the slots, and
-     * answers 1 before it has changed anything */
-    if (ngone || nfresh) {
-        enum { kMol = 8, kAt = 16 }; /* the engine's limits: beyond them it would answer 1 */
-        double buf[13][kMol][kAt]; /* x y z q alpha eps sig mass c6 c8 c10 c9(effective) c9(as read) */
-        double dw[kMol][kAt];
-        mpmc_hip_molecule ins[kMol];
-        int rfirst[kMol], rcount[kMol], slot[kMol];
-        for (int f = 0; f < ngone; f++) {
-            rfirst[f] = res[gone[f]].slot;
-            rcount[f] = res[gone[f]].natoms;
-        }
-        for (int f = 0; f < nfresh; f++) {
-            resident_t *r = &out[fresh[f]];
-            int k = 0;
-            for (atom_t *a = r->mol->atoms; a; a = a->next, k++) {
-                if (k == kAt) return 1;
-                buf[0][f][k] = a->pos[0]; buf[1][f][k] = a->pos[1]; buf[2][f][k] = a->pos[2];
-                buf[3][f][k] = a->charge; buf[4][f][k] = a->polarizability; buf[5][f][k] = a->epsilon;
-                buf[6][f][k] = a->sigma; buf[7][f][k] = a->mass;
-                buf[8][f][k] = a->c6; buf[9][f][k] = a->c8; buf[10][f][k] = a->c10;
-                buf[11][f][k] = energy_hip_effective_c9(system->midzuno_kihara_approx, a->polarizability, a->c6, a->c9);
-                buf[12][f][k] = a->c9;
-                dw[f][k] = a->omega;
-            }
-            mpmc_hip_molecule *m = &ins[f];
-            m->count = k; m->frozen = r->frozen;
-            m->x = buf[0][f]; m->y = buf[1][f]; m->z = buf[2][f]; m->charge = buf[3][f]; m->polarizability = buf[4][f];
-            m->epsilon = buf[5][f]; m->sigma = buf[6][f]; m->mass = buf[7][f];
-            m->c6 = buf[8][f]; m->c8 = buf[9][f]; m->c10 = buf[10][f]; m->c9 = buf[11][f];
-            slot[f] = -1;
-        }
-        const int rc = mpmc_hip_edit_molecules(st->ctx, ngone, rfirst, rcount, nfresh, ins, slot);
-        if (rc < 0) return hip_fail("edit_molecules");
-        if (rc > 0) return 1;
-        st->sync_counts[1]++;
-        st->sync_counts[2] += ngone + nfresh;
-        for (int f = 0; f < nfresh; f++) {
-            resident_t *r = &out[fresh[f]];
-            const int s = slot[f], k = ins[f].count;
-            if (s < 0 || s + k > st->cap) {
-                st->uploaded = 0; /* (cannot happen: the image was reserved for the context's capacity) */
-                return 1;
-            }
-            for (int a = 0; a < k; a++) {
-                st->x[s + a] = buf[0][f][a]; st->y[s + a] = buf[1][f][a]; st->z[s + a] = buf[2][f][a];
-                st->q[s + a] = buf[3][f][a]; st->alpha[s + a] = buf[4][f][a]; st->eps[s + a] = buf[5][f][a];
-                st->sig[s + a] = buf[6][f][a]; st->mass[s + a] = buf[7][f][a];
-                st->c6[s + a] = buf[8][f][a]; st->c8[s + a] = buf[9][f][a]; st->c10[s + a] = buf[10][f][a];
-                st->c9[s + a] = buf[12][f][a];
-                st->omega[s + a] = dw[f][a];
-            }
-            r->slot = s;
-        }
-    }
-    for (int f = 0; f < nmoved; f++) {
-        const int rc = sync_coordinates(st, out[moved[f]].mol, &out[moved[f]]);
+    for (int f = 0; f < plan.nmoved; f++) {
+        const int rc = sync_coordinates(st, out[plan.moved[f]].mol, &out[plan.moved[f]]);
         if (rc) return rc;
     }
     st->res = out;
     st->res2 = res;
-    st->nres = n2;
-    for (int k = 0; k < n2; k++) natoms += out[k].natoms;
-    if ((ngone || nfresh) && system->polarization && (system->polar_gs || system->polar_gs_ranked)) {
+    st->nres = plan.n;
+    int natoms = 0;
+    for (int k = 0; k < plan.n; k++) natoms += out[k].natoms;
+    if (edited && system->polarization && (system->polar_gs || system->polar_gs_ranked)) {
         /* Gauss-Seidel sweeps walk the atoms in list order (the reference's atom_array, thole_iterative.c:27-59), and the
          * device slots no longer follow the lists: state the order of the polarizable sites */
         int *order = malloc((natoms > 0 ? natoms : 1) * sizeof(int));
         if (!order) return 1;
         int k = 0;
-        for (int r = 0; r < n2; r++)
+        for (int r = 0; r < plan.n; r++)
             for (int a = 0; a < out[r].natoms; a++)
-                if (st->alpha[out[r].slot + a] != 0.0) order[k++] = out[r].slot + a;
+                if (st->col[COL_ALPHA][out[r].slot + a] != 0.0) order[k++] = out[r].slot + a;
         const int rc = mpmc_hip_set_sweep_order(st->ctx, k, order);
         free(order);
         if (rc) return hip_fail("set_sweep_order");
@@ -1154,22 +1188,11 @@ int energy_hip_begin(system_t *system) {
     const int scale_box = st->ctx && st->uploaded && st->in_sync && st->nvol > 0;
     if (scale_box) need_upload = 0;
     if (!need_upload) {
-        mpmc_hip_params now;
-        fill_params(system, &now); /* simulated annealing moves the temperature, surface fits the charges ... */
-        if (memcmp(&now, &st->params, sizeof(now))) need_upload = 1;
-        mpmc_hip_disp_params dnow;
-        fill_disp_params(system, &dnow);
-        if (memcmp(&dnow, &st->disp, sizeof(dnow))) need_upload = 1;
-        if ((system->rd_crystal ? system->rd_crystal_order : 0) != st->rdc_order) need_upload = 1;
-        mpmc_hip_rd_form_params fnow;
-        fill_rd_form(system, &fnow);
-        if (memcmp(&fnow, &st->rd_form, sizeof(fnow))) need_upload = 1;
-        if ((system->polarvdw != 0) != st->vdw_on) need_upload = 1;
-        if ((system->polarization && !system->polar_iterative) != st->exact) need_upload = 1;
-        mpmc_hip_thole_model tnow;
-        fill_thole_model(system, &tnow);
-        if (memcmp(&tnow, &st->thole, sizeof(tnow))) need_upload = 1;
-        if ((system->cavity_autoreject_absolute ? system->cavity_autoreject_scale : 0.0) != st->ar_scale) need_upload = 1;
+        sent_settings_t now;
+        fill_settings(system, &now); /* simulated annealing moves the temperature, surface fits the charges ... */
+        /* (byte for byte, the doubles too: a cavity_autoreject_scale that goes from 0 to -0 uploads again where != saw no
+         * change, and one that is NaN no longer uploads on every call) */
+        if (memcmp(&now, &st->sent, sizeof(now))) need_upload = 1;
     }
     if (!need_upload && scale_box) {
         const int rc = apply_volume_notes(st, system);
@@ -1233,6 +1256,13 @@ int energy_hip_begin(system_t *system) {
     return 0;
 }
 
+/* an error return of energy_hip_end() */
+static double end_failed(shim_state *st, const char *what) {
+    hip_fail(what);
+    device_failed(st);
+    return NAN;
+}
+
 /* Second half: the bookkeeping that does not need the energies runs while the device works, then the result
  * is collected into system->observables. */
 double energy_hip_end(system_t *system) {
@@ -1243,11 +1273,7 @@ double energy_hip_end(system_t *system) {
     countN(system);                /* energy.c:213 */
     const double t3 = now_s();
     mpmc_hip_result r;
-    if (mpmc_hip_energy_end(st->ctx, &r)) {
-        hip_fail("energy");
-        device_failed(st);
-        return NAN;
-    }
+    if (mpmc_hip_energy_end(st->ctx, &r)) return end_failed(st, "energy");
     const double t4 = now_s();
     g_prof[2] += t3 - t2; g_prof[3] += t4 - t3;
     if (++g_prof_calls == 64) { /* steady state only: forget the upload and the first steps */
@@ -1274,11 +1300,7 @@ double energy_hip_end(system_t *system) {
     observables_t *o = system->observables;
     if (system->cavity_autoreject_absolute) {
         long long contacts = 0;
-        if (mpmc_hip_get_close_contacts(st->ctx, &contacts)) {
-            hip_fail("get_close_contacts");
-            device_failed(st);
-            return NAN;
-        }
+        if (mpmc_hip_get_close_contacts(st->ctx, &contacts)) return end_failed(st, "get_close_contacts");
         if (contacts > 0) {
             /* energy.c:99-102, :187-194: a bad contact.  The potential energy is MAXVALUE, the rejection is counted, and
              * the terms of the observables stay what the previous call left (the reference skips their evaluation; here
@@ -1297,17 +1319,11 @@ double energy_hip_end(system_t *system) {
     o->polarization_energy = r.polarization_energy;
     o->energy = r.energy;
     o->three_body_energy = 0.0; /* energy.c:148-151, :194: part of o->energy when axilrod_teller is on */
-    if (system->axilrod_teller && mpmc_hip_get_three_body_energy(st->ctx, &o->three_body_energy)) {
-        hip_fail("get_three_body_energy");
-        device_failed(st);
-        return NAN;
-    }
+    if (system->axilrod_teller && mpmc_hip_get_three_body_energy(st->ctx, &o->three_body_energy))
+        return end_failed(st, "get_three_body_energy");
     /* energy.c:165-177: assigned only while polarvdw is on and rd_only is off; part of o->energy then */
-    if (system->polarvdw && !system->rd_only && mpmc_hip_get_vdw_energy(st->ctx, &o->vdw_energy)) {
-        hip_fail("get_vdw_energy");
-        device_failed(st);
-        return NAN;
-    }
+    if (system->polarvdw && !system->rd_only && mpmc_hip_get_vdw_energy(st->ctx, &o->vdw_energy))
+        return end_failed(st, "get_vdw_energy");
     o->dipole_rrms = r.dipole_rrms;
     system->nodestats->polarization_iterations = (double)r.polar_iterations;
     if (r.iter_success) system->iter_success = 1; /* thole_iterative.c:207; mc.c:347 resets it */
